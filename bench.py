@@ -117,6 +117,34 @@ def accuracy_block(pkg, eng, n, dev, samples=256, periodic=True):
                                "(tests/test_gpu_parity.py)")}
 
 
+DUMP_ROWS = 1 << 19    # rows kept by --dump-outputs: 2^19 * (acc 24 + pm 24 + old 8 + cost 4) B = 30 MB
+
+
+def dump_outputs(eng, n, dev, out_dir, periodic=True):
+    """--dump-outputs: what compute_accelerations() handed its caller in the last timed step -- GravAccel (tree), GravPM,
+    OldAcc, GravCost, caller order -- as <out_dir>/<name>.npy.  All rows up to DUMP_ROWS particles, above that the same seeded
+    sample of DUMP_ROWS rows (ascending) every run, so two builds can be compared row for row."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    d_acc = torch.empty((n, 3), dtype=torch.float64, device=dev)
+    d_pm = torch.empty((n, 3), dtype=torch.float64, device=dev) if periodic else None
+    d_old = torch.empty(n, dtype=torch.float64, device=dev)
+    d_cost = torch.empty(n, dtype=torch.float32, device=dev)
+    eng.get_accel_device(acc_ptr=d_acc.data_ptr(), pm_ptr=d_pm.data_ptr() if periodic else None, old_ptr=d_old.data_ptr(),
+                         cost_ptr=d_cost.data_ptr())
+    if n > DUMP_ROWS:
+        idx = np.sort(np.random.default_rng(20261015).choice(n, DUMP_ROWS, replace=False))
+    else:
+        idx = np.arange(n)
+    sel = torch.from_numpy(idx.astype(np.int64)).to(dev)
+    arrays = {"grav_accel": d_acc, "grav_pm": d_pm, "old_acc": d_old, "grav_cost": d_cost}
+    for name, d in arrays.items():
+        if d is not None:
+            np.save(os.path.join(out_dir, name + ".npy"), d[sel].cpu().numpy())
+    del d_acc, d_pm, d_old, d_cost, arrays
+    torch.cuda.synchronize()
+
+
 def make_box(pkg, n, L, n_gravs, seed):
     rng = np.random.default_rng(seed)
     chunk = 1 << 22
@@ -278,7 +306,14 @@ def main():
     ap.add_argument("--config", default="c4", choices=["c1", "c2", "c3", "c4", "c5"],
                     help="BASELINE.json config: c4 (default, the metric's) | c5: 256M N_GRAVS=3 PMGRID=1024 | c3: 16M N_GRAVS=1 PMGRID=256 | "
                          "c2: 4M Plummer tree-only | c1: the reference's own GalaxyCollision.IC (60k particles, N_GRAVS=2, tree-only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's accelerations, PM accelerations, OldAcc and GravCost (caller "
+                         "order; a fixed seeded sample of %d rows above that many particles) as DIR/<name>.npy (--gpus 1 only)" % DUMP_ROWS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.gpus != 1:
+        raise SystemExit("--dump-outputs needs --gpus 1: with more tasks no process holds every particle's result")
     if args.config == "c3":
         args.log2n, args.ngravs, args.wiring, args.pmgrid = (24 if args.log2n == 26 else args.log2n), 1, "newton", args.pmgrid or 256
     if args.config == "c5":    # 256M, N_GRAVS=3, PMGRID=1024: the 8-GPU config of BASELINE.json; it also fits ONE 288 GB MI355X
@@ -419,6 +454,9 @@ def main():
     shard_first, shard_count = eng.shard()
     if domain:
         shard_count = eng.num_local()
+
+    if args.dump_outputs:
+        dump_outputs(eng, n, dev, args.dump_outputs, periodic=not treeonly)
 
     if rank == 0:
         ms_per_step = dt / args.steps * 1e3

@@ -112,7 +112,8 @@ def _worker(rank, world, port, out_dir, name):
     assert np.array_equal(lcount, cnt)
     # ---- the cut
     owner = np.zeros(nl, dtype=np.int32)
-    assert L.ngravs_host_split(lcount.ctypes.data, sums[:, 0].copy().ctypes.data, nl, world, 1.5 * n / world, owner.ctypes.data) == 0
+    work = sums[:, 0].copy()                               # held: a pointer into a temporary would dangle during the call
+    assert L.ngravs_host_split(lcount.ctypes.data, work.ctypes.data, nl, world, 1.5 * n / world, owner.ctypes.data) == 0
     # ---- sums of every top node
     node_sums = np.zeros((nn, cw))
     for i in range(nn - 1, -1, -1):
