@@ -24,7 +24,8 @@ _LIB = None
 
 # every symbol include/ngravs_hip.h declares (tests/test_abi.py checks the .so exports all of them)
 EXPORTS = [
-    "ngravs_abi_version", "ngravs_build_info", "ngravs_config_default", "ngravs_create", "ngravs_destroy",
+    "ngravs_abi_version", "ngravs_build_info", "ngravs_config_default", "ngravs_create", "ngravs_create_with_laws", "ngravs_destroy",
+    "ngravs_last_walk_kernel", "ngravs_shortrange_table_with_laws", "ngravs_user_table_eval",
     "ngravs_set_fatal_handler", "ngravs_set_opening", "ngravs_set_walk_mode", "ngravs_set_softening", "ngravs_dd_record_bytes", "ngravs_get_config", "ngravs_set_tuning",
     "ngravs_memcpy", "ngravs_device_alloc", "ngravs_device_free",
     "ngravs_set_particles",
@@ -115,6 +116,11 @@ def lib():
         L.ngravs_dd_apply_migration.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
         L.ngravs_dd_set_halo.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
         L.ngravs_dd_set_ids.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.ngravs_create_with_laws.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.ngravs_last_walk_kernel.argtypes = [C.c_void_p]
+        L.ngravs_shortrange_table_with_laws.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.ngravs_user_table_eval.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_int64, C.c_void_p,
+                                             C.c_void_p]
         L.ngravs_dd_get_ids.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         _LIB = L
     return _LIB
@@ -147,6 +153,34 @@ def shortrange_table(cfg):
     return force, pot
 
 
+def shortrange_table_with_laws(cfg, user_fns):
+    """shortrange_table() where law_normed may hold user ids: user_fns = [(abi.USER_NORMED, f), ...]; no GPU needed"""
+    arr, nfns, keep = abi.user_registry(user_fns)
+    ng = cfg.n_gravs
+    force = np.zeros((ng, ng, abi.NTAB))
+    pot = np.zeros((ng, ng, abi.NTAB))
+    rc = lib().ngravs_shortrange_table_with_laws(C.byref(cfg), arr, nfns, force.ctypes.data, pot.ctypes.data)
+    del keep
+    if rc != 0:
+        raise NgravsError("ngravs_shortrange_table_with_laws: %d" % rc)
+    return force, pot
+
+
+def user_table_eval(kind, fn, r, r_lo=0.0, r_hi=0.0, h=0.0):
+    """what the kernels evaluate for a user law, built and evaluated on the host (no GPU): kind USER_ACCEL -> accel(1,1,r^2,r,1)
+    from the table over [r_lo, r_hi]; USER_SPLINE -> spline(1,1,h,r,1) from the table of softening h.  Returns (values, the
+    largest relative deviation the fit saw at its check points)."""
+    arr, _, keep = abi.user_registry([(kind, fn)])
+    r = np.ascontiguousarray(r, dtype=np.float64)
+    out = np.zeros_like(r)
+    err = C.c_double(0)
+    rc = lib().ngravs_user_table_eval(arr, r_lo, r_hi, h, r.ctypes.data, len(r), out.ctypes.data, C.byref(err))
+    del keep
+    if rc != 0:
+        raise NgravsError("ngravs_user_table_eval: %d" % rc)
+    return out, err.value
+
+
 def _ptr(a):
     return a.ctypes.data if a is not None else None
 
@@ -154,14 +188,24 @@ def _ptr(a):
 class Engine:
     """One task's gravity state: the replacement for the reference's globals on this path."""
 
-    def __init__(self, cfg):
+    def __init__(self, cfg, user_fns=None):
+        """user_fns: [(abi.USER_ACCEL | USER_SPLINE | USER_GREENS | USER_NORMED, f), ...], f(target, source, r2_or_h_or_k2,
+        r_or_k, N) -> float; entry k is wired as abi.LAW_USER0 + k / abi.SPLINE_USER0 + k.  The callbacks are kept alive with
+        the engine (the library calls them when it (re)builds its tables)."""
         self.cfg = cfg
         self._h = C.c_void_p()
-        rc = lib().ngravs_create(C.byref(cfg), C.byref(self._h))
+        self._user_arr, nfns, self._user_keep = abi.user_registry(user_fns)
+        rc = lib().ngravs_create_with_laws(C.byref(cfg), self._user_arr, nfns, C.byref(self._h))
         if rc != 0:
-            raise NgravsError("ngravs_create failed with status %d (no HIP device or bad wiring)" % rc)
+            msg = lib().ngravs_last_error(None)
+            self.status = rc
+            raise NgravsError("ngravs_create failed with status %d (no HIP device or bad wiring): %s" % (rc, msg.decode() if msg else ""))
         self._keep = []
         self.n = 0
+
+    def last_walk_kernel(self):
+        """abi.KERNEL_*: the kernel the last gravity_tree() walked with"""
+        return int(lib().ngravs_last_walk_kernel(self._h))
 
     def close(self):
         if self._h:

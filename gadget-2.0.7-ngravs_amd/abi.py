@@ -16,6 +16,14 @@ BITS_PER_DIMENSION = 18
 LAW_NONE, LAW_NEWTON, LAW_NEG_NEWTON, LAW_YUKAWA, LAW_COLOYUK, LAW_BAMBAM, LAW_SOURCEBAM, LAW_TARGETBAM = range(8)
 SPLINE_NONE, SPLINE_PLUMMER, SPLINE_NEG_PLUMMER, SPLINE_BAMBAM, SPLINE_SOURCEBAM, SPLINE_TARGETBAM = range(6)
 WALK_STRICT, WALK_GROUP = 0, 1
+# user-defined laws (ngravs_create_with_laws): registry entry k is LAW_USER0 + k / SPLINE_USER0 + k
+LAW_USER0 = 64
+SPLINE_USER0 = 64
+MAX_USER_FNS = 8
+USER_ACCEL, USER_SPLINE, USER_GREENS, USER_NORMED = range(4)
+KERNEL_NONE, KERNEL_STRICT, KERNEL_STRICT_USER, KERNEL_GROUP, KERNEL_GROUP_USER = range(5)
+# the reference's `gravity` type (allvars.h:134): double f(double target, double source, double r2_or_h_or_k2, double r_or_k, long N)
+GravityFn = C.CFUNCTYPE(C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_long)
 
 LAW_NAMES = {"none": LAW_NONE, "newtonian": LAW_NEWTON, "neg_newtonian": LAW_NEG_NEWTON,
              "yukawa": LAW_YUKAWA, "coloyuk": LAW_COLOYUK}
@@ -50,6 +58,25 @@ class Particles(C.Structure):
         ("grav_cost", C.c_void_p), ("grav_cost_stride", C.c_int64),
         ("on_device", C.c_int32), ("reserved", C.c_int32),
     ]
+
+
+class UserFn(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("fn", GravityFn)]
+
+
+def user_registry(user_fns):
+    """[(kind, callable), ...] -> (ctypes array of UserFn, the callback wrappers, which must outlive every use of the array)"""
+    user_fns = list(user_fns or [])
+    if len(user_fns) > MAX_USER_FNS:
+        raise ValueError("at most %d user-defined laws" % MAX_USER_FNS)
+    arr = (UserFn * max(len(user_fns), 1))()
+    keep = []
+    for k, (kind, fn) in enumerate(user_fns):
+        w = fn if isinstance(fn, GravityFn) else GravityFn(fn)
+        keep.append(w)
+        arr[k].kind = int(kind)
+        arr[k].fn = w
+    return arr, len(user_fns), keep
 
 
 class Stats(C.Structure):
@@ -102,10 +129,19 @@ def make_config(n_gravs=1, periodic=0, pmgrid=0, box_size=0.0, G=1.0, theta=0.5,
             elif wiring == "bam":
                 law, spl = {(0, 0): (LAW_NEWTON, SPLINE_PLUMMER), (0, 1): (LAW_SOURCEBAM, SPLINE_SOURCEBAM),
                             (1, 0): (LAW_TARGETBAM, SPLINE_TARGETBAM), (1, 1): (LAW_BAMBAM, SPLINE_BAMBAM)}[(i, j)]
+            elif isinstance(wiring, dict):
+                # explicit ids (built-in or LAW_USER0 + k / SPLINE_USER0 + k):
+                # {"accel": [[..]], "spline": [[..]], "greens": [[..]] (default none), "normed": [[..]] (default greens)}
+                law, spl = wiring["accel"][i][j], wiring["spline"][i][j]
             else:
                 raise ValueError("unknown wiring %r" % wiring)
             cfg.law_accel[i][j] = law
             cfg.law_spline[i][j] = spl
+            if isinstance(wiring, dict):
+                none = [[LAW_NONE] * n_gravs] * n_gravs
+                cfg.law_greens[i][j] = wiring.get("greens", none)[i][j]
+                cfg.law_normed[i][j] = wiring.get("normed", wiring.get("greens", none))[i][j]
+                continue
             cfg.law_greens[i][j] = law if wiring != "bam" else LAW_NONE
             cfg.law_normed[i][j] = law if wiring != "bam" else LAW_NONE
     cfg.yukawa_imass = float(yukawa_imass)

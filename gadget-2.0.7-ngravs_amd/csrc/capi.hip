@@ -8,10 +8,14 @@
 #include <chrono>
 #include <cmath>
 
+static thread_local std::string g_create_error;   // ngravs_last_error(NULL): why this thread's last ngravs_create[_with_laws] failed
+
 void ngravs_report(ngravs_ctx *ctx, int code, const std::string &msg)
 {
   if(ctx)
     ctx->last_error = msg;
+  else
+    g_create_error = msg;
   if(ctx && ctx->on_fatal)
     ctx->on_fatal(code, msg.c_str());
   else
@@ -237,19 +241,23 @@ static int check_config(const ngravs_config_t *cfg, std::string &why)
   for(int i = 0; i < cfg->n_gravs; i++)
     for(int j = 0; j < cfg->n_gravs; j++)
       {
-        if(cfg->law_accel[i][j] < 0 || cfg->law_accel[i][j] >= NGRAVS_LAW_COUNT || cfg->law_spline[i][j] < 0 ||
-           cfg->law_spline[i][j] >= NGRAVS_SPLINE_COUNT || cfg->law_greens[i][j] < 0 ||
-           cfg->law_greens[i][j] >= NGRAVS_LAW_COUNT || cfg->law_normed[i][j] < 0 || cfg->law_normed[i][j] >= NGRAVS_LAW_COUNT)
+        // (user ids, NGRAVS_LAW_USER0 + k, are checked by user_check_config against the registry)
+        auto bad = [](int id, int count) { return id < 0 || (id >= count && id < NGRAVS_LAW_USER0); };
+        if(bad(cfg->law_accel[i][j], NGRAVS_LAW_COUNT) || bad(cfg->law_spline[i][j], NGRAVS_SPLINE_COUNT) ||
+           bad(cfg->law_greens[i][j], NGRAVS_LAW_COUNT) || bad(cfg->law_normed[i][j], NGRAVS_LAW_COUNT))
           {
             why = "force-law table slot not wired (ngravs_core.c:321-360)";
             return NGRAVS_ERR_WIRING;
           }
         // Newton's third law probe F[i][j](1,1,0.5,3,1) == F[j][i](...) (ngravs_core.c:371-403): equal ids, or the two views of
         // the BAM-baryon pair (sourcebambaryon / sourcebaryonbam agree for unit masses and N = 1)
-        auto same = [](int a, int b, int p, int q) { return a == b || (a == p && b == q) || (a == q && b == p); };
+        // (a pair with a user id is probed through its callbacks by user_check_config)
+        auto same = [](int a, int b, int p, int q) {
+          return a == b || (a == p && b == q) || (a == q && b == p) || a >= NGRAVS_LAW_USER0 || b >= NGRAVS_LAW_USER0;
+        };
         if(!same(cfg->law_accel[i][j], cfg->law_accel[j][i], NGRAVS_LAW_SOURCEBAM, NGRAVS_LAW_TARGETBAM) ||
            !same(cfg->law_spline[i][j], cfg->law_spline[j][i], NGRAVS_SPLINE_SOURCEBAM, NGRAVS_SPLINE_TARGETBAM) ||
-           cfg->law_normed[i][j] != cfg->law_normed[j][i] || cfg->law_greens[i][j] != cfg->law_greens[j][i])
+           !same(cfg->law_normed[i][j], cfg->law_normed[j][i], -1, -1) || !same(cfg->law_greens[i][j], cfg->law_greens[j][i], -1, -1))
           {
             why = "force-law table violates Newton's third law (ngravs_core.c:371-403)";
             return NGRAVS_ERR_WIRING;
@@ -263,13 +271,17 @@ static int check_config(const ngravs_config_t *cfg, std::string &why)
   return NGRAVS_OK;
 }
 
-extern "C" int ngravs_create(const ngravs_config_t *cfg, ngravs_ctx **out)
+extern "C" int ngravs_create(const ngravs_config_t *cfg, ngravs_ctx **out) { return ngravs_create_with_laws(cfg, nullptr, 0, out); }
+
+extern "C" int ngravs_create_with_laws(const ngravs_config_t *cfg, const ngravs_user_fn_t *fns, int nfns, ngravs_ctx **out)
 {
   if(!cfg || !out)
     return NGRAVS_ERR_ARG;
   *out = nullptr;
   std::string why;
   int rc = check_config(cfg, why);
+  if(rc == NGRAVS_OK)
+    rc = user_check_config(cfg, fns, nfns, why);
   if(rc != NGRAVS_OK)
     {
       ngravs_report(nullptr, rc, why);
@@ -285,6 +297,7 @@ extern "C" int ngravs_create(const ngravs_config_t *cfg, ngravs_ctx **out)
     return NGRAVS_ERR_ARG;
   ngravs_ctx *c = new ngravs_ctx;
   c->cfg = *cfg;
+  c->user_fns.assign(fns, fns + nfns);
   memset(&c->stats, 0, sizeof(c->stats));
   if(hipSetDevice(cfg->device) != hipSuccess || hipStreamCreate(&c->stream) != hipSuccess ||
      hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess ||
@@ -350,6 +363,8 @@ extern "C" void ngravs_destroy(ngravs_ctx *c)
   c->n_geo.release();
   c->n_mom.release();
   c->n_npart.release();
+  c->user_tab.release();
+  c->user_green.release();
   c->scan_out.release();
   c->tb_count.release();
   c->scan_tmp.release();
@@ -912,7 +927,7 @@ static int ensure_table(ngravs_ctx *c)
     return NGRAVS_OK;
   const int ng = c->cfg.n_gravs;
   std::vector<double> h((size_t)(ng * ng + 1) * NTAB);
-  host_shortrange_table(&c->cfg, h.data(), nullptr);
+  host_shortrange_table(&c->cfg, h.data(), nullptr, c->user_fns.data(), (int)c->user_fns.size());
   {
     // bin-wise Yukawa factor E[tab] = exp(-ym tab/asmthfac) behind the tables (kernels_walk.hip, WalkParams::exp_tab)
     WalkParams wp;
@@ -1274,7 +1289,8 @@ extern "C" int ngravs_get_shard(ngravs_ctx *c, int64_t *first, int64_t *count)
   return NGRAVS_OK;
 }
 
-extern "C" const char *ngravs_last_error(ngravs_ctx *c) { return c ? c->last_error.c_str() : ""; }
+extern "C" const char *ngravs_last_error(ngravs_ctx *c) { return c ? c->last_error.c_str() : g_create_error.c_str(); }
+extern "C" int ngravs_last_walk_kernel(ngravs_ctx *c) { return c ? c->last_walk_kernel : NGRAVS_ERR_ARG; }
 
 // ---- stand-alone pieces -------------------------------------------------------------------------------
 extern "C" int64_t ngravs_peano_hilbert_key(int x, int y, int z, int bits) { return ngravs_ph_key(x, y, z, bits); }
@@ -1307,6 +1323,23 @@ extern "C" int ngravs_shortrange_table(const ngravs_config_t *cfg, double *force
   if(!cfg || !force_out || cfg->n_gravs < 1 || cfg->n_gravs > NGRAVS_MAX_GRAVS)
     return NGRAVS_ERR_ARG;
   host_shortrange_table(cfg, force_out, pot_out);
+  return NGRAVS_OK;
+}
+
+extern "C" int ngravs_shortrange_table_with_laws(const ngravs_config_t *cfg, const ngravs_user_fn_t *fns, int nfns, double *force_out,
+                                                 double *pot_out)
+{
+  if(!cfg || !force_out || cfg->n_gravs < 1 || cfg->n_gravs > NGRAVS_MAX_GRAVS || nfns < 0 || nfns > NGRAVS_MAX_USER_FNS ||
+     (nfns > 0 && !fns))
+    return NGRAVS_ERR_ARG;
+  for(int i = 0; i < cfg->n_gravs; i++)
+    for(int j = 0; j < cfg->n_gravs; j++)
+      {
+        const int law = cfg->law_normed[i][j], k = law - NGRAVS_LAW_USER0;
+        if(law >= NGRAVS_LAW_USER0 && (k >= nfns || fns[k].kind != NGRAVS_USER_NORMED || !fns[k].fn))
+          return NGRAVS_ERR_WIRING;
+      }
+  host_shortrange_table(cfg, force_out, pot_out, fns, nfns);
   return NGRAVS_OK;
 }
 
@@ -1350,19 +1383,22 @@ extern "C" int ngravs_direct_sum_targets(ngravs_ctx *c, const double *pos, const
   if(dt.ensure(nt) || dty.ensure(nt) || dacc.ensure(3 * nt))
     return NGRAVS_ERR_NOMEM;
   std::vector<double4> h((size_t)nt);
+  double r_need = 0;   // user-defined laws: farthest a target can be from a source (target to domain centre + half diagonal)
   for(int64_t k = 0; k < nt; k++)
     {
       h[k].x = pos[3 * k];
       h[k].y = pos[3 * k + 1];
       h[k].z = pos[3 * k + 2];
       h[k].w = mass ? mass[k] : 1.0;
+      const double dx = h[k].x - c->dom[3], dy = h[k].y - c->dom[4], dz = h[k].z - c->dom[5];
+      r_need = fmax(r_need, 1.25 * (sqrt(dx * dx + dy * dy + dz * dz) + 0.5 * sqrt(3.0) * c->dom[6]));
     }
   int rc = NGRAVS_OK;
   if(hipMemcpyAsync(dt.p, h.data(), sizeof(double4) * nt, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
      hipMemcpyAsync(dty.p, type, sizeof(int) * nt, hipMemcpyHostToDevice, c->stream) != hipSuccess)
     rc = NGRAVS_ERR_NO_DEVICE;
   if(!rc)
-    rc = direct_run_targets(c, dt.p, dty.p, nt, dacc.p);
+    rc = direct_run_targets(c, dt.p, dty.p, nt, dacc.p, r_need);
   if(!rc && hipMemcpyAsync(acc, dacc.p, sizeof(double) * 3 * nt, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
     rc = NGRAVS_ERR_NO_DEVICE;
   (void)hipStreamSynchronize(c->stream);

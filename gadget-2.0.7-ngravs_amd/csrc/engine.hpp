@@ -70,6 +70,57 @@ template <typename T> struct DevBuf
   }
 };
 
+// User-defined laws (ngravs_create_with_laws; user_laws.cpp builds the tables, DESIGN.md "User-defined force laws").
+// Every table is a run of sub-intervals with a degree-7 polynomial in t in [-1, 1] each (UL_NC coefficients, Horner order
+// c[7] .. c[0]).  r-space force of registry entry k: g(r) = r^2 accel(1, 1, r^2, r, 1) over the octaves [2^(e-1), 2^e),
+// e = e_lo .. e_lo + n_oct - 1, S sub-intervals of the mantissa each: coef + (k * n_oct + o) * S * UL_NC.  Spline of entry k
+// for the i-th distinct softening h[i]: spline(1, 1, h, u h, 1) over u in [0, 1), Ss sub-intervals: spl + ((k * nh + i) * Ss) * UL_NC.
+#define UL_NC 8
+struct UserTabs
+{
+  const double *coef, *spl;
+  int e_lo, n_oct, S;
+  int nh, Ss;
+  double h[NGRAVS_NTYPES];
+};
+__host__ __device__ inline double ul_poly(const double *c, double t)
+{
+  double v = c[7];
+  for(int j = 6; j >= 0; j--)
+    v = v * t + c[j];
+  return v;
+}
+// g(r) of entry k: octave and mantissa by frexp (v_frexp_exp_i32_f64 / v_frexp_mant_f64), clamped to the table's ends
+__host__ __device__ inline double ul_g(const UserTabs &u, int k, double r)
+{
+  int e;
+  (void)frexp(r, &e);
+  int o = e - u.e_lo;
+  const double m = ldexp(r, -(u.e_lo + (o < 0 ? 0 : (o >= u.n_oct ? u.n_oct - 1 : o))));   // [0.5, 1) inside the table
+  double s = (m - 0.5) * (2 * u.S);
+  // outside the table (or r = 0 / NaN) the value at its nearer end: no extrapolated polynomial
+  s = o < 0 ? 0.0 : (o >= u.n_oct ? (double)u.S : s);
+  o = o < 0 ? 0 : (o >= u.n_oct ? u.n_oct - 1 : o);
+  s = s >= 0 ? (s <= u.S ? s : (double)u.S) : 0.0;
+  int j = (int)s;
+  j = j >= u.S ? u.S - 1 : j;
+  return ul_poly(u.coef + ((size_t)(k * u.n_oct + o) * u.S + j) * UL_NC, 2 * (s - j) - 1);
+}
+__host__ __device__ inline double ul_spline(const UserTabs &u, int k, double h, double r)
+{
+  if(u.nh == 0)   // no positive softening: r < h never holds (a NaN pair of h = 0 gets no table read)
+    return 0.0;
+  int i = 0;
+  for(int q = 1; q < u.nh; q++)
+    if(fabs(u.h[q] - h) < fabs(u.h[i] - h))
+      i = q;
+  double s = r / h * u.Ss;
+  s = s >= 0 ? (s <= u.Ss ? s : (double)u.Ss) : 0.0;   // (NaN -> 0)
+  int j = (int)s;
+  j = j >= u.Ss ? u.Ss - 1 : j;
+  return ul_poly(u.spl + ((size_t)(k * u.nh + i) * u.Ss + j) * UL_NC, 2 * (s - j) - 1);
+}
+
 // constants every kernel needs, passed by value (fits kernarg / SGPRs)
 struct WalkParams
 {
@@ -101,7 +152,9 @@ struct WalkParams
   // the BAM / NGRAVS_ACCUMULATOR family in the group walk (tree-only wirings): law ids [target][source] and the flag that one is wired
   int bam;
   int law_accel[NG_MAX][NG_MAX], law_spline[NG_MAX][NG_MAX];
-
+  // user-defined laws (tree-only wirings with a user id: then bam = 1 too, which selects the variant that evaluates law ids)
+  int user;
+  UserTabs ut;
 };
 
 struct TreeView
@@ -281,6 +334,15 @@ struct ngravs_ctx
   int walk_lcap = 0;                  // split walk: item-list capacity per group and species (grown on overflow)
   int walk_scap = 0;                  // split walk: LIFO capacity per group (grown on overflow)
   std::string last_error;
+  // user-defined laws (ngravs_create_with_laws)
+  std::vector<ngravs_user_fn_t> user_fns;
+  DevBuf<double> user_tab;    // accel tables, then spline tables (UserTabs)
+  UserTabs user_ut = {};
+  bool user_ready = false;
+  double user_soft[NGRAVS_NTYPES] = {0, 0, 0, 0, 0, 0};   // the softenings the tables were built for
+  int last_walk_kernel = 0;   // NGRAVS_KERNEL_*
+  DevBuf<double> user_green;  // PM: user Green's functions G(k2) at the integer k2 (GreenParams::ug); empty without a user greens id
+  long long user_green_nk2 = 0;
 };
 
 // ---- kernels_domain.hip
@@ -316,16 +378,31 @@ static inline bool cfg_has_bam(const ngravs_config_t &cfg)
 {
   for(int i = 0; i < cfg.n_gravs; i++)
     for(int j = 0; j < cfg.n_gravs; j++)
-      if(cfg.law_accel[i][j] >= NGRAVS_LAW_BAMBAM || cfg.law_spline[i][j] >= NGRAVS_SPLINE_BAMBAM)
+      if((cfg.law_accel[i][j] >= NGRAVS_LAW_BAMBAM && cfg.law_accel[i][j] < NGRAVS_LAW_USER0) ||
+         (cfg.law_spline[i][j] >= NGRAVS_SPLINE_BAMBAM && cfg.law_spline[i][j] < NGRAVS_SPLINE_USER0))
         return true;
   return false;
 }
+static inline bool cfg_has_user(const ngravs_config_t &cfg)
+{
+  for(int i = 0; i < cfg.n_gravs; i++)
+    for(int j = 0; j < cfg.n_gravs; j++)
+      if(cfg.law_accel[i][j] >= NGRAVS_LAW_USER0 || cfg.law_spline[i][j] >= NGRAVS_SPLINE_USER0)
+        return true;
+  return false;
+}
+// ---- user_laws.cpp
+int user_check_config(const ngravs_config_t *cfg, const ngravs_user_fn_t *fns, int nfns, std::string &why);
+void ngravs_report(ngravs_ctx *ctx, int code, const std::string &msg);
+int user_tables_ensure(ngravs_ctx *c, double r_need);
+int user_green_ensure(ngravs_ctx *c);   // PM: the G(k2) tables of the user greens ids   // (re)build the tables if r_need or the softenings are not covered
+double user_normed(const ngravs_user_fn_t *fns, int nfns, int law, double k2);
 // ---- kernels_walk.hip
 void make_walk_params(const ngravs_ctx *c, WalkParams *wp);
 int walk_run(ngravs_ctx *c);
 int walk_finish(ngravs_ctx *c);
 int direct_run(ngravs_ctx *c, const int *d_idx, int64_t nt, double *d_acc);
-int direct_run_targets(ngravs_ctx *c, const double4 *d_tpm, const int *d_ttype, int64_t nt, double *d_acc);
+int direct_run_targets(ngravs_ctx *c, const double4 *d_tpm, const int *d_ttype, int64_t nt, double *d_acc, double r_need = 0);
 // ---- kernels_eval.hip
 int eval_ring_slots(const WalkParams &wp, bool yuk, int waves);
 int launch_eval_ring(ngravs_ctx *c, const TreeView &tv, const WalkParams &wp, bool yuk, int nblk, int waves, int K, const int *region,
@@ -341,6 +418,6 @@ int pmslab_pack(ngravs_ctx *c, int stage, const int *all_bbox, int64_t *send_cou
 int pmslab_unpack(ngravs_ctx *c, int stage);
 void pmslab_release(ngravs_ctx *c);
 // ---- shortrange_table.cpp
-void host_shortrange_table(const ngravs_config_t *cfg, double *force, double *pot);
+void host_shortrange_table(const ngravs_config_t *cfg, double *force, double *pot, const ngravs_user_fn_t *fns = nullptr, int nfns = 0);
 double cfg_asmth(const ngravs_config_t *c);
 double cfg_rcut(const ngravs_config_t *c);

@@ -609,6 +609,9 @@ int pm_finish(ngravs_ctx *c)
   for(int a = 0; a < ng; a++)
     FFT_TRY(c, hipfftExecD2Z(*(hipfftHandle *)c->fft_fwd, c->pm_rho.p + real_elems * a,
                              (hipfftDoubleComplex *)(c->pm_rho.p + real_elems * a)));
+  int rcg = user_green_ensure(c);
+  if(rcg)
+    return rcg;
   GreenParams gp;
   make_green_params(c, &gp);
   long long modes = (long long)N * N * (N / 2 + 1);

@@ -865,6 +865,9 @@ int pmslab_unpack(ngravs_ctx *c, int stage)
           for(int a = 0; a < ng; a++)
             FFT_TRY(c, hipfftExecZ2Z(*(hipfftHandle *)s.plan1, (hipfftDoubleComplex *)(rho_t + tcells * a),
                                      (hipfftDoubleComplex *)(rho_t + tcells * a), HIPFFT_FORWARD));
+          int rcg = user_green_ensure(c);
+          if(rcg)
+            return rcg;
           GreenParams gp;
           make_green_params(c, &gp);
           switch(ng)

@@ -1053,7 +1053,7 @@ int tree_moments(ngravs_ctx *c, bool refit, bool counts)
   const int bs = 128;
   double4 *grw = refit ? c->n_geo.p : nullptr;
   int *npp = nullptr;
-  if(cfg_has_bam(c->cfg))
+  if(cfg_has_bam(c->cfg) || cfg_has_user(c->cfg))   // (the group walk's law-id variant reads the counts)
     {
       if(c->n_npart.ensure((size_t)c->max_nodes * ng))
         return NGRAVS_ERR_NOMEM;

@@ -101,6 +101,21 @@ __device__ __forceinline__ double law_spline_ref(int id, double m, double h, dou
   return id == NGRAVS_SPLINE_NEG_PLUMMER ? -v : v;
 }
 
+// user-defined laws (ngravs_create_with_laws): ids NGRAVS_LAW_USER0 + k / NGRAVS_SPLINE_USER0 + k read the host-built tables
+// (engine.hpp UserTabs); the table holds r^2 accel(1, 1, r^2, r, 1) and the law is linear in the source mass m
+__device__ __forceinline__ double law_accel_any(int law, double m, double r2, double r, const WalkParams &wp, double target, double N)
+{
+  if(law >= NGRAVS_LAW_USER0)
+    return m * ul_g(wp.ut, law - NGRAVS_LAW_USER0, r) / r2;
+  return law_accel_ref(law, m, r2, r, wp.ym, target, N, wp.bam_eps);
+}
+__device__ __forceinline__ double law_spline_any(int id, double m, double h, double r, const WalkParams &wp, double target, double N)
+{
+  if(id >= NGRAVS_SPLINE_USER0)
+    return m * ul_spline(wp.ut, id - NGRAVS_SPLINE_USER0, h, r);
+  return law_spline_ref(id, m, h, r, target, N, wp.bam_eps);
+}
+
 struct LawIds
 {
   int accel[NG_MAX][NG_MAX], spline[NG_MAX][NG_MAX];
@@ -232,7 +247,7 @@ __device__ __forceinline__ void lat_lookup(const double *__restrict__ t3, double
 // =============================================================================================
 #pragma clang fp contract(off)
 
-template <int NG, bool PM, bool LATT>
+template <int NG, bool PM, bool LATT, bool USER = false>   // USER: tree-only wirings with a user-defined law
 __global__ __launch_bounds__(256) void k_walk_strict(TreeView tv, const double4 *__restrict__ s_pm,
                                                      const unsigned char *__restrict__ s_type,
                                                      const double *__restrict__ s_oldacc,
@@ -283,16 +298,23 @@ __global__ __launch_bounds__(256) void k_walk_strict(TreeView tv, const double4 
           return false;
         if(r >= h)
           {
-            fac = law_accel_ref(li.accel[tg][g], m, r2, r, wp.ym);
+            if constexpr(USER)
+              fac = law_accel_any(li.accel[tg][g], m, r2, r, wp, 1.0, 1.0);
+            else
+              fac = law_accel_ref(li.accel[tg][g], m, r2, r, wp.ym);
             fac -= m * wp.utor2wpi * table[((size_t)tg * NG + g) * NTAB + tab];
             fac /= r;
           }
+        else if constexpr(USER)
+          fac = law_spline_any(li.spline[tg][g], m, h, r, wp, 1.0, 1.0);
         else
           fac = law_spline_ref(li.spline[tg][g], m, h, r);
       }
     else
       {
-        if(r >= h)
+        if constexpr(USER)
+          fac = r >= h ? law_accel_any(li.accel[tg][g], m, r2, r, wp, pmass, N) / r : law_spline_any(li.spline[tg][g], m, h, r, wp, pmass, N);
+        else if(r >= h)
           fac = law_accel_ref(li.accel[tg][g], m, r2, r, wp.ym, pmass, N, wp.bam_eps) / r;
         else
           fac = law_spline_ref(li.spline[tg][g], m, h, r, pmass, N, wp.bam_eps);
@@ -622,7 +644,8 @@ __global__ __launch_bounds__(256) void k_walk_strict(TreeView tv, const double4 
 #define GW3_TBLOCK 256       // traversal kernel: 4 groups per workgroup
 #define GW3_RING 1024        // traversal kernel: LIFO positions mirrored in LDS per wave (a round pushes at most 512)
 
-template <int NG, bool PM, bool YUK, bool TAB_LDS, bool LATT, int MODE>
+// USR: TreePM wirings with a user-defined law (their own instantiation; the ring kernel never sees them)
+template <int NG, bool PM, bool YUK, bool TAB_LDS, bool LATT, int MODE, bool USR = false>
 __global__ __launch_bounds__(MODE == 1 ? GW3_TBLOCK : (MODE == 2 ? GW2_MAXWAVES : GW_MAXWAVES) * 64) void k_walk_group2(
     TreeView tv, const double4 *__restrict__ s_pm, const unsigned char *__restrict__ s_type,
     const double *__restrict__ s_oldacc, const unsigned char *__restrict__ s_active,
@@ -1045,11 +1068,31 @@ __global__ __launch_bounds__(MODE == 1 ? GW3_TBLOCK : (MODE == 2 ? GW2_MAXWAVES 
                   const double Nn = (double)__float_as_int(le2[je]);
                   double f = 0.0;
                   if(mw[k] != 0.0)   // (the NULL entry: no mass, and its slot holds no particle number)
-                    f = r[k] >= h ? law_accel_ref(lawA, mw[k], r2[k], r[k], wp.ym, pmassT, Nn, wp.bam_eps) * rinv[k]
-                                  : law_spline_ref(lawS, mw[k], h, r[k], pmassT, Nn, wp.bam_eps);
+                    f = r[k] >= h ? law_accel_any(lawA, mw[k], r2[k], r[k], wp, pmassT, Nn) * rinv[k]
+                                  : law_spline_any(lawS, mw[k], h, r[k], wp, pmassT, Nn);
                   fac[k] = f;
                 }
             }
+        if constexpr(USR && PM)
+          {
+#pragma unroll
+            for(int k = 0; k < ES; k++)
+              {
+                // forcetree.c:1953-1974 through the wired ids: (accel(r) - m utor2wpi T[tab]) / r, the spline inside the softening
+                // (slots beyond the exact cut and the NULL entry carry mass 0)
+                const int je = is_act(k) ? jj[k] : 127;
+                const double h = __builtin_fmax(hT, fsT[lty[je]]);
+                double f = 0.0;
+                if(mw[k] != 0.0)
+                  {
+                    int tab = (int)(wp.asmthfac * r[k]);
+                    tab = tab < NTAB - 1 ? tab : NTAB - 1;
+                    f = r[k] >= h ? (law_accel_any(lawA, mw[k], r2[k], r[k], wp, 1.0, 1.0) - mw[k] * wp.utor2wpi * trow[tab]) * rinv[k]
+                                  : law_spline_any(lawS, mw[k], h, r[k], wp, 1.0, 1.0);
+                  }
+                fac[k] = f;
+              }
+          }
 #pragma unroll
         for(int k = 0; k < ES; k++)
           {
@@ -1182,7 +1225,7 @@ __global__ __launch_bounds__(MODE == 1 ? GW3_TBLOCK : (MODE == 2 ? GW2_MAXWAVES 
         cNg = wp.cN[tg][g];
         cYg = wp.cY[tg][g];
         cSg = wp.cS[tg][g];
-        if constexpr(BAMCAP)
+        if constexpr(BAMCAP || USR)
           if(wp.bam)
             {
               lawA = wp.law_accel[tg][g];
@@ -2026,6 +2069,7 @@ __global__ void k_finish(long long t_first, long long t_count, const unsigned ch
 // targets: particles tidx[k] of the working set, or (tidx == nullptr) explicit records t_pm[k] / t_type[k] -- a test particle of
 // ANOTHER task in the distributed gravity_forcetest(); own_only: the imported copies (active bit 1) are not sources, each task
 // contributes its own particles and the host adds the partial sums up
+template <bool USER = false>   // USER: tree-only wirings with a user-defined law
 __global__ __launch_bounds__(256) void k_direct(const double4 *__restrict__ s_pm, const unsigned char *__restrict__ s_type,
                                                  long long n, const int *__restrict__ tidx, long long nt, WalkParams wp,
                                                  LawIds li, double G, const double *__restrict__ lat, double *__restrict__ acc,
@@ -2066,7 +2110,9 @@ __global__ __launch_bounds__(256) void k_direct(const double4 *__restrict__ s_pm
           dz = nearest(dz, wp.box, wp.boxhalf);
         }
       double r2 = dx * dx + dy * dy + dz * dz, r = sqrt(r2), u = r * (1 / h), fac;
-      if(u >= 1)
+      if constexpr(USER)
+        fac = u >= 1 ? law_accel_any(li.accel[tg][sg], q.w, r2, r, wp, p.w, 1.0) / r : law_spline_any(li.spline[tg][sg], q.w, h, r, wp, p.w, 1.0);
+      else if(u >= 1)
         fac = law_accel_ref(li.accel[tg][sg], q.w, r2, r, wp.ym, p.w, 1.0, wp.bam_eps) / r;
       else
         fac = law_spline_ref(li.spline[tg][sg], q.w, h, r, p.w, 1.0, wp.bam_eps);
@@ -2179,7 +2225,9 @@ void make_walk_params(const ngravs_ctx *c, WalkParams *wp)
     wp->ec[2] = ub * ub * ub / 6.0;
     wp->ec[3] = ub * ub * ub * ub / 24.0;
   }
-  wp->bam = cfg_has_bam(cfg) ? 1 : 0;
+  wp->user = cfg_has_user(cfg) ? 1 : 0;
+  wp->ut = c->user_ut;
+  wp->bam = (cfg_has_bam(cfg) || wp->user) ? 1 : 0;
   for(int i = 0; i < NG_MAX; i++)
     for(int j = 0; j < NG_MAX; j++)
       {
@@ -2233,7 +2281,7 @@ static TreeView tree_view(ngravs_ctx *c)
   tv.flags = c->n_flags.p;
   tv.geo = c->n_geo.p;
   tv.mom = c->n_mom.p;
-  tv.npart = cfg_has_bam(c->cfg) ? c->n_npart.p : nullptr;
+  tv.npart = (cfg_has_bam(c->cfg) || cfg_has_user(c->cfg)) ? c->n_npart.p : nullptr;
   tv.nnodes = (int)c->nnodes;
   tv.ltab = c->lvl_table.p;
   tv.ltab_level = c->lvl_table_level;
@@ -2324,11 +2372,12 @@ static int ensure_lattice(ngravs_ctx *c)
   return NGRAVS_OK;
 }
 
-template <int NG, bool PM, bool LATT> static void launch_strict(ngravs_ctx *c, const WalkParams &wp, const LawIds &li)
+template <int NG, bool PM, bool LATT, bool USER = false> static void launch_strict(ngravs_ctx *c, const WalkParams &wp, const LawIds &li)
 {
+  c->last_walk_kernel = USER ? NGRAVS_KERNEL_STRICT_USER : NGRAVS_KERNEL_STRICT;
   long long ngroups = (c->shard_count + WAVE - 1) / WAVE;
   unsigned nb = (unsigned)((ngroups + 3) / 4);
-  hipLaunchKernelGGL((k_walk_strict<NG, PM, LATT>), dim3(nb), dim3(256), 0, c->stream, tree_view(c), c->s_pm.p, c->s_type.p,
+  hipLaunchKernelGGL((k_walk_strict<NG, PM, LATT, USER>), dim3(nb), dim3(256), 0, c->stream, tree_view(c), c->s_pm.p, c->s_type.p,
                      c->s_oldacc.p, c->s_active.p, LATT ? c->lat.p : c->table.p, wp, li, (long long)c->shard_first,
                      (long long)c->shard_count, c->r_acc.p, c->r_nint.p, c->walk_counters.p + 1);
 }
@@ -2374,7 +2423,7 @@ static int walk_select_targets(ngravs_ctx *c)
   return NGRAVS_OK;
 }
 
-template <int NG, bool PM, bool YUK, bool TAB_LDS, bool LATT>
+template <int NG, bool PM, bool YUK, bool TAB_LDS, bool LATT, bool USR = false>
 static int launch_group2_t(ngravs_ctx *c, const WalkParams &wp, int *glist = nullptr, int nlist = 0)
 {
   // lanes per target: the walk's own S, or for the leftover pass (glist) enough to give the few scattered groups many waves
@@ -2411,7 +2460,7 @@ static int launch_group2_t(ngravs_ctx *c, const WalkParams &wp, int *glist = nul
     HIP_TRY(c, hipMemsetAsync(c->walk_counters.p + 8, 0, sizeof(int) * 8, c->stream));
   else
     HIP_TRY(c, hipMemsetAsync(c->walk_counters.p, 0, sizeof(int) * 32, c->stream));
-  auto kern = k_walk_group2<NG, PM, YUK, TAB_LDS, LATT, 0>;
+  auto kern = k_walk_group2<NG, PM, YUK, TAB_LDS, LATT, 0, USR>;
   HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(waves * 64), lds, c->stream, tree_view(c), c->s_pm.p,
                      c->s_type.p, c->s_oldacc.p, c->s_active.p, LATT ? c->lat.p : c->table.p, wp, (long long)c->shard_first,
@@ -2422,7 +2471,7 @@ static int launch_group2_t(ngravs_ctx *c, const WalkParams &wp, int *glist = nul
 
 // split walk: per batch of groups a high-occupancy traversal kernel (MODE 1) writes the item lists, then the persistent
 // evaluation kernel (MODE 2) consumes them.  Same results as the fused kernel (same lists, same order).
-template <int NG, bool PM, bool YUK, bool TAB_LDS, bool LATT> static int launch_group3_t(ngravs_ctx *c, const WalkParams &wp)
+template <int NG, bool PM, bool YUK, bool TAB_LDS, bool LATT, bool USR = false> static int launch_group3_t(ngravs_ctx *c, const WalkParams &wp)
 {
   int ncu = 256;
   hipDeviceProp_t prop;
@@ -2516,12 +2565,12 @@ template <int NG, bool PM, bool YUK, bool TAB_LDS, bool LATT> static int launch_
     return NGRAVS_ERR_NOMEM;
   int *region = c->walk_stack.p, *gcount = c->walk_stack.p + (size_t)batch * region_ints;
   HIP_TRY(c, hipMemsetAsync(c->walk_counters.p, 0, sizeof(int) * 32, c->stream));
-  auto kt = k_walk_group2<NG, PM, YUK, TAB_LDS, LATT, 1>;
-  auto ke = k_walk_group2<NG, PM, YUK, TAB_LDS, LATT, 2>;
+  auto kt = k_walk_group2<NG, PM, YUK, TAB_LDS, LATT, 1, USR>;
+  auto ke = k_walk_group2<NG, PM, YUK, TAB_LDS, LATT, 2, USR>;
   HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(ke), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   // TreePM lists with the tables in LDS go through the ring-pool evaluation kernel when at least 4 slots per wave fit
   int ringK = 0, ring_waves = waves;
-  if constexpr(PM && TAB_LDS && !LATT)
+  if constexpr(PM && TAB_LDS && !LATT && !USR)
     if(c->tune.walk_ring)
       {
         ring_waves = GW2_MAXWAVES;
@@ -2586,6 +2635,18 @@ static int launch_group(ngravs_ctx *c, const WalkParams &wp, bool allow_split, b
   // tables in LDS while they leave room for the pools of 16 waves (three 16 KB tables incl. the exp table; the C5 wiring --
   // Newton on the diagonal, one law off it -- has two distinct ones); otherwise they are read through L1/L2
   constexpr bool TL = (NG <= 2);
+  c->last_walk_kernel = NGRAVS_KERNEL_GROUP;
+  if(pm && wp.user)
+    {
+      // TreePM wirings with a user-defined law: their own evaluation variant (USR), never the ring kernel
+      c->last_walk_kernel = NGRAVS_KERNEL_GROUP_USER;
+      if(allow_split && !c->tune.walk_fused && !glist)
+        {
+          *used_split = true;
+          return launch_group3_t<NG, true, false, TL, false, true>(c, wp);
+        }
+      return launch_group2_t<NG, true, false, TL, false, true>(c, wp, glist, nlist);
+    }
   if constexpr(NG == 3)
     if(pm && wp.ntab_lds + wp.exp_tab <= 3)
       {
@@ -2605,8 +2666,11 @@ static int launch_group(ngravs_ctx *c, const WalkParams &wp, bool allow_split, b
         return yuk ? launch_group3_t<NG, true, true, TL, false>(c, wp) : launch_group3_t<NG, true, false, TL, false>(c, wp);
       if(c->cfg.periodic)
         return yuk ? launch_group3_t<NG, false, true, false, true>(c, wp) : launch_group3_t<NG, false, false, false, true>(c, wp);
-      if(!yuk && wp.bam)
-        return launch_group3_t<NG, false, false, true, false>(c, wp);   // the variant with the BAM laws
+      if((!yuk || wp.user) && wp.bam)
+        {
+          c->last_walk_kernel = wp.user ? NGRAVS_KERNEL_GROUP_USER : NGRAVS_KERNEL_GROUP;
+          return launch_group3_t<NG, false, false, true, false>(c, wp);   // the variant with the BAM and the user-defined laws
+        }
       return yuk ? launch_group3_t<NG, false, true, false, false>(c, wp) : launch_group3_t<NG, false, false, false, false>(c, wp);
     }
   if(pm)
@@ -2615,11 +2679,19 @@ static int launch_group(ngravs_ctx *c, const WalkParams &wp, bool allow_split, b
   if(c->cfg.periodic)
     return yuk ? launch_group2_t<NG, false, true, false, true>(c, wp, glist, nlist)
                : launch_group2_t<NG, false, false, false, true>(c, wp, glist, nlist);
-  if(!yuk && wp.bam)
-    return launch_group2_t<NG, false, false, true, false>(c, wp, glist, nlist);
+  if((!yuk || wp.user) && wp.bam)
+    {
+      c->last_walk_kernel = wp.user ? NGRAVS_KERNEL_GROUP_USER : NGRAVS_KERNEL_GROUP;
+      return launch_group2_t<NG, false, false, true, false>(c, wp, glist, nlist);
+    }
   return yuk ? launch_group2_t<NG, false, true, false, false>(c, wp, glist, nlist)
              : launch_group2_t<NG, false, false, false, false>(c, wp, glist, nlist);
 }
+
+// the largest distance a tree-only walk or direct sum can evaluate a law at: the diagonal of the domain cube (drifted
+// particles of a refit tree may leave it a little; beyond the table's end the last octave's polynomial is used)
+// TreePM: the end of the short-range table, r < NTAB / asmthfac = 6 Asmth (forcetree.c:1962-1967)
+static double user_reach(const ngravs_ctx *c) { return c->cfg.pmgrid ? 1.25 * 6.0 * c->asmth : 1.25 * sqrt(3.0) * c->dom[6]; }
 
 int walk_run(ngravs_ctx *c)
 {
@@ -2632,6 +2704,12 @@ int walk_run(ngravs_ctx *c)
       int rcl = ensure_lattice(c);   // begrun.c:47-49: lattice_init() if PERIODIC && !PMGRID
       if(rcl)
         return rcl;
+    }
+  if(!latt)
+    {
+      int rcu = user_tables_ensure(c, user_reach(c));
+      if(rcu)
+        return rcu;
     }
   WalkParams wp;
   make_walk_params(c, &wp);
@@ -2693,13 +2771,19 @@ int walk_run(ngravs_ctx *c)
     switch(c->cfg.n_gravs)
       {
       case 1:
-        pm ? launch_strict<1, true, false>(c, wp, li) : (latt ? launch_strict<1, false, true>(c, wp, li) : launch_strict<1, false, false>(c, wp, li));
+        pm ? (wp.user ? launch_strict<1, true, false, true>(c, wp, li) : launch_strict<1, true, false>(c, wp, li))
+           : (latt ? launch_strict<1, false, true>(c, wp, li)
+                   : (wp.user ? launch_strict<1, false, false, true>(c, wp, li) : launch_strict<1, false, false>(c, wp, li)));
         break;
       case 2:
-        pm ? launch_strict<2, true, false>(c, wp, li) : (latt ? launch_strict<2, false, true>(c, wp, li) : launch_strict<2, false, false>(c, wp, li));
+        pm ? (wp.user ? launch_strict<2, true, false, true>(c, wp, li) : launch_strict<2, true, false>(c, wp, li))
+           : (latt ? launch_strict<2, false, true>(c, wp, li)
+                   : (wp.user ? launch_strict<2, false, false, true>(c, wp, li) : launch_strict<2, false, false>(c, wp, li)));
         break;
       default:
-        pm ? launch_strict<3, true, false>(c, wp, li) : (latt ? launch_strict<3, false, true>(c, wp, li) : launch_strict<3, false, false>(c, wp, li));
+        pm ? (wp.user ? launch_strict<3, true, false, true>(c, wp, li) : launch_strict<3, true, false>(c, wp, li))
+           : (latt ? launch_strict<3, false, true>(c, wp, li)
+                   : (wp.user ? launch_strict<3, false, false, true>(c, wp, li) : launch_strict<3, false, false>(c, wp, li)));
         break;
       }
   };
@@ -2847,8 +2931,20 @@ int walk_finish(ngravs_ctx *c)
 }
 
 // direct sum for explicit target records over the OWN particles of this task (distributed gravity_forcetest)
-int direct_run_targets(ngravs_ctx *c, const double4 *d_tpm, const int *d_ttype, int64_t nt, double *d_acc)
+int direct_run_targets(ngravs_ctx *c, const double4 *d_tpm, const int *d_ttype, int64_t nt, double *d_acc, double r_need)
 {
+  if(c->cfg.periodic && cfg_has_user(c->cfg))
+    {
+      ngravs_report(c, NGRAVS_ERR_WIRING, "the periodic direct sum adds the lattice correction of the law (forcetree.c:3515-3529), "
+                                          "which user-defined laws do not have");
+      return NGRAVS_ERR_WIRING;
+    }
+  if(!c->cfg.periodic)
+    {
+      int rcu = user_tables_ensure(c, fmax(r_need, user_reach(c)));
+      if(rcu)
+        return rcu;
+    }
   WalkParams wp;
   make_walk_params(c, &wp);
   LawIds li;
@@ -2860,7 +2956,7 @@ int direct_run_targets(ngravs_ctx *c, const double4 *d_tpm, const int *d_ttype, 
       if(rcl)
         return rcl;
     }
-  hipLaunchKernelGGL(k_direct, dim3((unsigned)nt), dim3(256), 0, c->stream, c->s_pm.p, c->s_type.p, (long long)c->n, (const int *)nullptr,
+  hipLaunchKernelGGL(wp.user ? k_direct<true> : k_direct<false>, dim3((unsigned)nt), dim3(256), 0, c->stream, c->s_pm.p, c->s_type.p, (long long)c->n, (const int *)nullptr,
                      (long long)nt, wp, li, c->cfg.G, latt ? c->lat.p : (const double *)nullptr, d_acc, d_tpm, d_ttype, c->s_active.p, 1);
   HIP_TRY(c, hipGetLastError());
   return NGRAVS_OK;
@@ -2868,6 +2964,18 @@ int direct_run_targets(ngravs_ctx *c, const double4 *d_tpm, const int *d_ttype, 
 
 int direct_run(ngravs_ctx *c, const int *d_idx, int64_t nt, double *d_acc)
 {
+  if(c->cfg.periodic && cfg_has_user(c->cfg))
+    {
+      ngravs_report(c, NGRAVS_ERR_WIRING, "the periodic direct sum adds the lattice correction of the law (forcetree.c:3515-3529), "
+                                          "which user-defined laws do not have");
+      return NGRAVS_ERR_WIRING;
+    }
+  if(!c->cfg.periodic)
+    {
+      int rcu = user_tables_ensure(c, user_reach(c));
+      if(rcu)
+        return rcu;
+    }
   WalkParams wp;
   make_walk_params(c, &wp);
   LawIds li;
@@ -2879,8 +2987,9 @@ int direct_run(ngravs_ctx *c, const int *d_idx, int64_t nt, double *d_acc)
       if(rcl)
         return rcl;
     }
-  hipLaunchKernelGGL(k_direct, dim3((unsigned)nt), dim3(256), 0, c->stream, c->s_pm.p, c->s_type.p, (long long)c->n, d_idx,
-                     (long long)nt, wp, li, c->cfg.G, latt ? c->lat.p : (const double *)nullptr, d_acc);
+  hipLaunchKernelGGL(wp.user ? k_direct<true> : k_direct<false>, dim3((unsigned)nt), dim3(256), 0, c->stream, c->s_pm.p, c->s_type.p, (long long)c->n, d_idx,
+                     (long long)nt, wp, li, c->cfg.G, latt ? c->lat.p : (const double *)nullptr, d_acc, (const double4 *)nullptr,
+                     (const int *)nullptr, (const unsigned char *)nullptr, 0);
   HIP_TRY(c, hipGetLastError());
   return NGRAVS_OK;
 }

@@ -40,6 +40,11 @@ struct GreenParams
   double ym2;          // (YUKAWA_IMASS / 2 pi)^2                                 ngravs.c:871
   double yfac;         // exp(-ym^2 asmth2)                                       ngravs.c:877
   double cN[NG_MAX][NG_MAX], cY[NG_MAX][NG_MAX];   // [source][target], as pm_periodic.c:490 indexes GreensFxns
+  // user-defined Green's functions (ngravs_create_with_laws): G(k2) tabulated at the integer k2 = 0 .. 3 (N/2)^2 (user_laws.cpp),
+  // table uslot[a][b] of ug (-1: built-in pair); ug == nullptr when no user id is wired
+  const double *ug;
+  long long nk2;
+  int uslot[NG_MAX][NG_MAX];
 };
 
 
@@ -83,7 +88,10 @@ __device__ __forceinline__ void green_mode(const GreenParams &gp, int x, int y, 
 #pragma unroll
           for(int b = 0; b < NG; b++)
             {
-              double smth = (gp.cN[a][b] * gN + gp.cY[a][b] * gY) * common;
+              double g = gp.cN[a][b] * gN + gp.cY[a][b] * gY;
+              if(gp.ug && gp.uslot[a][b] >= 0)
+                g = gp.ug[gp.uslot[a][b] * gp.nk2 + (long long)k2];   // k2 is an integer <= 3 (N/2)^2
+              double smth = g * common;
               out[b].x += r.x * smth;
               out[b].y += r.y * smth;
             }
@@ -110,7 +118,10 @@ static inline void make_green_params(const ngravs_ctx *c, GreenParams *gpp)
         int law = c->cfg.law_greens[a][b];   // [source][target] (pm_periodic.c:490)
         gp.cN[a][b] = law == NGRAVS_LAW_NEWTON || law == NGRAVS_LAW_COLOYUK ? 1.0 : (law == NGRAVS_LAW_NEG_NEWTON ? -1.0 : 0.0);
         gp.cY[a][b] = law == NGRAVS_LAW_YUKAWA || law == NGRAVS_LAW_COLOYUK ? 1.0 : 0.0;
+        gp.uslot[a][b] = law >= NGRAVS_LAW_USER0 ? law - NGRAVS_LAW_USER0 : -1;
       }
+  gp.ug = c->user_green.p;   // built by user_green_ensure (only with a user id in law_greens)
+  gp.nk2 = c->user_green_nk2;
 }
 
 #define FFT_TRY(ctx, expr)                                                                  \

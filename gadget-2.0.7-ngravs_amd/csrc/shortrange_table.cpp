@@ -45,7 +45,7 @@ static double normed_green(const ngravs_config_t *c, double asmth, int law, doub
     }
 }
 
-void host_shortrange_table(const ngravs_config_t *cfg, double *force, double *pot)
+void host_shortrange_table(const ngravs_config_t *cfg, double *force, double *pot, const ngravs_user_fn_t *fns, int nfns)
 {
   const int ntab = NTAB, len = 3, ol = 8;
   const double n = 12.0 * ntab * ol * len - 6.0 * ol * len + 2.0;          // ngravs_core.c:177
@@ -61,7 +61,8 @@ void host_shortrange_table(const ngravs_config_t *cfg, double *force, double *po
         for(int j = 0; j < (int)(n / 2); j++)
           {
             double kj = dk * j, k2 = kj * kj;
-            double v = normed_green(cfg, asmth, law, k2) * std::exp(-k2 * Z * Z);
+            double v = (law >= NGRAVS_LAW_USER0 ? user_normed(fns, nfns, law, k2) : normed_green(cfg, asmth, law, k2)) *
+                       std::exp(-k2 * Z * Z);
             if(v == 0.0 && kj > 60.0)
               break;
             f.push_back(v);

@@ -1,0 +1,423 @@
+// user_laws.cpp -- host side of the user-defined force laws (ngravs_create_with_laws).
+//
+// The reference calls its laws through `gravity` pointers (allvars.h:134-146); a model's own ngravs.c wires its own functions
+// there.  The device cannot call host code, so each user law is sampled here into piecewise polynomials (engine.hpp UserTabs)
+// which the kernels evaluate: the r-space force as g(r) = r^2 accel(1, 1, r^2, r, 1) over octaves of r, the softened force per
+// distinct softening length over u = r/h in [0, 1).  Degree 7 at the Chebyshev nodes of every sub-interval; the number of
+// sub-intervals is doubled until the fit agrees with the callback to UL_TOL at check points between the nodes.
+#include <cmath>
+#include <vector>
+#include "engine.hpp"
+
+#define UL_TOL 1e-11        // relative deviation allowed at the check points (the tests ask for 1e-9 at random r)
+#define UL_S_MIN 32
+#define UL_S_MAX 2048
+#define UL_FAIL 1e-9        // ... and the deviation at which a law is refused rather than evaluated from its tables
+
+// degree-7 interpolant of phi at the Chebyshev nodes of [-1, 1], as monomial coefficients c[0..7]
+template <typename F> static void cheb_fit(F &&phi, double *c)
+{
+  double v[UL_NC], a[UL_NC];
+  for(int j = 0; j < UL_NC; j++)
+    v[j] = phi(cos(M_PI * (j + 0.5) / UL_NC));
+  for(int k = 0; k < UL_NC; k++)
+    {
+      double s = 0;
+      for(int j = 0; j < UL_NC; j++)
+        s += v[j] * cos(M_PI * k * (j + 0.5) / UL_NC);
+      a[k] = s * (k == 0 ? 1.0 : 2.0) / UL_NC;
+    }
+  // T_k as monomials: T_0 = 1, T_1 = t, T_k = 2 t T_{k-1} - T_{k-2}
+  double T[UL_NC][UL_NC] = {};
+  T[0][0] = 1;
+  T[1][1] = 1;
+  for(int k = 2; k < UL_NC; k++)
+    for(int j = 0; j < UL_NC; j++)
+      T[k][j] = (j > 0 ? 2 * T[k - 1][j - 1] : 0.0) - T[k - 2][j];
+  for(int j = 0; j < UL_NC; j++)
+    {
+      c[j] = 0;
+      for(int k = 0; k < UL_NC; k++)
+        c[j] += a[k] * T[k][j];
+    }
+}
+
+// fit phi(x) on n equal sub-intervals of a range (x(j, t): the point of sub-interval j at t in [-1, 1]) into out; returns the
+// largest relative deviation at the check points, relative to the sub-interval's largest |value|
+template <typename X, typename F> static double fit_run(int n, X &&x, F &&phi, double *out)
+{
+  static const double chk[3] = {0.913, -0.547, 0.171};
+  double worst = 0;
+  for(int j = 0; j < n; j++)
+    {
+      double *c = out + (size_t)j * UL_NC, scale = 0;
+      cheb_fit([&](double t) {
+        const double v = phi(x(j, t));
+        scale = fmax(scale, fabs(v));
+        return v;
+      }, c);
+      for(double t : chk)
+        {
+          const double v = phi(x(j, t)), d = fabs(ul_poly(c, t) - v);
+          const double s = fmax(scale, fabs(v));
+          if(s > 0)
+            worst = fmax(worst, d / s);
+          else if(d > 0 || v != v)
+            worst = INFINITY;
+        }
+    }
+  return worst;
+}
+
+// r-space table of one law over octaves e_lo .. e_lo + n_oct - 1 with S sub-intervals each
+static double fit_accel(ngravs_gravity_fn f, int e_lo, int n_oct, int S, double *out)
+{
+  double worst = 0;
+  for(int o = 0; o < n_oct; o++)
+    {
+      const int e = e_lo + o;
+      auto x = [&](int j, double t) { return ldexp(0.5 + (j + 0.5 * (t + 1)) / (2.0 * S), e); };
+      auto g = [&](double r) { return r * r * f(1.0, 1.0, r * r, r, 1); };
+      worst = fmax(worst, fit_run(S, x, g, out + (size_t)o * S * UL_NC));
+    }
+  return worst;
+}
+static double fit_spline(ngravs_gravity_fn f, double h, int S, double *out)
+{
+  auto x = [&](int j, double t) { return (j + 0.5 * (t + 1)) / S; };
+  auto s = [&](double u) { return f(1.0, 1.0, h, u * h, 1); };
+  return fit_run(S, x, s, out);
+}
+
+// octave layout covering [r_lo, r_hi]: r in octave e when 2^(e-1) <= r < 2^e
+static void octaves(double r_lo, double r_hi, int *e_lo, int *n_oct)
+{
+  int a, b;
+  (void)frexp(r_lo, &a);
+  (void)frexp(r_hi, &b);
+  *e_lo = a;
+  *n_oct = b - a + 1;
+}
+
+// distinct positive softening lengths (at most NGRAVS_NTYPES)
+static int distinct_soft(const double *fs, double *h)
+{
+  int nh = 0;
+  for(int t = 0; t < NGRAVS_NTYPES; t++)
+    {
+      bool seen = !(fs[t] > 0);
+      for(int q = 0; q < nh && !seen; q++)
+        seen = h[q] == fs[t];
+      if(!seen)
+        h[nh++] = fs[t];
+    }
+  return nh;
+}
+
+// Build the accel tables of every ACCEL entry and the spline tables of every SPLINE entry of a registry into host memory.
+// r_hi: largest r the walks can evaluate.  Returns the largest check-point deviation.
+static double build_tables(const ngravs_user_fn_t *fns, int nfns, const double *fsoft, double r_hi, UserTabs *ut, std::vector<double> &h)
+{
+  double hs[NGRAVS_NTYPES];
+  const int nh = distinct_soft(fsoft, hs);
+  double r_lo = INFINITY;
+  for(int q = 0; q < nh; q++)
+    r_lo = fmin(r_lo, hs[q]);
+  if(!(r_lo < INFINITY))
+    r_lo = ldexp(r_hi, -30);   // no softening: the table starts 30 octaves below its end (smaller r clamp to the first octave)
+  r_lo = fmin(r_lo, 0.5 * r_hi);
+  int e_lo, n_oct;
+  octaves(r_lo, r_hi, &e_lo, &n_oct);
+  double worst = 0;
+  int S = UL_S_MIN, Ss = UL_S_MIN;
+  std::vector<double> acc, spl;
+  for(;;)
+    {
+      acc.assign((size_t)nfns * n_oct * S * UL_NC, 0.0);
+      double w = 0;
+      for(int k = 0; k < nfns; k++)
+        if(fns[k].kind == NGRAVS_USER_ACCEL)
+          w = fmax(w, fit_accel(fns[k].fn, e_lo, n_oct, S, acc.data() + (size_t)k * n_oct * S * UL_NC));
+      if(w <= UL_TOL || S >= UL_S_MAX)
+        {
+          worst = fmax(worst, w);
+          break;
+        }
+      S *= 2;
+    }
+  for(;;)
+    {
+      spl.assign((size_t)nfns * nh * Ss * UL_NC, 0.0);
+      double w = 0;
+      for(int k = 0; k < nfns; k++)
+        if(fns[k].kind == NGRAVS_USER_SPLINE)
+          for(int q = 0; q < nh; q++)
+            w = fmax(w, fit_spline(fns[k].fn, hs[q], Ss, spl.data() + ((size_t)k * nh + q) * Ss * UL_NC));
+      if(w <= UL_TOL || Ss >= UL_S_MAX)
+        {
+          worst = fmax(worst, w);
+          break;
+        }
+      Ss *= 2;
+    }
+  h.assign(acc.begin(), acc.end());
+  h.insert(h.end(), spl.begin(), spl.end());
+  *ut = UserTabs{};
+  ut->e_lo = e_lo;
+  ut->n_oct = n_oct;
+  ut->S = S;
+  ut->nh = nh;
+  ut->Ss = Ss;
+  for(int q = 0; q < nh; q++)
+    ut->h[q] = hs[q];
+  ut->coef = nullptr;
+  ut->spl = (const double *)(uintptr_t)(acc.size() * sizeof(double));   // offset; rebased by the caller
+  return worst;
+}
+
+int user_green_ensure(ngravs_ctx *c)
+{
+  const ngravs_config_t &cfg = c->cfg;
+  bool any = false;
+  for(int a = 0; a < cfg.n_gravs; a++)
+    for(int b = 0; b < cfg.n_gravs; b++)
+      any = any || cfg.law_greens[a][b] >= NGRAVS_LAW_USER0;
+  if(!any || !cfg.pmgrid || c->user_green_nk2 > 0)
+    return NGRAVS_OK;
+  // pm_periodic.c:440-490: k2 = kx^2 + ky^2 + kz^2 with |k.| <= N/2 is an integer; GreensFxns(MassTable[a], MassTable[b], k2,
+  // sqrt(k2), 1) -- independent of the masses (checked at creation)
+  const long long half = cfg.pmgrid / 2, nk2 = 3 * half * half + 1;
+  const int nfns = (int)c->user_fns.size();
+  std::vector<double> h((size_t)nfns * nk2, 0.0);
+  for(int k = 0; k < nfns; k++)
+    if(c->user_fns[k].kind == NGRAVS_USER_GREENS)
+      for(long long q = 1; q < nk2; q++)
+        h[(size_t)k * nk2 + q] = c->user_fns[k].fn(1.0, 1.0, (double)q, sqrt((double)q), 1);
+  if(c->user_green.ensure(h.size()))
+    return NGRAVS_ERR_NOMEM;
+  HIP_TRY(c, hipMemcpyAsync(c->user_green.p, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  c->user_green_nk2 = nk2;
+  return NGRAVS_OK;
+}
+
+int user_tables_ensure(ngravs_ctx *c, double r_need)
+{
+  if(c->user_fns.empty() || !cfg_has_user(c->cfg))
+    return NGRAVS_OK;
+  bool same_soft = true;
+  for(int t = 0; t < NGRAVS_NTYPES; t++)
+    same_soft = same_soft && c->user_soft[t] == c->cfg.force_softening[t];
+  const double top = c->user_ready ? ldexp(1.0, c->user_ut.e_lo + c->user_ut.n_oct - 1) : 0.0;
+  if(c->user_ready && same_soft && r_need < top)
+    return NGRAVS_OK;
+  // grow geometrically so that a slowly expanding domain re-tabulates rarely
+  const double r_hi = fmax(r_need, 2.0 * top);
+  std::vector<double> h;
+  UserTabs ut;
+  const double worst = build_tables(c->user_fns.data(), (int)c->user_fns.size(), c->cfg.force_softening, r_hi > 0 ? r_hi : 1.0, &ut, h);
+  if(!(worst <= UL_FAIL))
+    {
+      ngravs_report(c, NGRAVS_ERR_WIRING, "a user-defined law cannot be tabulated to 1e-9 with " + std::to_string(UL_S_MAX) +
+                                               " sub-intervals per octave / softening (a kink or a steep feature?): deviation " +
+                                               std::to_string(worst));
+      return NGRAVS_ERR_WIRING;
+    }
+  const size_t spl_off = (size_t)(uintptr_t)ut.spl / sizeof(double);
+  if(c->user_tab.ensure(h.size() + 1))
+    return NGRAVS_ERR_NOMEM;
+  HIP_TRY(c, hipMemcpyAsync(c->user_tab.p, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  ut.coef = c->user_tab.p;
+  ut.spl = c->user_tab.p + spl_off;
+  c->user_ut = ut;
+  for(int t = 0; t < NGRAVS_NTYPES; t++)
+    c->user_soft[t] = c->cfg.force_softening[t];
+  c->user_ready = true;
+  return NGRAVS_OK;
+}
+
+extern "C" int ngravs_user_table_eval(const ngravs_user_fn_t *fn, double r_lo, double r_hi, double h, const double *r, int64_t n,
+                                      double *out, double *max_err)
+{
+  if(!fn || !fn->fn || !r || !out || n < 0 || (fn->kind != NGRAVS_USER_ACCEL && fn->kind != NGRAVS_USER_SPLINE))
+    return NGRAVS_ERR_ARG;
+  double fs[NGRAVS_NTYPES] = {0, 0, 0, 0, 0, 0};
+  if(fn->kind == NGRAVS_USER_ACCEL)
+    {
+      if(!(r_lo > 0) || !(r_hi > r_lo))
+        return NGRAVS_ERR_ARG;
+      fs[0] = r_lo;
+    }
+  else
+    {
+      if(!(h > 0))
+        return NGRAVS_ERR_ARG;
+      fs[0] = h;
+    }
+  std::vector<double> tab;
+  UserTabs ut;
+  const double w = build_tables(fn, 1, fs, fn->kind == NGRAVS_USER_ACCEL ? r_hi : 2 * h, &ut, tab);
+  const size_t spl_off = (size_t)(uintptr_t)ut.spl / sizeof(double);
+  ut.coef = tab.data();
+  ut.spl = tab.data() + spl_off;
+  for(int64_t i = 0; i < n; i++)
+    out[i] = fn->kind == NGRAVS_USER_ACCEL ? ul_g(ut, 0, r[i]) / (r[i] * r[i]) : ul_spline(ut, 0, h, r[i]);
+  if(max_err)
+    *max_err = w;
+  return NGRAVS_OK;
+}
+
+// ---- the checks of ngravs_create_with_laws ----------------------------------------------------------------------------------
+static bool is_user(int id) { return id >= NGRAVS_LAW_USER0; }
+
+// built-in laws at the probe of ngravs_core.c:367-403 (the reference's own functions, ngravs.c:351-455, 826-885)
+static bool builtin_value(const ngravs_config_t *cfg, int kind, int id, double t, double s, double x, double r, double *v)
+{
+  const double ym = cfg->box_size > 0 ? cfg->yukawa_imass / cfg->box_size : 0.0;
+  if(id == 0)
+    {
+      *v = 0;
+      return true;
+    }
+  if(kind == NGRAVS_USER_ACCEL)
+    switch(id)
+      {
+      case NGRAVS_LAW_NEWTON: *v = s / x; return true;
+      case NGRAVS_LAW_NEG_NEWTON: *v = -s / x; return true;
+      case NGRAVS_LAW_YUKAWA: *v = s * exp(-r * ym) * (ym / r + 1.0 / x); return true;
+      case NGRAVS_LAW_COLOYUK: *v = s * exp(-r * ym) * (ym / r + 1.0 / x) + s / x; return true;
+      default: return false;
+      }
+  if(kind == NGRAVS_USER_SPLINE && (id == NGRAVS_SPLINE_PLUMMER || id == NGRAVS_SPLINE_NEG_PLUMMER))
+    {
+      const double hi = 1 / x;
+      double u = r * hi, w;
+      if(u < 0.5)
+        w = s * hi * hi * hi * (10.666666666667 + u * u * (32.0 * u - 38.4));
+      else
+        w = s * hi * hi * hi * (21.333333333333 - 48.0 * u + 38.4 * u * u - 10.666666666667 * u * u * u - 0.066666666667 / (u * u * u));
+      *v = id == NGRAVS_SPLINE_NEG_PLUMMER ? -w : w;
+      return true;
+    }
+  if(kind == NGRAVS_USER_GREENS && (id == NGRAVS_LAW_NEWTON || id == NGRAVS_LAW_NEG_NEWTON))
+    {
+      *v = id == NGRAVS_LAW_NEWTON ? 1.0 / x : -1.0 / x;   // pgdelta / neg_pgdelta
+      return true;
+    }
+  if(kind == NGRAVS_USER_NORMED && (id == NGRAVS_LAW_NEWTON || id == NGRAVS_LAW_NEG_NEWTON))
+    {
+      *v = id == NGRAVS_LAW_NEWTON ? 1.0 : -1.0;             // normed_pgdelta / its negative
+      return true;
+    }
+  return false;
+}
+
+static bool close_to(double a, double b) { return a == b || fabs(a - b) <= 1e-12 * fmax(fabs(a), fabs(b)); }
+
+int user_check_config(const ngravs_config_t *cfg, const ngravs_user_fn_t *fns, int nfns, std::string &why)
+{
+  if(nfns < 0 || nfns > NGRAVS_MAX_USER_FNS || (nfns > 0 && !fns))
+    {
+      why = "user-law registry: at most NGRAVS_MAX_USER_FNS entries";
+      return NGRAVS_ERR_ARG;
+    }
+  for(int k = 0; k < nfns; k++)
+    if(!fns[k].fn || fns[k].kind < NGRAVS_USER_ACCEL || fns[k].kind > NGRAVS_USER_NORMED)
+      {
+        why = "user-law registry entry " + std::to_string(k) + ": no function or unknown kind";
+        return NGRAVS_ERR_ARG;
+      }
+  const int ng = cfg->n_gravs;
+  const int(*tabs[4])[NGRAVS_MAX_GRAVS] = {cfg->law_accel, cfg->law_spline, cfg->law_greens, cfg->law_normed};
+  static const char *names[4] = {"law_accel", "law_spline", "law_greens", "law_normed"};
+  bool any = false;
+  for(int kind = 0; kind < 4; kind++)
+    for(int i = 0; i < ng; i++)
+      for(int j = 0; j < ng; j++)
+        {
+          const int id = tabs[kind][i][j];
+          if(!is_user(id))
+            continue;
+          any = true;
+          const int k = id - NGRAVS_LAW_USER0;
+          if(k >= nfns || fns[k].kind != kind)
+            {
+              why = std::string(names[kind]) + "[" + std::to_string(i) + "][" + std::to_string(j) + "] = " + std::to_string(id) +
+                    (k >= nfns ? ": user id outside the registry" : ": registry entry of another kind");
+              return NGRAVS_ERR_WIRING;
+            }
+        }
+  if(!any)
+    return NGRAVS_OK;
+  if(cfg->periodic && !cfg->pmgrid)
+    {
+      why = "user-defined laws in a periodic tree-only run: the lattice correction would need the model's own LatticeForce "
+            "tables (out of scope; TreePM and non-periodic tree-only runs take user laws)";
+      return NGRAVS_ERR_WIRING;
+    }
+  // Newton's third law, the reference's probe F[i][j](1,1,0.5,3,1) == F[j][i](1,1,0.5,3,1) (ngravs_core.c:367-403)
+  for(int kind = 0; kind < 4; kind++)
+    for(int i = 0; i < ng; i++)
+      for(int j = 0; j < ng; j++)
+        {
+          const int a = tabs[kind][i][j], b = tabs[kind][j][i];
+          if(!is_user(a) && !is_user(b))
+            continue;
+          double va, vb;
+          bool ok = is_user(a) ? (va = fns[a - NGRAVS_LAW_USER0].fn(1, 1, 0.5, 3, 1), true) : builtin_value(cfg, kind, a, 1, 1, 0.5, 3, &va);
+          ok = ok && (is_user(b) ? (vb = fns[b - NGRAVS_LAW_USER0].fn(1, 1, 0.5, 3, 1), true) : builtin_value(cfg, kind, b, 1, 1, 0.5, 3, &vb));
+          if(!ok)
+            {
+              why = std::string(names[kind]) + ": a user law paired with a built-in law that cannot be probed on the host";
+              return NGRAVS_ERR_WIRING;
+            }
+          if(!(va == vb))
+            {
+              why = std::string(names[kind]) + "[" + std::to_string(i) + "][" + std::to_string(j) +
+                    "]: force-law table violates Newton's third law (ngravs_core.c:371-403)";
+              return NGRAVS_ERR_WIRING;
+            }
+        }
+  // what a tree can represent: linear in the source mass, independent of the target mass and of N
+  for(int k = 0; k < nfns; k++)
+    {
+      ngravs_gravity_fn f = fns[k].fn;
+      auto probe = [&](double x, double r) -> bool {
+        const double v = f(1, 1, x, r, 1);
+        if(fns[k].kind == NGRAVS_USER_GREENS || fns[k].kind == NGRAVS_USER_NORMED)
+          return close_to(f(2, 3, x, r, 1), v) && close_to(f(1, 1, x, r, 7), v);
+        return std::isfinite(v) && close_to(f(1, 2, x, r, 1), 2 * v) && close_to(f(1, 0.25, x, r, 1), 0.25 * v) &&
+               close_to(f(3, 1, x, r, 1), v) && close_to(f(1, 1, x, r, 7), v);
+      };
+      bool ok = true;
+      if(fns[k].kind == NGRAVS_USER_ACCEL)
+        for(double r : {1e-3, 0.05, 0.7, 3.0, 40.0, 900.0})
+          ok = ok && probe(r * r, r);
+      else if(fns[k].kind == NGRAVS_USER_SPLINE)
+        for(double u : {0.05, 0.3, 0.6, 0.95})
+          ok = ok && probe(1.0, u);
+      else
+        for(double k2 : {0.5, 3.0, 40.0})
+          ok = ok && probe(k2, sqrt(k2));
+      if(!ok)
+        {
+          why = "user-law registry entry " + std::to_string(k) +
+                (fns[k].kind <= NGRAVS_USER_SPLINE
+                     ? ": the tree needs a force linear in the source mass and independent of the target mass and of N "
+                       "(a node's monopole is a mass sum)"
+                     : ": a Green's function must not depend on its mass arguments");
+          return NGRAVS_ERR_WIRING;
+        }
+    }
+  return NGRAVS_OK;
+}
+
+// NormedGreensFxns of a user id for the short-range table (k^2 in the table's units, shortrange_table.cpp)
+double user_normed(const ngravs_user_fn_t *fns, int nfns, int law, double k2)
+{
+  const int k = law - NGRAVS_LAW_USER0;
+  if(k < 0 || k >= nfns || fns[k].kind != NGRAVS_USER_NORMED)
+    return 0.0;
+  return fns[k].fn(1.0, 1.0, k2, sqrt(k2), 1);
+}

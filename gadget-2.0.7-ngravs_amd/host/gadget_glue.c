@@ -55,8 +55,32 @@ static ngravs_ctx *Ctx = NULL;
 static ngravs_comm Comm;
 static unsigned char *ActiveFlag = NULL;
 
+/* A wired function the library has no built-in for -- a model's own law in its ngravs.c -- is handed over as a user-defined law
+ * (ngravs_create_with_laws): the library samples it on the host into tables its kernels evaluate.  One registry entry per
+ * distinct (pointer, kind). */
+static ngravs_user_fn_t UserFns[NGRAVS_MAX_USER_FNS];
+static int NUserFns = 0;
+
+static int user_id(gravity f, int kind)
+{
+  int k;
+
+  for(k = 0; k < NUserFns; k++)
+    if(UserFns[k].fn == f && UserFns[k].kind == kind)
+      return k;
+  if(NUserFns == NGRAVS_MAX_USER_FNS)
+    {
+      printf("ngravs-hip: more than %d distinct user-defined force-law functions are wired\n", NGRAVS_MAX_USER_FNS);
+      endrun(1050);
+    }
+  UserFns[NUserFns].kind = kind;
+  UserFns[NUserFns].reserved = 0;
+  UserFns[NUserFns].fn = f;
+  return NUserFns++;
+}
+
 /* wired function pointer -> law id (the device cannot call through `gravity` pointers) */
-static int law_id(gravity f)
+static int law_id(gravity f, int kind)
 {
   if(f == none)
     return NGRAVS_LAW_NONE;
@@ -74,9 +98,7 @@ static int law_id(gravity f)
     return NGRAVS_LAW_SOURCEBAM;
   if(f == sourcebaryonbam)
     return NGRAVS_LAW_TARGETBAM;
-  printf("ngravs-hip: a wired force law has no device implementation\n");
-  endrun(1050);
-  return -1;
+  return NGRAVS_LAW_USER0 + user_id(f, kind);
 }
 static int spline_id(gravity f)
 {
@@ -92,8 +114,7 @@ static int spline_id(gravity f)
     return NGRAVS_SPLINE_SOURCEBAM;
   if(f == sourcebaryonbam_spline)
     return NGRAVS_SPLINE_TARGETBAM;
-  endrun(1051);
-  return -1;
+  return NGRAVS_SPLINE_USER0 + user_id(f, NGRAVS_USER_SPLINE);
 }
 
 static void on_fatal(int code, const char *msg)
@@ -204,11 +225,11 @@ static void ensure_ctx(void)
   for(i = 0; i < N_GRAVS; i++)
     for(j = 0; j < N_GRAVS; j++)
       {
-        cfg.law_accel[i][j] = law_id(AccelFxns[i][j]);
+        cfg.law_accel[i][j] = law_id(AccelFxns[i][j], NGRAVS_USER_ACCEL);
         cfg.law_spline[i][j] = spline_id(AccelSplines[i][j]);
 #ifdef PMGRID
-        cfg.law_greens[i][j] = law_id(GreensFxns[i][j]);
-        cfg.law_normed[i][j] = law_id(NormedGreensFxns[i][j]);
+        cfg.law_greens[i][j] = law_id(GreensFxns[i][j], NGRAVS_USER_GREENS);
+        cfg.law_normed[i][j] = law_id(NormedGreensFxns[i][j], NGRAVS_USER_NORMED);
 #endif
       }
 #ifdef YUKAWA_IMASS
@@ -229,8 +250,17 @@ static void ensure_ctx(void)
 #ifdef NGRAVS_GLUE_DEVICE
   cfg.device = NGRAVS_GLUE_DEVICE;	/* rehearsals: several tasks on one GPU */
 #endif
-  if(ngravs_create(&cfg, &Ctx) != NGRAVS_OK)
-    endrun(1053);
+  {
+    int rc = NUserFns > 0 ? ngravs_create_with_laws(&cfg, UserFns, NUserFns, &Ctx) : ngravs_create(&cfg, &Ctx);
+
+    if(rc == NGRAVS_ERR_WIRING && NUserFns > 0)
+      {
+        printf("ngravs-hip: the wired force laws cannot be evaluated: %s\n", ngravs_last_error(NULL));
+        endrun(1050);
+      }
+    if(rc != NGRAVS_OK)
+      endrun(1053);
+  }
   ngravs_set_fatal_handler(Ctx, on_fatal);
   memset(&Comm, 0, sizeof(Comm));
 #ifdef NGRAVS_WITH_RCCL

@@ -75,6 +75,13 @@ typedef enum {
   NGRAVS_SPLINE_COUNT
 } ngravs_spline;
 
+/* User-defined laws (ngravs_create_with_laws): entry k of the registry is named NGRAVS_LAW_USER0 + k (accel, greens, normed
+ * entries) or NGRAVS_SPLINE_USER0 + k (spline entries) and goes into law_accel / law_spline / law_greens / law_normed like a
+ * built-in id. */
+#define NGRAVS_LAW_USER0 64
+#define NGRAVS_SPLINE_USER0 64
+#define NGRAVS_MAX_USER_FNS 8
+
 typedef enum {
   NGRAVS_OK = 0,
   NGRAVS_ERR_ARG = -1,        /* bad argument / unsupported configuration                 */
@@ -165,12 +172,47 @@ typedef struct {
 typedef struct ngravs_ctx ngravs_ctx;
 typedef void (*ngravs_fatal_fn)(int code, const char *msg);
 
+/* A force law of the host: exactly the reference's `gravity` type (allvars.h:134), so that AccelFxns[i][j] etc. pass without
+ * casts.  accel: f(target mass, source mass, r^2, r, N); spline: f(target, source, h, r, N), the softened force already divided
+ * by r (ngravs.c, the WARNING above plummer); greens / normed: f(target, source, k^2, k, N). */
+typedef double (*ngravs_gravity_fn)(double, double, double, double, long);
+typedef enum {
+  NGRAVS_USER_ACCEL = 0,    /* AccelFxns        */
+  NGRAVS_USER_SPLINE = 1,   /* AccelSplines     */
+  NGRAVS_USER_GREENS = 2,   /* GreensFxns       */
+  NGRAVS_USER_NORMED = 3    /* NormedGreensFxns */
+} ngravs_user_kind;
+typedef struct {
+  int32_t kind;             /* ngravs_user_kind */
+  int32_t reserved;
+  ngravs_gravity_fn fn;     /* called on the host only, at creation, in ngravs_set_softening and when a table grows; must
+                               stay valid as long as the context */
+} ngravs_user_fn_t;
+/* Which kernel the last ngravs_gravity_tree() walked with (ngravs_last_walk_kernel) */
+typedef enum {
+  NGRAVS_KERNEL_NONE = 0,
+  NGRAVS_KERNEL_STRICT = 1,        /* k_walk_strict, built-in laws                                  */
+  NGRAVS_KERNEL_STRICT_USER = 2,   /* k_walk_strict with the user-law tables                       */
+  NGRAVS_KERNEL_GROUP = 3,         /* the group walk, built-in laws                                 */
+  NGRAVS_KERNEL_GROUP_USER = 4     /* the group walk with user laws: the law-id variant (tree-only) or k_walk_group2<..., USR> (TreePM) */
+} ngravs_walk_kernel_id;
+
 /* ---- lifecycle ------------------------------------------------------------------------- */
 int ngravs_abi_version(void);
 const char *ngravs_build_info(void);                    /* arch, N_GRAVS instantiations, NTAB ... */
 void ngravs_config_default(ngravs_config_t *cfg);       /* N_GRAVS=1 Newton/plummer, tree-only    */
 /* init_grav_maps()+wire_grav_maps() checks (ngravs_core.c:321-424) happen here. */
 int ngravs_create(const ngravs_config_t *cfg, ngravs_ctx **out);
+/* ngravs_create with a registry of nfns <= NGRAVS_MAX_USER_FNS host laws (ngravs_create is this with an empty one).  The laws
+ * are sampled on the host into tables the kernels evaluate (DESIGN.md "User-defined force laws").  Refused with
+ * NGRAVS_ERR_WIRING and a message in ngravs_last_error(NULL): a user id outside the registry or of the wrong kind for its
+ * table; a pair that fails the reference's Newton's-third-law probe F[i][j](1,1,0.5,3,1) == F[j][i](...); an accel or spline
+ * law that is not linear in the source mass or depends on the target mass or N (a tree node's monopole is a mass sum); a
+ * Green's function that depends on its mass arguments; a user id in a periodic tree-only run (its lattice correction would
+ * need the model's own tables).  ngravs_last_error(NULL) is per thread. */
+int ngravs_create_with_laws(const ngravs_config_t *cfg, const ngravs_user_fn_t *fns, int nfns, ngravs_ctx **out);
+/* NGRAVS_KERNEL_* of the last walk of the context (0 before the first) */
+int ngravs_last_walk_kernel(ngravs_ctx *ctx);
 void ngravs_destroy(ngravs_ctx *ctx);
 void ngravs_set_fatal_handler(ngravs_ctx *ctx, ngravs_fatal_fn fn);
 /* Change the walk parameters between calls (All.ErrTolTheta latch, gravtree.c:334-335). */
@@ -282,6 +324,15 @@ int ngravs_peano_keys(ngravs_ctx *ctx, const double *pos, int64_t n, const doubl
 /* shortrange_fourier_force[target][source][NTAB] (forcetree.c:3246-3403): out has
  * n_gravs*n_gravs*NTAB doubles; pot_out (may be NULL) the matching shortrange_fourier_pot. */
 int ngravs_shortrange_table(const ngravs_config_t *cfg, double *force_out, double *pot_out);
+/* The same with a registry of user laws: a user id in law_normed calls its NORMED callback.  No GPU needed. */
+int ngravs_shortrange_table_with_laws(const ngravs_config_t *cfg, const ngravs_user_fn_t *fns, int nfns, double *force_out,
+                                      double *pot_out);
+/* The tables the kernels evaluate for one user law, built and evaluated on the host (no GPU): kind NGRAVS_USER_ACCEL tabulates
+ * fn over r in [r_lo, r_hi] and returns accel(1, 1, r^2, r, 1) from the table at the n radii r[]; NGRAVS_USER_SPLINE tabulates
+ * fn for softening h and returns spline(1, 1, h, r, 1) from the table (0 <= r < h).  *max_err (may be NULL): the largest
+ * relative deviation from the callback the fit saw at its check points. */
+int ngravs_user_table_eval(const ngravs_user_fn_t *fn, double r_lo, double r_hi, double h, const double *r, int64_t n, double *out,
+                           double *max_err);
 /* force_treeevaluate_direct for targets idx[0..nt) against all particles; with PERIODIC the nearest-image
  * sum plus lattice_corr (Ewald / lattice-sum tables, forcetree.c:3515-3529, 3803-3885), i.e. the truth
  * gravity_forcetest() compares the tree / TreePM force against; result xG into acc[3*nt]. */
