@@ -487,22 +487,12 @@ extern "C" int ngravs_set_tuning(ngravs_ctx *c, const char *name, double v)
     t.walk_nleaf = (int)iv;
   else if(k == "walk_exact_reach")
     t.walk_exact_reach = iv != 0;
-  else if(k == "pm_notile")
-    t.pm_notile = iv != 0;
-  else if(k == "pm_fused_gather")
-    t.pm_fused_gather = iv != 0;
-  else if(k == "pm_tile_gather")
-    t.pm_tile_gather = iv != 0;
   else if(k == "sort_full")
     t.sort_full = iv != 0;
-  else if(k == "pm_tile8")
-    t.pm_tile8 = iv != 0;
   else if(k == "tree_levelwise")
     t.tree_levelwise = iv != 0;
   else if(k == "dd_keep" && v >= 0 && v <= 0.25)
     t.dd_keep = v;
-  else if(k == "moments_octet")
-    t.moments_octet = iv != 0;
   else
     {
       ngravs_report(c, NGRAVS_ERR_ARG, "ngravs_set_tuning: unknown name or value out of range: " + k);

@@ -251,24 +251,24 @@ __global__ void k_gather_force(const double4 *__restrict__ s_pm, const unsigned 
 }
 
 // ---------------------------------------------------------------------------------------------------
-// Tiled variants.  The particles are Peano-sorted and the tree node of a level-Lt cell owns one contiguous
-// particle range, so one workgroup per node can deposit into / gather from an LDS copy of the mesh patch
-// the cell touches: the 8 scattered fp64 global atomics per particle (64 lanes -> 64 rows, the slow atomic
-// shape) become LDS atomics plus one coalesced atomic flush per patch row, and the gather's 72 scattered L2
-// reads per particle become LDS reads.  Particles that are direct children of nodes above level Lt (sparse
-// regions) go through the per-particle kernels.
+// Tiled deposit.  The particles are Peano-sorted and the tree node of a level-Lt cell owns one contiguous
+// particle range, so one workgroup per node can deposit into an LDS copy of the mesh patch the cell touches:
+// the 8 scattered fp64 global atomics per particle (64 lanes -> 64 rows, the slow atomic shape) become LDS
+// atomics plus one coalesced atomic flush per patch row.  Particles that are direct children of nodes above
+// level Lt (sparse regions) go through the per-particle kernel.  (A gather tiled the same way lost to the
+// two-pass gather of pm_finish, 13 against 6.3 ms at C4, and was removed.)
 // ---------------------------------------------------------------------------------------------------
 #define PM_DT 18                     // deposit patch edge: 16-cell node + CIC neighbour + 1 slack
-#define PM_GT (PM_DT + 4)            // gather patch edge: +-2 for the 4-point gradient
 #define PM_TILE_THREADS 1024
 
 
-template <int NG, int DT>
-__global__ __launch_bounds__(DT > 10 ? PM_TILE_THREADS : 256) void k_cic_deposit_tiled(
+template <int NG>
+__global__ __launch_bounds__(PM_TILE_THREADS) void k_cic_deposit_tiled(
     const double4 *__restrict__ s_pm, const unsigned char *__restrict__ s_type, const unsigned char *__restrict__ s_flag,
     const int *__restrict__ n_first, const int *__restrict__ n_count, const double4 *__restrict__ n_geo, int node0,
     double to_slab, int N, const int *__restrict__ t2g_tab, double *__restrict__ rho, MeshAddr ma)
 {
+  constexpr int DT = PM_DT;
   extern __shared__ double tile[];   // [NG][DT][DT][DT]
   const int node = node0 + blockIdx.x;
   const double4 geo = n_geo[node];
@@ -358,137 +358,16 @@ __global__ void k_cic_deposit_loose(const double4 *__restrict__ s_pm, const unsi
   atomicAdd(&grid[ma.cell(sx + 1, sy + 1, sz + 1)], m * (dx)*dy * dz);
 }
 
-// gather: one workgroup per node of the level whose cells are at most 8 mesh cells wide; the potential patches of
-// ALL species (edge 8 + misalignment + CIC neighbour + 2x2 gradient halo = 15) sit in LDS, one thread per particle
-#define PM_G8 15
-template <int NG>
-__global__ __launch_bounds__(256) void k_gradient_gather_tiled(
-    const double4 *__restrict__ s_pm, const unsigned char *__restrict__ s_type, const unsigned char *__restrict__ s_flag,
-    const int *__restrict__ n_first, const int *__restrict__ n_count, const double4 *__restrict__ n_geo, int node0,
-    long long shard_first, long long shard_count, double to_slab, int N, const int *__restrict__ t2g_tab,
-    const double *__restrict__ phi, double fac, double *__restrict__ r_pm)
-{
-  extern __shared__ double tile[];   // [NG][G8][G8][G8]
-  const int node = node0 + blockIdx.x;
-  const int first = n_first[node], count = n_count[node];
-  if((long long)first + count <= shard_first || (long long)first >= shard_first + shard_count)
-    return;                                     // no target of this task in the cell (uniform per block)
-  const double4 geo = n_geo[node];
-  const long long NZ = N + 2;
-  int o[3];
-  {
-    const double h = 0.5 * geo.w;
-    o[0] = (int)floor((geo.x - h) * to_slab) - 2;
-    o[1] = (int)floor((geo.y - h) * to_slab) - 2;
-    o[2] = (int)floor((geo.z - h) * to_slab) - 2;
-  }
-  constexpr int T3 = PM_G8 * PM_G8 * PM_G8;
-  for(int t = threadIdx.x; t < NG * T3; t += blockDim.x)
-    {
-      const int g = t / T3, r = t - g * T3;
-      const int lx = r / (PM_G8 * PM_G8), ly = (r / PM_G8) % PM_G8, lz = r % PM_G8;
-      tile[t] = phi[(size_t)g * N * N * NZ + ((long long)wrapN(o[0] + lx, N) * N + wrapN(o[1] + ly, N)) * NZ + wrapN(o[2] + lz, N)];
-    }
-  __syncthreads();
-  for(int k = threadIdx.x; k < count; k += blockDim.x)
-    {
-      const long long i = (long long)first + k;
-      if(i < shard_first || i >= shard_first + shard_count)
-        continue;
-      if(s_flag[i] & 2)
-        {
-          r_pm[3 * i + 0] = r_pm[3 * i + 1] = r_pm[3 * i + 2] = 0.0;
-          continue;
-        }
-      const int g = t2g_tab[s_type[i]];
-      const double *grid = phi + (size_t)g * N * N * NZ;
-      const double *tg = tile + (size_t)g * T3;
-      const double4 p = s_pm[i];
-      double dx, dy, dz;
-      const int sx = cell_of(p.x, to_slab, N, &dx), sy = cell_of(p.y, to_slab, N, &dy), sz = cell_of(p.z, to_slab, N, &dz);
-      const int lx = sx - o[0], ly = sy - o[1], lz = sz - o[2];
-      const bool inside = lx >= 2 && ly >= 2 && lz >= 2 && lx < PM_G8 - 3 && ly < PM_G8 - 3 && lz < PM_G8 - 3;
-      const double wx[2] = {1.0 - dx, dx}, wy[2] = {1.0 - dy, dy}, wz[2] = {1.0 - dz, dz};
-      double acc[3] = {0, 0, 0};
-      const int ox[8] = {0, 0, 0, 0, 1, 1, 1, 1}, oy[8] = {0, 1, 0, 1, 0, 1, 0, 1}, oz[8] = {0, 0, 1, 1, 0, 0, 1, 1};
-      auto at = [&](int x, int y, int z) -> double {
-        if(inside)
-          return tg[(x * PM_G8 + y) * PM_G8 + z];
-        return grid[((long long)wrapN(o[0] + x, N) * N + wrapN(o[1] + y, N)) * NZ + wrapN(o[2] + z, N)];
-      };
-      for(int c = 0; c < 8; c++)
-        {
-          const int x = lx + ox[c], y = ly + oy[c], z = lz + oz[c];
-          const double w = wx[ox[c]] * wy[oy[c]] * wz[oz[c]];
-          const double fxv = fac * ((4.0 / 3) * (at(x - 1, y, z) - at(x + 1, y, z)) - (1.0 / 6) * (at(x - 2, y, z) - at(x + 2, y, z)));
-          const double fyv = fac * ((4.0 / 3) * (at(x, y - 1, z) - at(x, y + 1, z)) - (1.0 / 6) * (at(x, y - 2, z) - at(x, y + 2, z)));
-          const double fzv = fac * ((4.0 / 3) * (at(x, y, z - 1) - at(x, y, z + 1)) - (1.0 / 6) * (at(x, y, z - 2) - at(x, y, z + 2)));
-          acc[0] += fxv * w;
-          acc[1] += fyv * w;
-          acc[2] += fzv * w;
-        }
-      r_pm[3 * i + 0] = acc[0];
-      r_pm[3 * i + 1] = acc[1];
-      r_pm[3 * i + 2] = acc[2];
-    }
-}
-
-__global__ void k_gradient_gather_loose(const double4 *__restrict__ s_pm, const unsigned char *__restrict__ s_type,
-                                        const unsigned char *__restrict__ s_flag,
-                                        const int *__restrict__ n_child, int nnodes_above, long long shard_first,
-                                        long long shard_count, double to_slab, int N, const int *__restrict__ t2g_tab,
-                                        const double *__restrict__ phi, double fac, double *__restrict__ r_pm)
-{
-  long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-  if(t >= 8ll * nnodes_above)
-    return;
-  const int c = n_child[t];
-  if(c > -2)
-    return;
-  const long long i = -2 - c;
-  if(i < shard_first || i >= shard_first + shard_count)
-    return;
-  if(s_flag[i] & 2)
-    {
-      r_pm[3 * i + 0] = r_pm[3 * i + 1] = r_pm[3 * i + 2] = 0.0;
-      return;
-    }
-  double4 p = s_pm[i];
-  int g = t2g_tab[s_type[i]];
-  const long long NZ = N + 2;
-  const double *grid = phi + (size_t)g * N * N * NZ;
-  double dx, dy, dz;
-  int sx = cell_of(p.x, to_slab, N, &dx), sy = cell_of(p.y, to_slab, N, &dy), sz = cell_of(p.z, to_slab, N, &dz);
-  double wx[2] = {1.0 - dx, dx}, wy[2] = {1.0 - dy, dy}, wz[2] = {1.0 - dz, dz};
-  double acc[3] = {0, 0, 0};
-  auto at = [&](int x, int y, int z) { return grid[((long long)wrapN(x, N) * N + wrapN(y, N)) * NZ + wrapN(z, N)]; };
-  const int ox[8] = {0, 0, 0, 0, 1, 1, 1, 1}, oy[8] = {0, 1, 0, 1, 0, 1, 0, 1}, oz[8] = {0, 0, 1, 1, 0, 0, 1, 1};
-  for(int cc = 0; cc < 8; cc++)
-    {
-      int x = sx + ox[cc], y = sy + oy[cc], z = sz + oz[cc];
-      double w = wx[ox[cc]] * wy[oy[cc]] * wz[oz[cc]];
-      double fxv = fac * ((4.0 / 3) * (at(x - 1, y, z) - at(x + 1, y, z)) - (1.0 / 6) * (at(x - 2, y, z) - at(x + 2, y, z)));
-      double fyv = fac * ((4.0 / 3) * (at(x, y - 1, z) - at(x, y + 1, z)) - (1.0 / 6) * (at(x, y - 2, z) - at(x, y + 2, z)));
-      double fzv = fac * ((4.0 / 3) * (at(x, y, z - 1) - at(x, y, z + 1)) - (1.0 / 6) * (at(x, y, z - 2) - at(x, y, z + 2)));
-      acc[0] += fxv * w;
-      acc[1] += fyv * w;
-      acc[2] += fzv * w;
-    }
-  r_pm[3 * i + 0] = acc[0];
-  r_pm[3 * i + 1] = acc[1];
-  r_pm[3 * i + 2] = acc[2];
-}
-
 // the level whose cells are at most 16 mesh cells wide (-1: no such level in this tree -> per-particle kernels)
-static int pm_tile_level(const ngravs_ctx *c, double to_slab, double max_cells = 16.0)
+static int pm_tile_level(const ngravs_ctx *c, double to_slab)
 {
-  if(!c->have_tree || c->tune.pm_notile)
+  if(!c->have_tree)
     return -1;
   // (the tree's root cube is 1.001 x the particle extent, domain.c:909-923: a "16-cell" node of a full box is 16.016 cells wide.
   // The patches have one point of slack for that; the rare particle beyond it takes the direct path.)
   double len = c->dom[6];
   for(int l = 0; l < c->nlevels && l < TREE_BITS; l++, len *= 0.5)
-    if(len * to_slab <= max_cells * 1.002)
+    if(len * to_slab <= 16.0 * 1.002)
       return (c->level_start[l + 1] - c->level_start[l] > 0) ? l : -1;
   return -1;
 }
@@ -511,33 +390,26 @@ void pm_release(ngravs_ctx *c)
 }
 
 // CIC deposit of the working set's own particles into `dst` (zeroed by the caller), a full mesh or a brick (MeshAddr), by tiles:
-// tree cells at most 16 mesh cells wide (18^3 patch per species, one 1024-thread workgroup per CU), or -- tuning "pm_tile8" -- at
-// most 8 (10^3 patches, 256 threads).  Returns 1 if the tree has no such level (caller deposits per particle), 0, or an error.
+// tree cells at most 16 mesh cells wide (18^3 patch per species, one 1024-thread workgroup per CU).  Returns 1 if the tree has no
+// such level (caller deposits per particle), 0, or an error.
 // Expects the type -> species table in d_counters[8..13].
 int pm_deposit_tiles(ngravs_ctx *c, const MeshAddr &ma, double *dst)
 {
   const int N = c->cfg.pmgrid, ng = c->cfg.n_gravs;
   const double to_slab = N / c->cfg.box_size;
   const int bs = 256;
-  const bool t8 = c->tune.pm_tile8 != 0;
-  const int tl = pm_tile_level(c, to_slab, t8 ? 8.0 : 16.0);
+  const int tl = pm_tile_level(c, to_slab);
   if(tl < 0)
     return 1;
   const long long tl0 = c->level_start[tl], tln = c->level_start[tl + 1] - tl0;
-  const int dt = t8 ? 10 : PM_DT;
-  const size_t lds = sizeof(double) * ng * dt * dt * dt;
+  const size_t lds = sizeof(double) * ng * PM_DT * PM_DT * PM_DT;
   auto launch_dep = [&](auto kern) -> int {
     HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3((unsigned)tln), dim3(t8 ? 256 : PM_TILE_THREADS), lds, c->stream, c->s_pm.p, c->s_type.p, c->s_active.p,
+    hipLaunchKernelGGL(kern, dim3((unsigned)tln), dim3(PM_TILE_THREADS), lds, c->stream, c->s_pm.p, c->s_type.p, c->s_active.p,
                        c->n_first.p, c->n_count.p, c->n_geo.p, (int)tl0, to_slab, N, c->d_counters.p + 8, dst, ma);
     return NGRAVS_OK;
   };
-  int rc;
-  if(t8)
-    rc = ng == 1 ? launch_dep(k_cic_deposit_tiled<1, 10>) : (ng == 2 ? launch_dep(k_cic_deposit_tiled<2, 10>) : launch_dep(k_cic_deposit_tiled<3, 10>));
-  else
-    rc = ng == 1 ? launch_dep(k_cic_deposit_tiled<1, PM_DT>)
-                 : (ng == 2 ? launch_dep(k_cic_deposit_tiled<2, PM_DT>) : launch_dep(k_cic_deposit_tiled<3, PM_DT>));
+  const int rc = ng == 1 ? launch_dep(k_cic_deposit_tiled<1>) : (ng == 2 ? launch_dep(k_cic_deposit_tiled<2>) : launch_dep(k_cic_deposit_tiled<3>));
   if(rc)
     return rc;
   if(tl0 > 0)
@@ -603,9 +475,6 @@ int pm_finish(ngravs_ctx *c)
   const size_t real_elems = (size_t)N * N * (N + 2);
   const double L = c->cfg.box_size, to_slab = N / L;
   const int bs = 256;
-  const int tl = pm_tile_level(c, to_slab);
-  const long long tl0 = tl >= 0 ? c->level_start[tl] : 0, tln = tl >= 0 ? c->level_start[tl + 1] - tl0 : 0;
-  (void)tln;
   for(int a = 0; a < ng; a++)
     FFT_TRY(c, hipfftExecD2Z(*(hipfftHandle *)c->fft_fwd, c->pm_rho.p + real_elems * a,
                              (hipfftDoubleComplex *)(c->pm_rho.p + real_elems * a)));
@@ -637,30 +506,7 @@ int pm_finish(ngravs_ctx *c)
   if(c->cfg.world_size > 1)
     HIP_TRY(c, hipMemsetAsync(c->r_pm.p, 0, sizeof(double) * 3 * n, c->stream));
   unsigned nbg = (unsigned)((c->shard_count + bs - 1) / bs);
-  // tiled gather (cells at most 8 mesh cells wide, all species' potential patches in LDS): measured at C4 it LOSES to the
-  // two-pass gather below (13 ms against 3.0 + 3.3 ms: 15^3 patches for 8^3 cells re-read the mesh 6.6 times in short rows),
-  // so it is opt-in for tuning only
-  const int gl = c->tune.pm_tile_gather ? pm_tile_level(c, to_slab, 8.0) : -1;
-  if(gl >= 0)
-    {
-      const long long gl0 = c->level_start[gl], gln = c->level_start[gl + 1] - gl0;
-      const size_t lds = sizeof(double) * ng * PM_G8 * PM_G8 * PM_G8;
-      auto launch_gat = [&](auto kern) -> int {
-        HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(kern, dim3((unsigned)gln), dim3(256), lds, c->stream, c->s_pm.p, c->s_type.p, c->s_active.p, c->n_first.p,
-                           c->n_count.p, c->n_geo.p, (int)gl0, (long long)c->shard_first, (long long)c->shard_count, to_slab, N,
-                           c->d_counters.p + 8, c->pm_phi.p, fac, c->r_pm.p);
-        return NGRAVS_OK;
-      };
-      int rc = ng == 1 ? launch_gat(k_gradient_gather_tiled<1>) : (ng == 2 ? launch_gat(k_gradient_gather_tiled<2>) : launch_gat(k_gradient_gather_tiled<3>));
-      if(rc)
-        return rc;
-      if(gl0 > 0)
-        hipLaunchKernelGGL(k_gradient_gather_loose, dim3((unsigned)((8 * gl0 + bs - 1) / bs)), dim3(bs), 0, c->stream, c->s_pm.p,
-                           c->s_type.p, c->s_active.p, c->n_child.p, (int)gl0, (long long)c->shard_first, (long long)c->shard_count,
-                           to_slab, N, c->d_counters.p + 8, c->pm_phi.p, fac, c->r_pm.p);
-    }
-  else if(nbg > 0 && c->cfg.world_size <= 2 && !c->tune.pm_fused_gather)
+  if(nbg > 0 && c->cfg.world_size <= 2)
     {
       // two passes per target species (see k_force_mesh_march); with many tasks the (replicated) force-mesh pass would cost more
       // than the sharded fused gather below

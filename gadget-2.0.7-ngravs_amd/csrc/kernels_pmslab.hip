@@ -285,48 +285,11 @@ __global__ void k_unpack_planes(const double *__restrict__ recv, const long long
   eb[(size_t)g * bcells + (long long)i * per + r] = recv[off + (g * np + q) * per + r];
 }
 
-// 4-point gradient at the 8 CIC corners + CIC gather on the extended brick (pm_periodic.c:681-763)
-__global__ void k_gradient_gather_brick(const double4 *__restrict__ s_pm, const unsigned char *__restrict__ s_type,
-                                        const unsigned char *__restrict__ s_flag, long long n, double to_slab, WalkParams wp, Brick E,
-                                        const double *__restrict__ eb, double fac, double *__restrict__ r_pm)
-{
-  long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-  if(i >= n)
-    return;
-  if(s_flag[i] & 2)
-    {
-      r_pm[3 * i + 0] = r_pm[3 * i + 1] = r_pm[3 * i + 2] = 0.0;
-      return;
-    }
-  const double4 p = s_pm[i];
-  const double *grid = eb + (size_t)wp.t2g[s_type[i]] * E.cells();
-  double dx, dy, dz;
-  const int sx = cell_of(p.x, to_slab, E.N, &dx), sy = cell_of(p.y, to_slab, E.N, &dy), sz = cell_of(p.z, to_slab, E.N, &dz);
-  const double wx[2] = {1.0 - dx, dx}, wy[2] = {1.0 - dy, dy}, wz[2] = {1.0 - dz, dz};
-  double acc[3] = {0, 0, 0};
-  auto at = [&](int x, int y, int z) { return grid[E.at(x, y, z)]; };
-  // corner order of the reference's gather (x outer, then y/z as written at pm_periodic.c:749-757)
-  const int ox[8] = {0, 0, 0, 0, 1, 1, 1, 1}, oy[8] = {0, 1, 0, 1, 0, 1, 0, 1}, oz[8] = {0, 0, 1, 1, 0, 0, 1, 1};
-  for(int c = 0; c < 8; c++)
-    {
-      const int x = sx + ox[c], y = sy + oy[c], z = sz + oz[c];
-      const double w = wx[ox[c]] * wy[oy[c]] * wz[oz[c]];
-      const double fxv = fac * ((4.0 / 3) * (at(x - 1, y, z) - at(x + 1, y, z)) - (1.0 / 6) * (at(x - 2, y, z) - at(x + 2, y, z)));
-      const double fyv = fac * ((4.0 / 3) * (at(x, y - 1, z) - at(x, y + 1, z)) - (1.0 / 6) * (at(x, y - 2, z) - at(x, y + 2, z)));
-      const double fzv = fac * ((4.0 / 3) * (at(x, y, z - 1) - at(x, y, z + 1)) - (1.0 / 6) * (at(x, y, z - 2) - at(x, y, z + 2)));
-      acc[0] += fxv * w;
-      acc[1] += fyv * w;
-      acc[2] += fzv * w;
-    }
-  r_pm[3 * i + 0] = acc[0];
-  r_pm[3 * i + 1] = acc[1];
-  r_pm[3 * i + 2] = acc[2];
-}
-
-// The same gather in two passes, as on the single mesh (kernels_pm.hip: k_force_mesh_march + k_gather_force): (1) the 4-point force of
-// every cell of the extended brick whose +-2 neighbours it holds, 3 doubles per cell; (2) the CIC gather of 8 cell forces per
-// particle, the two z-neighbour corners as 48 contiguous bytes.  Same expressions and the same corner order as the fused kernel
-// above, hence bitwise the same GravPM; 8 + 12 loads per particle instead of 96, each with three index wraps.
+// 4-point gradient at the 8 CIC corners + CIC gather on the extended brick (pm_periodic.c:681-763), in two passes as on the single
+// mesh (kernels_pm.hip: k_force_mesh_march + k_gather_force): (1) the 4-point force of every cell of the extended brick whose +-2
+// neighbours it holds, 3 doubles per cell; (2) the CIC gather of 8 cell forces per particle, the two z-neighbour corners as 48
+// contiguous bytes.  Same expressions and the same corner order as the one-pass k_gradient_gather, hence bitwise the same GravPM;
+// 8 + 12 loads per particle instead of 96, each with three index wraps.
 __global__ void k_force_mesh_brick(Brick E, int ng, const double *__restrict__ eb, double fac, double *__restrict__ fm)
 {
   const long long cells = E.cells();
@@ -917,10 +880,7 @@ int pmslab_unpack(ngravs_ctx *c, int stage)
       WalkParams wp;
       make_walk_params(c, &wp);
       const long long n = c->n;
-      if(n > 0 && ecells > 0 && c->tune.pm_fused_gather)
-        hipLaunchKernelGGL(k_gradient_gather_brick, GRIDN(n), 0, c->stream, c->s_pm.p, c->s_type.p, c->s_active.p, n, N / L, wp, E, s.ebrick.p,
-                           fac, c->r_pm.p);
-      else if(n > 0 && ecells > 0)
+      if(n > 0 && ecells > 0)
         {
           if(s.fmesh.ensure((size_t)3 * ecells * ng + 1))
             return NGRAVS_ERR_NOMEM;

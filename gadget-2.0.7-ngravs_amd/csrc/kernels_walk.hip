@@ -633,13 +633,6 @@ __global__ __launch_bounds__(256) void k_walk_strict(TreeView tv, const double4 
 #define GW3_LIST_MAX 65536
 #define GW3_STK_MIN 4096      // split walk: pending-node LIFO ints per group (scap; grown likewise)
 #define GW3_STK_MAX 65536
-#ifndef GW_DIRECT
-#define GW_DIRECT 1   // the tree-only force loop in assembly: 1 = ER_DIRECT_ASM (one entry per trip, the next one in flight), 2 = ER_DIRECT2_ASM (two
-                      // interleaved entries per trip)
-#endif
-#ifndef GW2_ES
-#define GW2_ES 1   // measured at C4 (round 2, after the table-bin exp and the expanded-form masks): 1 -> 91.5 ms, 2 -> 96.8 ms
-#endif
 #define GW2_MAXWAVES 16      // evaluation kernel: 4 waves per SIMD (128 VGPRs), 5 KB of LDS each beside the tables
 #define GW3_TBLOCK 256       // traversal kernel: 4 groups per workgroup
 #define GW3_RING 1024        // traversal kernel: LIFO positions mirrored in LDS per wave (a round pushes at most 512)
@@ -658,7 +651,7 @@ __global__ __launch_bounds__(MODE == 1 ? GW3_TBLOCK : (MODE == 2 ? GW2_MAXWAVES 
   // The evaluation kernel culls the unit's lists against the box of its own group, so pool, masks and forces are those of a
   // per-group list; the lists (HBM traffic of the hand-over) and the traversal's work shrink by ~SG/1.7.  MODE 1 runs over
   // units (g_first, g_cnt, the group index are unit indices), MODE 2 over groups.
-  constexpr int ES = GW2_ES;   // entries per force-loop trip (independent instruction streams)
+  constexpr int ES = 1;   // entries per force-loop trip (a constant: with the [ES] arrays written as scalars the kernels compile differently)
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __shared__ int ring_s[MODE == 1 ? (GW3_TBLOCK / 64) * GW3_RING : 1];   // traversal kernel: LDS mirror of each wave's LIFO top
   int *const ring = ring_s + (MODE == 1 ? (threadIdx.x >> 6) * GW3_RING : 0);
@@ -945,9 +938,9 @@ __global__ __launch_bounds__(MODE == 1 ? GW3_TBLOCK : (MODE == 2 ? GW2_MAXWAVES 
       int nint = 0;
       int st_entries = 0, st_nodes = 0, st_batches = 0;   // walk statistics (per group, wave-uniform)
 
-      // ES list entries against this lane's target as ES independent straight-line streams (no branch on the common
-      // path).  Measured: with 4 waves per SIMD the latencies are hidden by the other waves, and ES = 2 beats 4 (fewer
-      // registers -> no spills in the loop, and a trip only rounds the longest lane's hit count up to a multiple of 2).
+      // ES list entries against this lane's target as straight-line code (no branch on the common path).  Measured at C4
+      // (round 2): with 4 waves per SIMD the latencies are hidden by the other waves, and one entry per trip beats two
+      // independent streams, 91.5 against 96.8 ms (the ES > 1 variants were removed; they are in the git history).
       // Inactive slots (a lane whose mask is exhausted) point at the pool's NULL entry (index 127: far away, mass 0), so the
       // common path needs no per-slot masking at all; the rare slot that passed the fp32 pre-test but fails the exact
       // r2 < reach2 test is removed under a wave-level branch.
@@ -1474,7 +1467,7 @@ __global__ __launch_bounds__(MODE == 1 ? GW3_TBLOCK : (MODE == 2 ? GW2_MAXWAVES 
                 unsigned long long m = (((unsigned long long)mhi << 32) | mlo) & lane_pat;
                 nint += direct ? (valid ? nc : 0) : __popcll(m);   // evalN takes the (rare) slots beyond the exact cut off again
                 bool direct_done = false;
-                if constexpr(!PM && !LATT && ES == 1)
+                if constexpr(!PM && !LATT)
                   if(direct && !lanewrap && !(BAMCAP && wp.bam))
                     {
                       // the common tree-only case in assembly (eval_asm.inc ER_DIRECT_ASM: unrolled twice, the next entry in flight,
@@ -1486,19 +1479,11 @@ __global__ __launch_bounds__(MODE == 1 ? GW3_TBLOCK : (MODE == 2 ? GW2_MAXWAVES 
                       const double cNv = valid ? cNg : 0.0, cSv = valid ? cSg : 0.0;
                       const int ncs = __builtin_amdgcn_readfirstlane(nc);
                       const double h2u = wave_uniform(h2max);
-#if GW_DIRECT == 2
-                      asm volatile(ER_DIRECT2_ASM
-                                   : [ax] "+v"(ax), [ay] "+v"(ay), [az] "+v"(az), [ptr] "+v"(ptr)
-                                   : [n] "s"(ncs), [tpx] "v"(tpx), [tpy] "v"(tpy), [tpz] "v"(tpz), [cN] "v"(cNv), [cS] "v"(cSv), [hT] "v"(hT),
-                                     [tyb] "v"(tya), [fst] "s"(fsa), [tiny] "s"(1e-290), [h2max] "s"(h2u)
-                                   : ER_DIRECT2_CLOBBERS);
-#else
                       asm volatile(ER_DIRECT_ASM
                                    : [ax] "+v"(ax), [ay] "+v"(ay), [az] "+v"(az), [ptr] "+v"(ptr)
                                    : [n] "s"(ncs), [tpx] "v"(tpx), [tpy] "v"(tpy), [tpz] "v"(tpz), [cN] "v"(cNv), [cS] "v"(cSv), [hT] "v"(hT),
                                      [tyb] "v"(tya), [fst] "s"(fsa), [tiny] "s"(1e-290), [h2max] "s"(h2u)
                                    : ER_DIRECT_CLOBBERS);
-#endif
                       st_iters += nc;
                       direct_done = true;
                       m = 0;

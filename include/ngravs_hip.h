@@ -232,12 +232,10 @@ int ngravs_get_config(ngravs_ctx *ctx, ngravs_config_t *out);
  *   "walk_spread" S: lanes per target for compacted active sets (1..64, 0 = auto)  "walk_exact_reach" 1: fp64 reach test, no fp32 pre-test
  *   "walk_sg" n: groups of 64 targets per traversal unit = per shared item list (0 = auto: with TreePM 4, or 2 / 1 when the last walk evaluated more than 1.4 / 2 x the pairs per target of a uniform box -- a clustered set; else 1)
  *   "walk_nleaf" k: an opened node with <= k particles hands its particles over instead of its children (0..8, -1 = default 8)
- *   "pm_notile" 1: per-particle CIC deposit     "pm_fused_gather" 1: one-pass gradient+gather    "pm_tile_gather" 1: LDS-tiled gather
- *   "pm_tile8" 1: deposit tiles of 8 instead of 16 mesh cells    "tree_levelwise" 1: level-by-level tree build for single-task trees too
+ *   "tree_levelwise" 1: level-by-level tree build for single-task trees too
  *   "sort_full" 1: Peano order by one radix sort on all key bits (default: top 28 to 42 bits + fix-up of the ties, the same order)
  *   "dd_keep" f: decompositions are kept over several steps (ngravs_host_kept_step): leaves are imported for ALL own particles as
  *       targets, whose cells may have grown by f x the domain's side (0 <= f <= 0.25; default 0: import for this step's active targets)
- *   "moments_octet" 1: node moments with eight lanes per node instead of one thread per node (another summation order; slower)
  * Returns NGRAVS_ERR_ARG for an unknown name or a value out of range. */
 int ngravs_set_tuning(ngravs_ctx *ctx, const char *name, double value);
 /* Plain copies for hosts that do not link HIP themselves (a C/MPI host staging exchange buffers through host memory):
