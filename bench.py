@@ -19,6 +19,10 @@ inputs already resident in HBM.  value = particles * steps / wall time (max over
              top-tree leaves, particle migration, all-reduced top-leaf moments + import of the top-tree cells a task may
              open, x-slab decomposed PM with four plane exchanges; total work is fixed: "scaling": "strong".
              --decomp replicated (tree-only configs): every rank holds all particles, only the walk is sharded.
+
+  --full   : after the timed steps, also the direct-sum accuracy check ("accuracy") and the CPU port on a sample of the
+             workload ("cpu_baseline"), both at N=1; a plain run prints them as null.  --no-accuracy / --no-cpu-baseline
+             drop one of the two from a --full run.
 """
 import argparse
 import json
@@ -291,8 +295,11 @@ def main():
     ap.add_argument("--ngravs", type=int, default=2)
     ap.add_argument("--wiring", default="c4")
     ap.add_argument("--walk", default="group", choices=["group", "strict"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-accuracy", action="store_true", help="skip the direct-sum accuracy check after the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run the direct-sum accuracy check and the CPU baseline (N=1 only); "
+                         "a plain run does neither and prints both as null")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-accuracy", action="store_true", help="--full: skip the direct-sum accuracy check")
     ap.add_argument("--tune", action="append", default=[], metavar="NAME=VALUE",
                     help="ngravs_set_tuning() parameters, e.g. --tune walk_sg=2 (experiments; the default run sets none)")
     ap.add_argument("--decomp", default=None, choices=["replicated", "domain"],
@@ -542,11 +549,11 @@ def main():
                 "top_tree": {"nodes": int(eng.info.n_topnodes), "leaves": int(eng.info.n_topleaves), "counting_rounds": int(eng.info.toptree_rounds)},
                 "decomposition_collectives": int(eng.info.collectives),
                 "decomposition_stage_ms": dict(zip(DD_STAGES, [1e3 * float(v) for v in eng.info.seconds]))}
-        if world == 1 and not args.no_accuracy:
+        if args.full and world == 1 and not args.no_accuracy:
             out["accuracy"] = accuracy_block(pkg, eng, n, dev, periodic=not treeonly)
         else:
             out["accuracy"] = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(pkg, args, cells_per_particle, st.interactions / max(1, st.n_active))
         else:
             out["cpu_baseline"] = None

@@ -9,7 +9,7 @@ O=$R/gpurun_out/${TAG}_ab.txt
 : > $O
 one() {
   cp $2 $L
-  timeout -k 10 200 python3 $R/bench.py --steps 5 --warmup 1 --no-cpu-baseline > /tmp/ab.json 2> /tmp/ab.err || { echo "$1 bench failed" >> $O; tail -3 /tmp/ab.err >> $O; return 1; }
+  timeout -k 10 200 python3 $R/bench.py --steps 5 --warmup 1 --full --no-cpu-baseline > /tmp/ab.json 2> /tmp/ab.err || { echo "$1 bench failed" >> $O; tail -3 /tmp/ab.err >> $O; return 1; }
   python3 - "$1" >> $O <<PY
 import json, sys
 d = json.loads(open("/tmp/ab.json").read().strip().splitlines()[-1])
