@@ -25,7 +25,7 @@ _LIB = None
 # every symbol include/ngravs_hip.h declares (tests/test_abi.py checks the .so exports all of them)
 EXPORTS = [
     "ngravs_abi_version", "ngravs_build_info", "ngravs_config_default", "ngravs_create", "ngravs_create_with_laws", "ngravs_destroy",
-    "ngravs_last_walk_kernel", "ngravs_shortrange_table_with_laws", "ngravs_user_table_eval",
+    "ngravs_last_walk_kernel", "ngravs_last_pm_cus", "ngravs_cu_probe", "ngravs_shortrange_table_with_laws", "ngravs_user_table_eval",
     "ngravs_set_fatal_handler", "ngravs_set_opening", "ngravs_set_walk_mode", "ngravs_set_softening", "ngravs_dd_record_bytes", "ngravs_get_config", "ngravs_set_tuning",
     "ngravs_memcpy", "ngravs_device_alloc", "ngravs_device_free",
     "ngravs_set_particles",
@@ -118,6 +118,8 @@ def lib():
         L.ngravs_dd_set_ids.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.ngravs_create_with_laws.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.ngravs_last_walk_kernel.argtypes = [C.c_void_p]
+        L.ngravs_last_pm_cus.argtypes = [C.c_void_p]
+        L.ngravs_cu_probe.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.ngravs_shortrange_table_with_laws.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.ngravs_user_table_eval.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_int64, C.c_void_p,
                                              C.c_void_p]
@@ -206,6 +208,17 @@ class Engine:
     def last_walk_kernel(self):
         """abi.KERNEL_*: the kernel the last gravity_tree() walked with"""
         return int(lib().ngravs_last_walk_kernel(self._h))
+
+    def last_pm_cus(self):
+        """CUs reserved for PM beside the walk in the last compute_accelerations() (0: one after another)"""
+        return int(lib().ngravs_last_pm_cus(self._h))
+
+    def cu_probe(self, which, nblocks=2048):
+        """ids (XCC << 8 | CU/SH/SE bits of HW_ID) of the CUs nblocks workgroups ran on: which = 0 the context's stream,
+        1 the PM stream, 2 the walk stream of the overlapped step"""
+        out = np.zeros(nblocks, dtype=np.int32)
+        self._check(lib().ngravs_cu_probe(self._h, which, nblocks, out.ctypes.data), "ngravs_cu_probe")
+        return out
 
     def close(self):
         if self._h:

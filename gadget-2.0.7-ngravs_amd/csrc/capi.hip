@@ -301,7 +301,8 @@ extern "C" int ngravs_create_with_laws(const ngravs_config_t *cfg, const ngravs_
   memset(&c->stats, 0, sizeof(c->stats));
   if(hipSetDevice(cfg->device) != hipSuccess || hipStreamCreate(&c->stream) != hipSuccess ||
      hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess ||
-     hipEventCreate(&c->evk0) != hipSuccess || hipEventCreate(&c->evk1) != hipSuccess)
+     hipEventCreate(&c->evk0) != hipSuccess || hipEventCreate(&c->evk1) != hipSuccess || hipEventCreate(&c->ev_fork) != hipSuccess ||
+     hipEventCreate(&c->ev_pm0) != hipSuccess || hipEventCreate(&c->ev_pm1) != hipSuccess || hipEventCreate(&c->ev_walk) != hipSuccess)
     {
       delete c;
       return NGRAVS_ERR_NO_DEVICE;
@@ -394,6 +395,18 @@ extern "C" void ngravs_destroy(ngravs_ctx *c)
   (void)hipEventDestroy(c->evk1);
   for(hipEvent_t e : c->ev_batch)
     (void)hipEventDestroy(e);
+  (void)hipEventDestroy(c->ev_fork);
+  (void)hipEventDestroy(c->ev_pm0);
+  (void)hipEventDestroy(c->ev_pm1);
+  (void)hipEventDestroy(c->ev_walk);
+  if(c->pm_stream)
+    {
+      (void)hipStreamSynchronize(c->pm_stream);
+      (void)hipStreamSynchronize(c->walk_stream);
+      (void)hipStreamDestroy(c->pm_stream);
+      (void)hipStreamDestroy(c->walk_stream);
+    }
+  c->probe_out.release();
   (void)hipStreamDestroy(c->stream);
   delete c;
 }
@@ -493,6 +506,8 @@ extern "C" int ngravs_set_tuning(ngravs_ctx *c, const char *name, double v)
     t.tree_levelwise = iv != 0;
   else if(k == "dd_keep" && v >= 0 && v <= 0.25)
     t.dd_keep = v;
+  else if(k == "pm_cus" && (iv == -1 || (iv >= 0 && iv <= 32 && iv % 8 == 0)))   // multiples of 8: the same share of every XCD
+    t.pm_cus = (int)iv;
   else
     {
       ngravs_report(c, NGRAVS_ERR_ARG, "ngravs_set_tuning: unknown name or value out of range: " + k);
@@ -585,6 +600,7 @@ static int set_particles_impl(ngravs_ctx *c, const ngravs_particles_t *p, bool k
       c->sort_low = 35;
       c->all_active = true;
       c->walk_ia_ratio = 0;   // (a new particle set: the walk's unit is chosen afresh)
+      c->pm_solo_steps = 0, c->pm_auto_cus = -1;   // ... and so are the CUs reserved for PM
       c->walk_unit_state = 4;
       c->have_particles = true;
       c->have_order = c->have_tree = c->have_pm = c->have_acc = false;
@@ -712,6 +728,7 @@ static int set_particles_impl(ngravs_ctx *c, const ngravs_particles_t *p, bool k
     hipLaunchKernelGGL(k_fill_u8, GRID1(n), 0, c->stream, c->in_active.p, (long long)n, (unsigned char)1);
   HIP_TRY(c, hipGetLastError());
   c->walk_ia_ratio = 0;   // (a new particle set: the walk's unit is chosen afresh)
+  c->pm_solo_steps = 0, c->pm_auto_cus = -1;   // ... and so are the CUs reserved for PM
   c->walk_unit_state = 4;
   c->have_particles = true;
   if(keep_tree)
@@ -933,7 +950,72 @@ static int ensure_table(ngravs_ctx *c)
   return NGRAVS_OK;
 }
 
-extern "C" int ngravs_gravity_tree(ngravs_ctx *c)
+// PM beside the walk: whole CUs are split between two masked streams.  R = 8 m reserved CUs (m = 1..4) are m CUs of every XCD: mask
+// bits 33 x + 8 j (x = 0..7, j < m) lie on XCD x whether the runtime deals the bits to the 8 XCDs round robin (bit % 8) or in blocks
+// of 32 (bit / 32); tests/test_gpu_overlap.py checks with ngravs_cu_probe where the two streams' workgroups land.
+static bool pm_cu_bit(int R, int b)
+{
+  const int x = b / 32, k = b - 33 * x;
+  return b < 256 && k >= 0 && k % 8 == 0 && k / 8 < R / 8;
+}
+
+// the two masked streams for R reserved CUs (created on first use, recreated when R changes); an error leaves the serial path
+static int masked_streams(ngravs_ctx *c, int R)
+{
+  if(c->pm_stream && c->pm_stream_cus == R)
+    return NGRAVS_OK;
+  if(!c->device_cus)
+    {
+      hipDeviceProp_t prop;
+      HIP_TRY(c, hipGetDeviceProperties(&prop, c->cfg.device));
+      c->device_cus = prop.multiProcessorCount;
+    }
+  if(c->device_cus != 256 || R < 8 || R > 32 || R % 8)   // (the mask layout above is that of 8 XCDs of 32 CUs)
+    return NGRAVS_ERR_ARG;
+  if(c->pm_stream)
+    {
+      HIP_TRY(c, hipStreamSynchronize(c->pm_stream));
+      HIP_TRY(c, hipStreamSynchronize(c->walk_stream));
+      (void)hipStreamDestroy(c->pm_stream);
+      (void)hipStreamDestroy(c->walk_stream);
+      c->pm_stream = c->walk_stream = nullptr;
+      c->pm_stream_cus = 0;
+    }
+  uint32_t mp[8] = {0}, mw[8] = {0};
+  for(int b = 0; b < 256; b++)
+    (pm_cu_bit(R, b) ? mp : mw)[b / 32] |= 1u << (b % 32);
+  hipStream_t sp = nullptr, sw = nullptr;
+  if(hipExtStreamCreateWithCUMask(&sp, 8, mp) != hipSuccess || hipExtStreamCreateWithCUMask(&sw, 8, mw) != hipSuccess)
+    {
+      if(sp)
+        (void)hipStreamDestroy(sp);
+      (void)hipGetLastError();
+      return NGRAVS_ERR_NO_DEVICE;
+    }
+  uint32_t gp[8] = {0}, gw[8] = {0};
+  if(hipExtStreamGetCUMask(sp, 8, gp) != hipSuccess || hipExtStreamGetCUMask(sw, 8, gw) != hipSuccess || memcmp(gp, mp, sizeof mp) ||
+     memcmp(gw, mw, sizeof mw))
+    {
+      (void)hipStreamDestroy(sp);
+      (void)hipStreamDestroy(sw);
+      (void)hipGetLastError();
+      return NGRAVS_ERR_NO_DEVICE;
+    }
+  c->pm_stream = sp;
+  c->walk_stream = sw;
+  c->pm_stream_cus = R;
+  return NGRAVS_OK;
+}
+
+// PM steps that can run PM beside the walk: one task, the group walk of a TreePM run
+static bool overlap_eligible(const ngravs_ctx *c)
+{
+  return c->cfg.pmgrid && c->cfg.periodic && c->cfg.world_size == 1 && !c->top.on && c->cfg.walk_mode == NGRAVS_WALK_GROUP &&
+         c->n > 0 && c->n_local > 0;
+}
+
+// The walk (traversal, evaluation, k_finish).  pm_done: PM was enqueued on pm_stream beside it, and k_finish waits for that event.
+static int gravity_tree_impl(ngravs_ctx *c, hipEvent_t pm_done)
 {
   if(!c || !c->have_order)
     return NGRAVS_ERR_STATE;
@@ -959,8 +1041,23 @@ extern "C" int ngravs_gravity_tree(ngravs_ctx *c)
       return NGRAVS_OK;
     }
   HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
-  if((rc = walk_run(c)))
+  // the walk alone on walk_stream: beside PM, or (stand-alone calls) when the pm_cus knob forces the masked streams
+  const bool masked = (pm_done || (c->tune.pm_cus > 0 && overlap_eligible(c))) && masked_streams(c, pm_done ? c->pm_stream_cus : c->tune.pm_cus) == NGRAVS_OK;
+  if(masked)
+    {
+      HIP_TRY(c, hipStreamWaitEvent(c->walk_stream, c->ev0, 0));
+      {
+        OnStream on(c, c->walk_stream, c->device_cus - c->pm_stream_cus);
+        if((rc = walk_run(c)))
+          return rc;
+      }
+      HIP_TRY(c, hipEventRecord(c->ev_walk, c->walk_stream));
+      HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_walk, 0));
+    }
+  else if((rc = walk_run(c)))
     return rc;
+  if(pm_done)
+    HIP_TRY(c, hipStreamWaitEvent(c->stream, pm_done, 0));
   if((rc = walk_finish(c)))
     return rc;
   HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
@@ -999,6 +1096,22 @@ extern "C" int ngravs_gravity_tree(ngravs_ctx *c)
   return NGRAVS_OK;
 }
 
+extern "C" int ngravs_gravity_tree(ngravs_ctx *c) { return gravity_tree_impl(c, nullptr); }
+
+// PM on pm_stream, after what c->stream holds so far; the span is timed by ev_pm0 / ev_pm1
+static int pm_on_masked_stream(ngravs_ctx *c)
+{
+  HIP_TRY(c, hipEventRecord(c->ev_fork, c->stream));
+  HIP_TRY(c, hipStreamWaitEvent(c->pm_stream, c->ev_fork, 0));
+  OnStream on(c, c->pm_stream, c->pm_stream_cus);
+  HIP_TRY(c, hipEventRecord(c->ev_pm0, c->stream));
+  int rc = pm_run(c);
+  if(rc)
+    return rc;
+  HIP_TRY(c, hipEventRecord(c->ev_pm1, c->stream));
+  return NGRAVS_OK;
+}
+
 extern "C" int ngravs_pmforce_periodic(ngravs_ctx *c)
 {
   if(!c || !c->have_particles)
@@ -1015,12 +1128,57 @@ extern "C" int ngravs_pmforce_periodic(ngravs_ctx *c)
     }
   else if(c->tree_stale && (rc = ngravs_force_update_tree(c)))
     return rc;
+  if(c->tune.pm_cus > 0 && overlap_eligible(c) && masked_streams(c, c->tune.pm_cus) == NGRAVS_OK)
+    {
+      // the pm_cus knob: PM alone on its reserved CUs (how the two halves of the overlapped step are timed one at a time)
+      if((rc = pm_on_masked_stream(c)))
+        return rc;
+      float ms = 0;
+      HIP_TRY(c, hipEventSynchronize(c->ev_pm1));
+      (void)hipEventElapsedTime(&ms, c->ev_pm0, c->ev_pm1);
+      HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_pm1, 0));
+      c->stats.t_pm = ms * 1e-3;
+      return NGRAVS_OK;
+    }
   HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
   if((rc = pm_run(c)))
     return rc;
   HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
   c->stats.t_pm = ev_ms(c) * 1e-3;
   return NGRAVS_OK;
+}
+
+// Reserved CUs for PM beside the walk in this step (0: one after another), from the PM and walk spans of the second serial PM step
+// of the particle set (the first is often a different walk: the reference's first force computation opens by the angle alone): the smallest R whose PM, PM_CU_SCALE x its whole-device span, ends inside the walk on the other 256 - R CUs
+// with PM_FIT_MARGIN to spare, if the overlapped step is predicted to be shorter than the serial one (the walk, slower on fewer CUs,
+// also loses PM_SHARE_COST beside PM's traffic).  A step whose PM ended after the walk moves R one notch up (to serial after 32);
+// R never comes down for the same particle set, so that the streams are not recreated from step to step.
+// Measured at C4 (2^26 particles, N_GRAVS = 2, PMGRID = 512): PM alone took 17.4 ms on 256 CUs and 309.5 / 158.2 /
+// 107.4 / 82.6 ms on 8 / 16 / 24 / 32; the walk 78.8 ms on 256 and 89.8 ms on 224 CUs alone, 93.0 ms beside PM.
+static const double PM_CU_SCALE[4] = {17.75, 9.07, 6.16, 4.74};
+static const double PM_FIT_MARGIN = 1.05, PM_SHARE_COST = 1.04;
+static int choose_pm_cus(ngravs_ctx *c)
+{
+  if(!overlap_eligible(c))
+    return 0;
+  if(c->tune.pm_cus >= 0)
+    return c->tune.pm_cus;
+  if(c->pm_auto_cus >= 0)
+    return c->pm_auto_cus;
+  if(c->pm_solo_steps < 2 || c->pm_solo_ms <= 0 || c->walk_solo_ms <= 0)
+    return 0;   // (this step measures them)
+  c->pm_auto_cus = 0;
+  for(int m = 1; m <= 4; m++)
+    {
+      const double walk = c->walk_solo_ms * 256.0 / (256 - 8 * m);
+      if(c->pm_solo_ms * PM_CU_SCALE[m - 1] * PM_FIT_MARGIN < walk)
+        {
+          if(walk * PM_SHARE_COST < 0.99 * (c->pm_solo_ms + c->walk_solo_ms))
+            c->pm_auto_cus = 8 * m;
+          break;
+        }
+    }
+  return c->pm_auto_cus;
 }
 
 extern "C" int ngravs_compute_accelerations(ngravs_ctx *c, int pm_step)
@@ -1030,9 +1188,40 @@ extern "C" int ngravs_compute_accelerations(ngravs_ctx *c, int pm_step)
   int rc;
   if((rc = domain_decomposition_impl(c, !(pm_step && c->cfg.pmgrid))))
     return rc;
-  if(pm_step && c->cfg.pmgrid && (rc = ngravs_pmforce_periodic(c)))   // accel.c:34-42
+  c->last_pm_cus = 0;
+  if(!(pm_step && c->cfg.pmgrid))
+    return ngravs_gravity_tree(c);                                      // accel.c:46
+  const int R = choose_pm_cus(c);
+  if(R > 0 && masked_streams(c, R) == NGRAVS_OK)
+    {
+      // PM (accel.c:34-42) does not feed the walk: the tree first, then PM on its reserved CUs beside the walk on the others;
+      // only k_finish, which adds GravPM, waits for both
+      int64_t nn = ngravs_force_treebuild(c);
+      if(nn < 0)
+        return (int)nn;
+      if((rc = pm_on_masked_stream(c)))
+        return rc;
+      if((rc = gravity_tree_impl(c, c->ev_pm1)))
+        return rc;
+      float ms = 0;
+      (void)hipEventElapsedTime(&ms, c->ev_pm0, c->ev_pm1);   // (complete: k_finish waited for it)
+      c->stats.t_pm = ms * 1e-3;
+      c->last_pm_cus = R;
+      if(c->tune.pm_cus < 0 && ms > c->stats.walk_kernel_ms)   // PM did not fit beside the walk: more CUs next time
+        c->pm_auto_cus = R < 32 ? R + 8 : 0;
+      return NGRAVS_OK;
+    }
+  if((rc = ngravs_pmforce_periodic(c)))   // accel.c:34-42
     return rc;
-  return ngravs_gravity_tree(c);                                        // accel.c:46
+  if((rc = ngravs_gravity_tree(c)))       // accel.c:46
+    return rc;
+  if(overlap_eligible(c) && c->tune.pm_cus < 0 && c->pm_auto_cus < 0)
+    {
+      c->pm_solo_ms = c->stats.t_pm * 1e3;
+      c->walk_solo_ms = c->stats.walk_kernel_ms;
+      c->pm_solo_steps++;
+    }
+  return NGRAVS_OK;
 }
 
 // ---- results ----------------------------------------------------------------------------------------
@@ -1281,6 +1470,44 @@ extern "C" int ngravs_get_shard(ngravs_ctx *c, int64_t *first, int64_t *count)
 
 extern "C" const char *ngravs_last_error(ngravs_ctx *c) { return c ? c->last_error.c_str() : g_create_error.c_str(); }
 extern "C" int ngravs_last_walk_kernel(ngravs_ctx *c) { return c ? c->last_walk_kernel : NGRAVS_ERR_ARG; }
+extern "C" int ngravs_last_pm_cus(ngravs_ctx *c) { return c ? c->last_pm_cus : NGRAVS_ERR_ARG; }
+
+// ngravs_cu_probe: where the workgroups launched on a stream run.  Each workgroup takes a whole CU (its LDS) for about 20 us and
+// records XCC_ID << 8 | bits 8-15 of HW_ID (CU, SH and SE of the CU); hardware registers are only read.
+#define CU_PROBE_LDS (96 * 1024)
+__global__ void k_cu_probe(int *out, int n)
+{
+  extern __shared__ int probe_lds[];
+  if(threadIdx.x != 0)
+    return;
+  unsigned xcc = 0, hw = 0;
+  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
+  probe_lds[0] = (int)(((xcc & 15u) << 8) | ((hw >> 8) & 0xffu));
+  const unsigned long long t0 = wall_clock64();
+  while(wall_clock64() - t0 < 2000)   // 20 us of the 100 MHz clock
+    __builtin_amdgcn_s_sleep(8);
+  if((int)blockIdx.x < n)
+    out[blockIdx.x] = probe_lds[0];
+}
+
+extern "C" int ngravs_cu_probe(ngravs_ctx *c, int which, int nblocks, int32_t *cu_ids)
+{
+  if(!c || !cu_ids || nblocks < 1 || nblocks > 65536 || which < 0 || which > 2)
+    return NGRAVS_ERR_ARG;
+  if(which > 0 && !c->pm_stream)
+    return NGRAVS_ERR_STATE;
+  (void)hipSetDevice(c->cfg.device);
+  hipStream_t s = which == 0 ? c->stream : (which == 1 ? c->pm_stream : c->walk_stream);
+  if(c->probe_out.ensure((size_t)nblocks))
+    return NGRAVS_ERR_NOMEM;
+  HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(k_cu_probe), hipFuncAttributeMaxDynamicSharedMemorySize, CU_PROBE_LDS));
+  hipLaunchKernelGGL(k_cu_probe, dim3((unsigned)nblocks), dim3(64), CU_PROBE_LDS, s, c->probe_out.p, nblocks);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(cu_ids, c->probe_out.p, sizeof(int) * nblocks, hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipStreamSynchronize(s));
+  return NGRAVS_OK;
+}
 
 // ---- stand-alone pieces -------------------------------------------------------------------------------
 extern "C" int64_t ngravs_peano_hilbert_key(int x, int y, int z, int bits) { return ngravs_ph_key(x, y, z, bits); }

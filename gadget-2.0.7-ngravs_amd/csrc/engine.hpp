@@ -179,6 +179,7 @@ struct Tuning
   double dd_keep = 0;       // > 0: the next decompositions will be KEPT for some steps -- import for ALL own particles (not only the active ones), own boxes grown by dd_keep x the domain's side
   int walk_ring = 1;        // TreePM evaluation through the ring-pool kernel (kernels_eval.hip); 0: k_walk_group2<...,2>
   int walk_ring_k = 0;      // ... with at most this many slots per wave (0: as many as fit, at most 8)
+  int pm_cus = -1;          // PM beside the walk on this many reserved CUs (-1: chosen per step, 0: PM and walk one after another)
 };
 
 // The global top of the tree for multi-task runs (force_exchange_pseudodata / force_treeupdate_pseudos, forcetree.c:766-996):
@@ -339,8 +340,38 @@ struct ngravs_ctx
   bool user_ready = false;
   double user_soft[NGRAVS_NTYPES] = {0, 0, 0, 0, 0, 0};   // the softenings the tables were built for
   int last_walk_kernel = 0;   // NGRAVS_KERNEL_*
+  // PM beside the walk (ngravs_compute_accelerations): two streams masked to disjoint sets of CUs
+  hipStream_t pm_stream = nullptr, walk_stream = nullptr;
+  int pm_stream_cus = 0;      // CUs of pm_stream's mask (0: no masked streams); walk_stream has the device's other CUs
+  int device_cus = 0;         // CUs of the device
+  int stream_cus = 0;         // CUs the launches on c->stream may use (0: the whole device); set by OnStream
+  int last_pm_cus = 0;        // CUs PM ran on beside the walk in the last step (0: one after another)
+  double pm_solo_ms = 0, walk_solo_ms = 0;   // PM and walk spans of the last serial PM step of the particle set ...
+  int pm_solo_steps = 0;      // ... of this many
+  int pm_auto_cus = -1;       // the CUs chosen from them (-1: not yet)
+  hipEvent_t ev_fork = nullptr, ev_pm0 = nullptr, ev_pm1 = nullptr, ev_walk = nullptr;
+  DevBuf<int> probe_out;      // ngravs_cu_probe
   DevBuf<double> user_green;  // PM: user Green's functions G(k2) at the integer k2 (GreenParams::ug); empty without a user greens id
   long long user_green_nk2 = 0;
+};
+
+// Routes the context's launches to stream `s`, whose CU mask leaves them `cus` CUs, until the end of the scope (the kernels
+// enqueue on c->stream, and the persistent ones size their grids by c->stream_cus)
+struct OnStream
+{
+  ngravs_ctx *c;
+  hipStream_t s0;
+  int n0;
+  OnStream(ngravs_ctx *c_, hipStream_t s, int cus) : c(c_), s0(c_->stream), n0(c_->stream_cus)
+  {
+    c->stream = s;
+    c->stream_cus = cus;
+  }
+  ~OnStream()
+  {
+    c->stream = s0;
+    c->stream_cus = n0;
+  }
 };
 
 // ---- kernels_domain.hip

@@ -438,10 +438,11 @@ int pm_deposit(ngravs_ctx *c)
       c->fft_inv = new hipfftHandle;
       FFT_TRY(c, hipfftPlan3d((hipfftHandle *)c->fft_fwd, N, N, N, HIPFFT_D2Z));
       FFT_TRY(c, hipfftPlan3d((hipfftHandle *)c->fft_inv, N, N, N, HIPFFT_Z2D));
-      FFT_TRY(c, hipfftSetStream(*(hipfftHandle *)c->fft_fwd, c->stream));
-      FFT_TRY(c, hipfftSetStream(*(hipfftHandle *)c->fft_inv, c->stream));
       c->pm_plan_n = N;
     }
+  // the stream PM is enqueued on this time (the context's, or the masked stream of the overlapped step: OnStream)
+  FFT_TRY(c, hipfftSetStream(*(hipfftHandle *)c->fft_fwd, c->stream));
+  FFT_TRY(c, hipfftSetStream(*(hipfftHandle *)c->fft_inv, c->stream));
   // type -> species table on the device (6 ints, lives in d_counters[8..13])
   HIP_TRY(c, hipMemcpyAsync(c->d_counters.p + 8, c->cfg.type_to_grav, sizeof(int) * 6, hipMemcpyHostToDevice, c->stream));
   const double L = c->cfg.box_size, to_slab = N / L;

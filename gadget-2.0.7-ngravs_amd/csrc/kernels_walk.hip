@@ -2408,6 +2408,17 @@ static int walk_select_targets(ngravs_ctx *c)
   return NGRAVS_OK;
 }
 
+// CUs the persistent kernels size their grids by: those of the stream they are launched on (OnStream), else the device's
+static int walk_cus(const ngravs_ctx *c)
+{
+  if(c->stream_cus > 0)
+    return c->stream_cus;
+  hipDeviceProp_t prop;
+  if(hipGetDeviceProperties(&prop, c->cfg.device) == hipSuccess && prop.multiProcessorCount > 0)
+    return prop.multiProcessorCount;
+  return 256;
+}
+
 template <int NG, bool PM, bool YUK, bool TAB_LDS, bool LATT, bool USR = false>
 static int launch_group2_t(ngravs_ctx *c, const WalkParams &wp, int *glist = nullptr, int nlist = 0)
 {
@@ -2420,10 +2431,7 @@ static int launch_group2_t(ngravs_ctx *c, const WalkParams &wp, int *glist = nul
       S = want > S0 ? want : S0;
     }
   const int G = WAVE / S;
-  int ncu = 256;
-  hipDeviceProp_t prop;
-  if(hipGetDeviceProperties(&prop, c->cfg.device) == hipSuccess && prop.multiProcessorCount > 0)
-    ncu = prop.multiProcessorCount;
+  const int ncu = walk_cus(c);
   const size_t fixed = ((PM && TAB_LDS) ? sizeof(double) * (wp.ntab_lds + wp.exp_tab) * NTAB : 0) + 40 * sizeof(double);
   // one persistent workgroup per CU with as many waves as fit beside the tables (or several smaller ones)
   int waves = (int)((160 * 1024 - fixed) / GW2_WAVE_LDS);
@@ -2458,10 +2466,7 @@ static int launch_group2_t(ngravs_ctx *c, const WalkParams &wp, int *glist = nul
 // evaluation kernel (MODE 2) consumes them.  Same results as the fused kernel (same lists, same order).
 template <int NG, bool PM, bool YUK, bool TAB_LDS, bool LATT, bool USR = false> static int launch_group3_t(ngravs_ctx *c, const WalkParams &wp)
 {
-  int ncu = 256;
-  hipDeviceProp_t prop;
-  if(hipGetDeviceProperties(&prop, c->cfg.device) == hipSuccess && prop.multiProcessorCount > 0)
-    ncu = prop.multiProcessorCount;
+  const int ncu = walk_cus(c);
   const size_t fixed = ((PM && TAB_LDS) ? sizeof(double) * (wp.ntab_lds + wp.exp_tab) * NTAB : 0) + 40 * sizeof(double);
   int waves = (int)((160 * 1024 - fixed) / GW2_WAVE_LDS);
   if(waves > GW2_MAXWAVES)

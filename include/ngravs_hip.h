@@ -213,6 +213,12 @@ int ngravs_create(const ngravs_config_t *cfg, ngravs_ctx **out);
 int ngravs_create_with_laws(const ngravs_config_t *cfg, const ngravs_user_fn_t *fns, int nfns, ngravs_ctx **out);
 /* NGRAVS_KERNEL_* of the last walk of the context (0 before the first) */
 int ngravs_last_walk_kernel(ngravs_ctx *ctx);
+/* CUs reserved for PM beside the walk in the last ngravs_compute_accelerations (0: PM and walk ran one after another) */
+int ngravs_last_pm_cus(ngravs_ctx *ctx);
+/* Where workgroups launched on a stream of the context run: which = 0 its stream, 1 the PM stream, 2 the walk stream of the
+ * overlapped step (NGRAVS_ERR_STATE before an overlapped step created them).  Writes one id per workgroup, nblocks of them:
+ * XCC << 8 | bits 8-15 of the CU's hardware id. */
+int ngravs_cu_probe(ngravs_ctx *ctx, int which, int nblocks, int32_t *cu_ids);
 void ngravs_destroy(ngravs_ctx *ctx);
 void ngravs_set_fatal_handler(ngravs_ctx *ctx, ngravs_fatal_fn fn);
 /* Change the walk parameters between calls (All.ErrTolTheta latch, gravtree.c:334-335). */
