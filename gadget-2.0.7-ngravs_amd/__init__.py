@@ -26,6 +26,7 @@ _LIB = None
 EXPORTS = [
     "ngravs_abi_version", "ngravs_build_info", "ngravs_config_default", "ngravs_create", "ngravs_create_with_laws", "ngravs_destroy",
     "ngravs_last_walk_kernel", "ngravs_last_pm_cus", "ngravs_cu_probe", "ngravs_shortrange_table_with_laws", "ngravs_user_table_eval",
+    "ngravs_create_with_lattice", "ngravs_user_lattice_table",
     "ngravs_set_fatal_handler", "ngravs_set_opening", "ngravs_set_walk_mode", "ngravs_set_softening", "ngravs_dd_record_bytes", "ngravs_get_config", "ngravs_set_tuning",
     "ngravs_memcpy", "ngravs_device_alloc", "ngravs_device_free",
     "ngravs_set_particles",
@@ -124,6 +125,8 @@ def lib():
         L.ngravs_user_table_eval.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_int64, C.c_void_p,
                                              C.c_void_p]
         L.ngravs_dd_get_ids.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.ngravs_create_with_lattice.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        L.ngravs_user_lattice_table.argtypes = [abi.LATTICE_FN, C.c_double, C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -183,6 +186,18 @@ def user_table_eval(kind, fn, r, r_lo=0.0, r_hi=0.0, h=0.0):
     return out, err.value
 
 
+def user_lattice_table(fn, box_size):
+    """one lattice-correction table as the kernels read it, built on the host (no GPU): fn (abi.LATTICE_FN or a Python callable
+    fn(i, j, k, x, force)) sampled at x = 0.5 (i, j, k) / 64 and divided by box_size^2; shape (3, 65, 65, 65)"""
+    w = abi.lattice_fn(fn)
+    out = np.zeros((3, abi.LAT_EN1, abi.LAT_EN1, abi.LAT_EN1))
+    rc = lib().ngravs_user_lattice_table(w, float(box_size), out.ctypes.data)
+    if rc != 0:
+        msg = lib().ngravs_last_error(None)
+        raise NgravsError("ngravs_user_lattice_table: %d: %s" % (rc, msg.decode() if msg else ""))
+    return out
+
+
 def _ptr(a):
     return a.ctypes.data if a is not None else None
 
@@ -190,14 +205,18 @@ def _ptr(a):
 class Engine:
     """One task's gravity state: the replacement for the reference's globals on this path."""
 
-    def __init__(self, cfg, user_fns=None):
+    def __init__(self, cfg, user_fns=None, user_lattice=None):
         """user_fns: [(abi.USER_ACCEL | USER_SPLINE | USER_GREENS | USER_NORMED, f), ...], f(target, source, r2_or_h_or_k2,
-        r_or_k, N) -> float; entry k is wired as abi.LAW_USER0 + k / abi.SPLINE_USER0 + k.  The callbacks are kept alive with
-        the engine (the library calls them when it (re)builds its tables)."""
+        r_or_k, N) -> float; entry k is wired as abi.LAW_USER0 + k / abi.SPLINE_USER0 + k.  user_lattice: [(target, source,
+        fn), ...], the lattice correction of a pair wired with a user accel id in a periodic run (the reference's
+        LatticeForce[target][source]): fn is an abi.LATTICE_FN (e.g. from the model's shared library) or a Python callable
+        fn(i, j, k, x, force), which is slow here -- 65^3 = 274 625 calls, serialised by the GIL.  The callbacks are kept alive
+        with the engine (the library calls them when it (re)builds its tables)."""
         self.cfg = cfg
         self._h = C.c_void_p()
         self._user_arr, nfns, self._user_keep = abi.user_registry(user_fns)
-        rc = lib().ngravs_create_with_laws(C.byref(cfg), self._user_arr, nfns, C.byref(self._h))
+        self._lat_arr, nlat, self._lat_keep = abi.lattice_registry(user_lattice)
+        rc = lib().ngravs_create_with_lattice(C.byref(cfg), self._user_arr, nfns, self._lat_arr, nlat, C.byref(self._h))
         if rc != 0:
             msg = lib().ngravs_last_error(None)
             self.status = rc

@@ -64,6 +64,35 @@ class UserFn(C.Structure):
     _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("fn", GravityFn)]
 
 
+# the model's lattice corrections (ngravs_create_with_lattice): the reference's latforce, fn(i, j, k, x[3], force[3])
+LATTICE_FN = C.CFUNCTYPE(None, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double))
+LAT_EN1 = 65   # NGRAVS_EN + 1 points per dimension of a lattice table
+
+
+class UserLattice(C.Structure):
+    _fields_ = [("target", C.c_int32), ("source", C.c_int32), ("fn", LATTICE_FN)]
+
+
+def lattice_fn(fn):
+    """a LATTICE_FN instance as it is, a Python callable fn(i, j, k, x, force) wrapped (x and force are ctypes double pointers)"""
+    if fn is None:
+        return LATTICE_FN()   # NULL: the library refuses the entry
+    return fn if isinstance(fn, LATTICE_FN) else LATTICE_FN(fn)
+
+
+def lattice_registry(user_lattice):
+    """[(target, source, fn), ...] -> (ctypes array of UserLattice, its length, the callback wrappers, which must outlive
+    every use of the array)"""
+    user_lattice = list(user_lattice or [])
+    arr = (UserLattice * max(len(user_lattice), 1))()
+    keep = []
+    for k, (t, s, fn) in enumerate(user_lattice):
+        w = lattice_fn(fn)
+        keep.append(w)
+        arr[k].target, arr[k].source, arr[k].fn = int(t), int(s), w
+    return arr, len(user_lattice), keep
+
+
 def user_registry(user_fns):
     """[(kind, callable), ...] -> (ctypes array of UserFn, the callback wrappers, which must outlive every use of the array)"""
     user_fns = list(user_fns or [])

@@ -275,13 +275,19 @@ extern "C" int ngravs_create(const ngravs_config_t *cfg, ngravs_ctx **out) { ret
 
 extern "C" int ngravs_create_with_laws(const ngravs_config_t *cfg, const ngravs_user_fn_t *fns, int nfns, ngravs_ctx **out)
 {
+  return ngravs_create_with_lattice(cfg, fns, nfns, nullptr, 0, out);
+}
+
+extern "C" int ngravs_create_with_lattice(const ngravs_config_t *cfg, const ngravs_user_fn_t *fns, int nfns,
+                                          const ngravs_user_lattice_t *lat, int nlat, ngravs_ctx **out)
+{
   if(!cfg || !out)
     return NGRAVS_ERR_ARG;
   *out = nullptr;
   std::string why;
   int rc = check_config(cfg, why);
   if(rc == NGRAVS_OK)
-    rc = user_check_config(cfg, fns, nfns, why);
+    rc = user_check_config(cfg, fns, nfns, lat, nlat, why);
   if(rc != NGRAVS_OK)
     {
       ngravs_report(nullptr, rc, why);
@@ -298,6 +304,7 @@ extern "C" int ngravs_create_with_laws(const ngravs_config_t *cfg, const ngravs_
   ngravs_ctx *c = new ngravs_ctx;
   c->cfg = *cfg;
   c->user_fns.assign(fns, fns + nfns);
+  c->user_lat.assign(lat, lat + nlat);
   memset(&c->stats, 0, sizeof(c->stats));
   if(hipSetDevice(cfg->device) != hipSuccess || hipStreamCreate(&c->stream) != hipSuccess ||
      hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess ||

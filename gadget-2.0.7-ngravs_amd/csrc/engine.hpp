@@ -335,6 +335,7 @@ struct ngravs_ctx
   std::string last_error;
   // user-defined laws (ngravs_create_with_laws)
   std::vector<ngravs_user_fn_t> user_fns;
+  std::vector<ngravs_user_lattice_t> user_lat;   // the model's lattice corrections (ngravs_create_with_lattice), tabulated in ensure_lattice
   DevBuf<double> user_tab;    // accel tables, then spline tables (UserTabs)
   UserTabs user_ut = {};
   bool user_ready = false;
@@ -421,7 +422,13 @@ static inline bool cfg_has_user(const ngravs_config_t &cfg)
   return false;
 }
 // ---- user_laws.cpp
-int user_check_config(const ngravs_config_t *cfg, const ngravs_user_fn_t *fns, int nfns, std::string &why);
+int user_check_config(const ngravs_config_t *cfg, const ngravs_user_fn_t *fns, int nfns, const ngravs_user_lattice_t *lat, int nlat,
+                      std::string &why);
+// the lattice function of pair (a, b) (nullptr: none); whether every pair wired with a user accel id has one
+ngravs_lattice_fn user_lattice_fn(const ngravs_ctx *c, int a, int b);
+bool user_lattice_complete(const ngravs_ctx *c);
+// samples fn into out[3][65^3] / box^2 on host threads; NGRAVS_ERR_WIRING with the first non-finite point in `why`
+int user_lattice_tabulate(ngravs_lattice_fn fn, double box, double *out, std::string &why);
 void ngravs_report(ngravs_ctx *ctx, int code, const std::string &msg);
 int user_tables_ensure(ngravs_ctx *c, double r_need);
 int user_green_ensure(ngravs_ctx *c);   // PM: the G(k2) tables of the user greens ids   // (re)build the tables if r_need or the softenings are not covered

@@ -637,7 +637,8 @@ __global__ __launch_bounds__(256) void k_walk_strict(TreeView tv, const double4 
 #define GW3_TBLOCK 256       // traversal kernel: 4 groups per workgroup
 #define GW3_RING 1024        // traversal kernel: LIFO positions mirrored in LDS per wave (a round pushes at most 512)
 
-// USR: TreePM wirings with a user-defined law (their own instantiation; the ring kernel never sees them)
+// USR: wirings with a user-defined law in TreePM (PM) and periodic tree-only (LATT) runs (their own instantiations; the ring
+// kernel never sees them)
 template <int NG, bool PM, bool YUK, bool TAB_LDS, bool LATT, int MODE, bool USR = false>
 __global__ __launch_bounds__(MODE == 1 ? GW3_TBLOCK : (MODE == 2 ? GW2_MAXWAVES : GW_MAXWAVES) * 64) void k_walk_group2(
     TreeView tv, const double4 *__restrict__ s_pm, const unsigned char *__restrict__ s_type,
@@ -1083,6 +1084,22 @@ __global__ __launch_bounds__(MODE == 1 ? GW3_TBLOCK : (MODE == 2 ? GW2_MAXWAVES 
                     f = r[k] >= h ? (law_accel_any(lawA, mw[k], r2[k], r[k], wp, 1.0, 1.0) - mw[k] * wp.utor2wpi * trow[tab]) * rinv[k]
                                   : law_spline_any(lawS, mw[k], h, r[k], wp, 1.0, 1.0);
                   }
+                fac[k] = f;
+              }
+          }
+        if constexpr(USR && !PM)
+          {
+#pragma unroll
+            for(int k = 0; k < ES; k++)
+              {
+                // periodic tree-only wirings with a user-defined law (LATT): forcetree.c:1534-1583 through the wired ids, the
+                // nearest image here and the lattice correction below (the NULL entry carries mass 0)
+                const int je = is_act(k) ? jj[k] : 127;
+                const double h = __builtin_fmax(hT, fsT[lty[je]]);
+                double f = 0.0;
+                if(mw[k] != 0.0)
+                  f = r[k] >= h ? law_accel_any(lawA, mw[k], r2[k], r[k], wp, 1.0, 1.0) * rinv[k]
+                                : law_spline_any(lawS, mw[k], h, r[k], wp, 1.0, 1.0);
                 fac[k] = f;
               }
           }
@@ -2324,23 +2341,37 @@ static int ensure_level_table(ngravs_ctx *c, double reach)
   return NGRAVS_OK;
 }
 
-// lattice_init: one Ewald / lattice sum per distinct law, replicated into the [target][source] slots
+// lattice_init: one Ewald / lattice sum per distinct built-in law, replicated into the [target][source] slots; a pair wired with
+// a user accel id gets the model's own function (ngravs_create_with_lattice), sampled on the host once per distinct function
 static int ensure_lattice(ngravs_ctx *c)
 {
   if(c->lat_ready)
     return NGRAVS_OK;
   const int ng = c->cfg.n_gravs;
+  for(int a = 0; a < ng; a++)
+    for(int b = 0; b < ng; b++)
+      if(c->cfg.law_accel[a][b] >= NGRAVS_LAW_USER0 && !user_lattice_fn(c, a, b))
+        {
+          ngravs_report(c, NGRAVS_ERR_WIRING, "law_accel[" + std::to_string(a) + "][" + std::to_string(b) +
+                                                  "] is a user-defined law without a lattice function: the periodic lattice "
+                                                  "correction (forcetree.c:3515-3529) needs the model's own (ngravs_create_with_lattice)");
+          return NGRAVS_ERR_WIRING;
+        }
   if(c->lat.ensure((size_t)ng * ng * LAT_SZ))
     return NGRAVS_ERR_NOMEM;
   const double L2 = c->cfg.box_size * c->cfg.box_size;
   const int npts = LAT_E1 * LAT_E1 * LAT_E1;
+  std::vector<double> h;
   for(int a = 0; a < ng; a++)
     for(int b = 0; b < ng; b++)
       {
         const int law = c->cfg.law_accel[a][b];
+        const bool user = law >= NGRAVS_LAW_USER0;
+        const ngravs_lattice_fn fn = user ? user_lattice_fn(c, a, b) : nullptr;
         int src = -1;
         for(int k = 0; k < a * ng + b; k++)
-          if(c->cfg.law_accel[k / ng][k % ng] == law)
+          if(user ? (c->cfg.law_accel[k / ng][k % ng] >= NGRAVS_LAW_USER0 && user_lattice_fn(c, k / ng, k % ng) == fn)
+                  : c->cfg.law_accel[k / ng][k % ng] == law)
             {
               src = k;
               break;
@@ -2348,6 +2379,18 @@ static int ensure_lattice(ngravs_ctx *c)
         double *dst = c->lat.p + (size_t)(a * ng + b) * LAT_SZ;
         if(src >= 0)
           HIP_TRY(c, hipMemcpyAsync(dst, c->lat.p + (size_t)src * LAT_SZ, sizeof(double) * LAT_SZ, hipMemcpyDeviceToDevice, c->stream));
+        else if(user)
+          {
+            std::string why;
+            h.resize(LAT_SZ);
+            if(int rc = user_lattice_tabulate(fn, c->cfg.box_size, h.data(), why))
+              {
+                ngravs_report(c, rc, "law_accel[" + std::to_string(a) + "][" + std::to_string(b) + "]: " + why);
+                return rc;
+              }
+            HIP_TRY(c, hipMemcpyAsync(dst, h.data(), sizeof(double) * LAT_SZ, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(c, hipStreamSynchronize(c->stream));   // h is reused by the next distinct function
+          }
         else
           hipLaunchKernelGGL(k_lattice_table, dim3((npts + 63) / 64), dim3(64), 0, c->stream, law, c->cfg.yukawa_imass, L2, dst);
       }
@@ -2654,6 +2697,11 @@ static int launch_group(ngravs_ctx *c, const WalkParams &wp, bool allow_split, b
       *used_split = true;
       if(pm)
         return yuk ? launch_group3_t<NG, true, true, TL, false>(c, wp) : launch_group3_t<NG, true, false, TL, false>(c, wp);
+      if(c->cfg.periodic && wp.user)
+        {
+          c->last_walk_kernel = NGRAVS_KERNEL_GROUP_USER;
+          return launch_group3_t<NG, false, false, false, true, true>(c, wp);
+        }
       if(c->cfg.periodic)
         return yuk ? launch_group3_t<NG, false, true, false, true>(c, wp) : launch_group3_t<NG, false, false, false, true>(c, wp);
       if((!yuk || wp.user) && wp.bam)
@@ -2666,6 +2714,11 @@ static int launch_group(ngravs_ctx *c, const WalkParams &wp, bool allow_split, b
   if(pm)
     return yuk ? launch_group2_t<NG, true, true, TL, false>(c, wp, glist, nlist)
                : launch_group2_t<NG, true, false, TL, false>(c, wp, glist, nlist);
+  if(c->cfg.periodic && wp.user)
+    {
+      c->last_walk_kernel = NGRAVS_KERNEL_GROUP_USER;
+      return launch_group2_t<NG, false, false, false, true, true>(c, wp, glist, nlist);
+    }
   if(c->cfg.periodic)
     return yuk ? launch_group2_t<NG, false, true, false, true>(c, wp, glist, nlist)
                : launch_group2_t<NG, false, false, false, true>(c, wp, glist, nlist);
@@ -2682,6 +2735,8 @@ static int launch_group(ngravs_ctx *c, const WalkParams &wp, bool allow_split, b
 // particles of a refit tree may leave it a little; beyond the table's end the last octave's polynomial is used)
 // TreePM: the end of the short-range table, r < NTAB / asmthfac = 6 Asmth (forcetree.c:1962-1967)
 static double user_reach(const ngravs_ctx *c) { return c->cfg.pmgrid ? 1.25 * 6.0 * c->asmth : 1.25 * sqrt(3.0) * c->dom[6]; }
+// periodic tree-only walk and periodic direct sum: the nearest image is at most half a box diagonal away
+static double lattice_reach(const ngravs_ctx *c) { return 1.25 * 0.5 * sqrt(3.0) * c->cfg.box_size; }
 
 int walk_run(ngravs_ctx *c)
 {
@@ -2695,12 +2750,11 @@ int walk_run(ngravs_ctx *c)
       if(rcl)
         return rcl;
     }
-  if(!latt)
-    {
-      int rcu = user_tables_ensure(c, user_reach(c));
-      if(rcu)
-        return rcu;
-    }
+  {
+    int rcu = user_tables_ensure(c, latt ? lattice_reach(c) : user_reach(c));
+    if(rcu)
+      return rcu;
+  }
   WalkParams wp;
   make_walk_params(c, &wp);
   LawIds li;
@@ -2762,17 +2816,17 @@ int walk_run(ngravs_ctx *c)
       {
       case 1:
         pm ? (wp.user ? launch_strict<1, true, false, true>(c, wp, li) : launch_strict<1, true, false>(c, wp, li))
-           : (latt ? launch_strict<1, false, true>(c, wp, li)
+           : (latt ? (wp.user ? launch_strict<1, false, true, true>(c, wp, li) : launch_strict<1, false, true>(c, wp, li))
                    : (wp.user ? launch_strict<1, false, false, true>(c, wp, li) : launch_strict<1, false, false>(c, wp, li)));
         break;
       case 2:
         pm ? (wp.user ? launch_strict<2, true, false, true>(c, wp, li) : launch_strict<2, true, false>(c, wp, li))
-           : (latt ? launch_strict<2, false, true>(c, wp, li)
+           : (latt ? (wp.user ? launch_strict<2, false, true, true>(c, wp, li) : launch_strict<2, false, true>(c, wp, li))
                    : (wp.user ? launch_strict<2, false, false, true>(c, wp, li) : launch_strict<2, false, false>(c, wp, li)));
         break;
       default:
         pm ? (wp.user ? launch_strict<3, true, false, true>(c, wp, li) : launch_strict<3, true, false>(c, wp, li))
-           : (latt ? launch_strict<3, false, true>(c, wp, li)
+           : (latt ? (wp.user ? launch_strict<3, false, true, true>(c, wp, li) : launch_strict<3, false, true>(c, wp, li))
                    : (wp.user ? launch_strict<3, false, false, true>(c, wp, li) : launch_strict<3, false, false>(c, wp, li)));
         break;
       }
@@ -2923,18 +2977,17 @@ int walk_finish(ngravs_ctx *c)
 // direct sum for explicit target records over the OWN particles of this task (distributed gravity_forcetest)
 int direct_run_targets(ngravs_ctx *c, const double4 *d_tpm, const int *d_ttype, int64_t nt, double *d_acc, double r_need)
 {
-  if(c->cfg.periodic && cfg_has_user(c->cfg))
+  if(c->cfg.periodic && !user_lattice_complete(c))
     {
-      ngravs_report(c, NGRAVS_ERR_WIRING, "the periodic direct sum adds the lattice correction of the law (forcetree.c:3515-3529), "
-                                          "which user-defined laws do not have");
+      ngravs_report(c, NGRAVS_ERR_WIRING, "the periodic direct sum adds the lattice correction of the law (forcetree.c:3515-3529): "
+                                          "a pair wired with a user-defined law has no lattice function (ngravs_create_with_lattice)");
       return NGRAVS_ERR_WIRING;
     }
-  if(!c->cfg.periodic)
-    {
-      int rcu = user_tables_ensure(c, fmax(r_need, user_reach(c)));
-      if(rcu)
-        return rcu;
-    }
+  {
+    int rcu = user_tables_ensure(c, c->cfg.periodic ? lattice_reach(c) : fmax(r_need, user_reach(c)));
+    if(rcu)
+      return rcu;
+  }
   WalkParams wp;
   make_walk_params(c, &wp);
   LawIds li;
@@ -2954,18 +3007,17 @@ int direct_run_targets(ngravs_ctx *c, const double4 *d_tpm, const int *d_ttype, 
 
 int direct_run(ngravs_ctx *c, const int *d_idx, int64_t nt, double *d_acc)
 {
-  if(c->cfg.periodic && cfg_has_user(c->cfg))
+  if(c->cfg.periodic && !user_lattice_complete(c))
     {
-      ngravs_report(c, NGRAVS_ERR_WIRING, "the periodic direct sum adds the lattice correction of the law (forcetree.c:3515-3529), "
-                                          "which user-defined laws do not have");
+      ngravs_report(c, NGRAVS_ERR_WIRING, "the periodic direct sum adds the lattice correction of the law (forcetree.c:3515-3529): "
+                                          "a pair wired with a user-defined law has no lattice function (ngravs_create_with_lattice)");
       return NGRAVS_ERR_WIRING;
     }
-  if(!c->cfg.periodic)
-    {
-      int rcu = user_tables_ensure(c, user_reach(c));
-      if(rcu)
-        return rcu;
-    }
+  {
+    int rcu = user_tables_ensure(c, c->cfg.periodic ? lattice_reach(c) : user_reach(c));
+    if(rcu)
+      return rcu;
+  }
   WalkParams wp;
   make_walk_params(c, &wp);
   LawIds li;

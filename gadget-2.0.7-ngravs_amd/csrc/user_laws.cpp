@@ -5,7 +5,9 @@
 // which the kernels evaluate: the r-space force as g(r) = r^2 accel(1, 1, r^2, r, 1) over octaves of r, the softened force per
 // distinct softening length over u = r/h in [0, 1).  Degree 7 at the Chebyshev nodes of every sub-interval; the number of
 // sub-intervals is doubled until the fit agrees with the callback to UL_TOL at check points between the nodes.
+#include <algorithm>
 #include <cmath>
+#include <thread>
 #include <vector>
 #include "engine.hpp"
 
@@ -268,6 +270,91 @@ extern "C" int ngravs_user_table_eval(const ngravs_user_fn_t *fn, double r_lo, d
   return NGRAVS_OK;
 }
 
+// ---- the model's lattice corrections (ngravs_create_with_lattice) ------------------------------------------------------------
+// lattice_init (forcetree.c:3611-3793): LatticeForce[l][m](i, j, k, x, force) at x = 0.5 (i, j, k) / NGRAVS_EN, divided by
+// BoxSize^2; the layout of k_lattice_table, [3][65^3] with point (i, j, k) at (i * 65 + j) * 65 + k
+#define ULAT_EN 64
+#define ULAT_E1 (ULAT_EN + 1)
+#define ULAT_THREADS 16   // the most host threads a tabulation uses (a job's share of the machine, not the machine)
+
+int user_lattice_tabulate(ngravs_lattice_fn fn, double box, double *out, std::string &why)
+{
+  const long long npts = (long long)ULAT_E1 * ULAT_E1 * ULAT_E1;
+  const double L2 = box * box;
+  const unsigned hc = std::thread::hardware_concurrency();
+  const int nth = (int)std::max(1u, std::min((unsigned)ULAT_THREADS, hc));
+  std::vector<long long> bad(nth, -1);   // per thread: the first point whose sample is not finite
+  auto work = [&](int t) {
+    for(long long n = npts * t / nth; n < npts * (t + 1) / nth; n++)
+      {
+        const int i = (int)(n / (ULAT_E1 * ULAT_E1)), j = (int)((n / ULAT_E1) % ULAT_E1), k = (int)(n % ULAT_E1);
+        double x[3] = {0.5 * ((double)i) / ULAT_EN, 0.5 * ((double)j) / ULAT_EN, 0.5 * ((double)k) / ULAT_EN};
+        double f[3] = {0, 0, 0};   // the reference's yukawa_lattice_force returns at the origin without writing it
+        fn(i, j, k, x, f);
+        if(!std::isfinite(f[0]) || !std::isfinite(f[1]) || !std::isfinite(f[2]))
+          {
+            bad[t] = n;
+            return;
+          }
+        for(int c = 0; c < 3; c++)
+          out[c * npts + n] = f[c] / L2;
+      }
+  };
+  std::vector<std::thread> th;
+  for(int t = 1; t < nth; t++)
+    {
+      try
+        {
+          th.emplace_back(work, t);
+        }
+      catch(...)
+        {
+          work(t);   // no thread to be had: this one does the share
+        }
+    }
+  work(0);
+  for(auto &x : th)
+    x.join();
+  for(int t = 0; t < nth; t++)
+    if(bad[t] >= 0)
+      {
+        const long long n = bad[t];
+        why = "lattice function: non-finite force at point (" + std::to_string(n / (ULAT_E1 * ULAT_E1)) + ", " +
+              std::to_string((n / ULAT_E1) % ULAT_E1) + ", " + std::to_string(n % ULAT_E1) + ")";
+        return NGRAVS_ERR_WIRING;
+      }
+  return NGRAVS_OK;
+}
+
+extern "C" int ngravs_user_lattice_table(ngravs_lattice_fn fn, double box_size, double *out)
+{
+  if(!fn || !out || !(box_size > 0))
+    return NGRAVS_ERR_ARG;
+  std::string why;
+  const int rc = user_lattice_tabulate(fn, box_size, out, why);
+  if(rc)
+    ngravs_report(nullptr, rc, why);
+  return rc;
+}
+
+ngravs_lattice_fn user_lattice_fn(const ngravs_ctx *c, int a, int b)
+{
+  for(const ngravs_user_lattice_t &e : c->user_lat)
+    if(e.target == a && e.source == b)
+      return e.fn;
+  return nullptr;
+}
+
+bool user_lattice_complete(const ngravs_ctx *c)
+{
+  const int ng = c->cfg.n_gravs;
+  for(int a = 0; a < ng; a++)
+    for(int b = 0; b < ng; b++)
+      if(c->cfg.law_accel[a][b] >= NGRAVS_LAW_USER0 && !user_lattice_fn(c, a, b))
+        return false;
+  return true;
+}
+
 // ---- the checks of ngravs_create_with_laws ----------------------------------------------------------------------------------
 static bool is_user(int id) { return id >= NGRAVS_LAW_USER0; }
 
@@ -315,13 +402,55 @@ static bool builtin_value(const ngravs_config_t *cfg, int kind, int id, double t
 
 static bool close_to(double a, double b) { return a == b || fabs(a - b) <= 1e-12 * fmax(fabs(a), fabs(b)); }
 
-int user_check_config(const ngravs_config_t *cfg, const ngravs_user_fn_t *fns, int nfns, std::string &why)
+// the lattice entries of ngravs_create_with_lattice
+static int user_check_lattice(const ngravs_config_t *cfg, const ngravs_user_lattice_t *lat, int nlat, std::string &why)
+{
+  if(nlat < 0 || (nlat > 0 && !lat))
+    {
+      why = "lattice entries: a negative count or no array";
+      return NGRAVS_ERR_ARG;
+    }
+  const int ng = cfg->n_gravs;
+  for(int e = 0; e < nlat; e++)
+    {
+      const int a = lat[e].target, b = lat[e].source;
+      const std::string name = "lattice entry " + std::to_string(e) + " [" + std::to_string(a) + "][" + std::to_string(b) + "]";
+      if(a < 0 || a >= ng || b < 0 || b >= ng || !lat[e].fn)
+        {
+          why = name + ": species pair out of range or no function";
+          return NGRAVS_ERR_WIRING;
+        }
+      if(!cfg->periodic)
+        {
+          why = name + ": lattice corrections in a non-periodic configuration";
+          return NGRAVS_ERR_WIRING;
+        }
+      for(int q = 0; q < e; q++)
+        if(lat[q].target == a && lat[q].source == b)
+          {
+            why = name + ": a second entry for this pair (entry " + std::to_string(q) + ")";
+            return NGRAVS_ERR_WIRING;
+          }
+      if(!is_user(cfg->law_accel[a][b]))
+        {
+          why = name + ": law_accel of the pair is the built-in id " + std::to_string(cfg->law_accel[a][b]) +
+                " (its lattice correction is the library's own)";
+          return NGRAVS_ERR_WIRING;
+        }
+    }
+  return NGRAVS_OK;
+}
+
+int user_check_config(const ngravs_config_t *cfg, const ngravs_user_fn_t *fns, int nfns, const ngravs_user_lattice_t *lat, int nlat,
+                      std::string &why)
 {
   if(nfns < 0 || nfns > NGRAVS_MAX_USER_FNS || (nfns > 0 && !fns))
     {
       why = "user-law registry: at most NGRAVS_MAX_USER_FNS entries";
       return NGRAVS_ERR_ARG;
     }
+  if(int rc = user_check_lattice(cfg, lat, nlat, why))
+    return rc;
   for(int k = 0; k < nfns; k++)
     if(!fns[k].fn || fns[k].kind < NGRAVS_USER_ACCEL || fns[k].kind > NGRAVS_USER_NORMED)
       {
@@ -351,11 +480,20 @@ int user_check_config(const ngravs_config_t *cfg, const ngravs_user_fn_t *fns, i
   if(!any)
     return NGRAVS_OK;
   if(cfg->periodic && !cfg->pmgrid)
-    {
-      why = "user-defined laws in a periodic tree-only run: the lattice correction would need the model's own LatticeForce "
-            "tables (out of scope; TreePM and non-periodic tree-only runs take user laws)";
-      return NGRAVS_ERR_WIRING;
-    }
+    for(int i = 0; i < ng; i++)
+      for(int j = 0; j < ng; j++)
+        {
+          bool has = false;
+          for(int e = 0; e < nlat && !has; e++)
+            has = lat[e].target == i && lat[e].source == j;
+          if(is_user(cfg->law_accel[i][j]) && !has)
+            {
+              why = "law_accel[" + std::to_string(i) + "][" + std::to_string(j) +
+                    "] is a user-defined law in a periodic tree-only run: its lattice correction needs the model's own "
+                    "LatticeForce function (ngravs_create_with_lattice)";
+              return NGRAVS_ERR_WIRING;
+            }
+        }
   // Newton's third law, the reference's probe F[i][j](1,1,0.5,3,1) == F[j][i](1,1,0.5,3,1) (ngravs_core.c:367-403)
   for(int kind = 0; kind < 4; kind++)
     for(int i = 0; i < ng; i++)

@@ -207,14 +207,14 @@ class TorchComm:
 
 
 class DistributedEngine(Engine):
-    def __init__(self, cfg, leaf_max=None, group=None, comm=None, user_fns=None):
+    def __init__(self, cfg, leaf_max=None, group=None, comm=None, user_fns=None, user_lattice=None):
         """leaf_max: a top-tree node is split while it holds more particles (None: the reference's TotNumPart / (20 NTask), at
         most NGRAVS_TOPLEAF_MAX).  comm: "rccl" (C, libngravs_rccl.so) | "torch" | None = rccl when the process group's backend
-        is nccl, else torch."""
+        is nccl, else torch.  user_fns, user_lattice: as Engine; every task tabulates its own lattice tables (no collectives)."""
         import torch
         import torch.distributed as dist
         cfg.rank, cfg.world_size = 0, 1          # the library sees its working set (own + imported) as a single task
-        super().__init__(cfg, user_fns=user_fns)
+        super().__init__(cfg, user_fns=user_fns, user_lattice=user_lattice)
         dev = torch.device("cuda", cfg.device)
         if comm is None:
             comm = "rccl" if dist.get_backend(group) == "nccl" else "torch"

@@ -61,6 +61,17 @@ static unsigned char *ActiveFlag = NULL;
 static ngravs_user_fn_t UserFns[NGRAVS_MAX_USER_FNS];
 static int NUserFns = 0;
 
+#ifdef PERIODIC
+/* allvars.h:138-140: the model's lattice corrections, LatticeForce[l][m] next to AccelFxns[l][m].  Declared here weak, with the
+ * reference's exact type (latforce is ngravs_lattice_fn): it agrees with allvars.h's declaration, and the glue still links in
+ * a tree where no unit defines the array (its address is then NULL and no lattice function is handed over).  Every pair whose
+ * accel law became a user registry entry hands over its LatticeForce (ngravs_create_with_lattice); the library samples each
+ * distinct function pointer once, on the host, when a periodic tree-only walk or periodic direct sum first needs it. */
+extern ngravs_lattice_fn LatticeForce[N_GRAVS][N_GRAVS] __attribute__((weak));
+static ngravs_user_lattice_t UserLat[N_GRAVS * N_GRAVS];
+#endif
+static int NUserLat = 0;
+
 static int user_id(gravity f, int kind)
 {
   int k;
@@ -250,8 +261,28 @@ static void ensure_ctx(void)
 #ifdef NGRAVS_GLUE_DEVICE
   cfg.device = NGRAVS_GLUE_DEVICE;	/* rehearsals: several tasks on one GPU */
 #endif
+  NUserLat = 0;
+#ifdef PERIODIC
+  if(&LatticeForce[0][0] != NULL)
+    for(i = 0; i < N_GRAVS; i++)
+      for(j = 0; j < N_GRAVS; j++)
+        if(cfg.law_accel[i][j] >= NGRAVS_LAW_USER0 && LatticeForce[i][j])
+          {
+            UserLat[NUserLat].target = i;
+            UserLat[NUserLat].source = j;
+            UserLat[NUserLat].fn = LatticeForce[i][j];
+            NUserLat++;
+          }
+#endif
   {
-    int rc = NUserFns > 0 ? ngravs_create_with_laws(&cfg, UserFns, NUserFns, &Ctx) : ngravs_create(&cfg, &Ctx);
+    int rc;
+
+#ifdef PERIODIC
+    if(NUserLat > 0)
+      rc = ngravs_create_with_lattice(&cfg, UserFns, NUserFns, UserLat, NUserLat, &Ctx);
+    else
+#endif
+      rc = NUserFns > 0 ? ngravs_create_with_laws(&cfg, UserFns, NUserFns, &Ctx) : ngravs_create(&cfg, &Ctx);
 
     if(rc == NGRAVS_ERR_WIRING && NUserFns > 0)
       {
@@ -572,7 +603,8 @@ void force_update_hmax(void)
 
 #ifdef PERIODIC
 /* proto.h:61 -- forcetree.c:3611: the Ewald / lattice-sum correction tables (begrun.c:48, under PERIODIC && (!PMGRID ||
- * FORCETEST)).  The library tabulates them on the device on first use (k_lattice_table) and needs no file cache. */
+ * FORCETEST)).  The library tabulates them on first use and needs no file cache: on the device (k_lattice_table) for built-in
+ * laws, on the host from the model's LatticeForce for user-defined ones (ensure_ctx). */
 void lattice_init(void)
 {
 }

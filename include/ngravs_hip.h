@@ -188,6 +188,17 @@ typedef struct {
   ngravs_gravity_fn fn;     /* called on the host only, at creation, in ngravs_set_softening and when a table grows; must
                                stay valid as long as the context */
 } ngravs_user_fn_t;
+/* A lattice-correction function of the host: exactly the reference's `latforce` type (allvars.h:138), so that
+ * LatticeForce[l][m] passes without a cast.  Called as fn(i, j, k, x, force) at x = 0.5 (i, j, k) / 64, i, j, k = 0..64, in
+ * units of the box; it writes the force correction of the periodic images into force[3] (force[] is zeroed before every call).
+ * The library divides the samples by BoxSize^2, as lattice_init does (forcetree.c:3611-3793).  The function is called
+ * concurrently from several host threads (at most 16): 65^3 = 274 625 calls per distinct function, once per context, at the
+ * first periodic tree-only walk or periodic direct sum. */
+typedef void (*ngravs_lattice_fn)(int i, int j, int k, double x[3], double force[3]);
+typedef struct {
+  int32_t target, source;   /* the species pair: law_accel[target][source] is a user id */
+  ngravs_lattice_fn fn;     /* must stay valid as long as the context */
+} ngravs_user_lattice_t;
 /* Which kernel the last ngravs_gravity_tree() walked with (ngravs_last_walk_kernel) */
 typedef enum {
   NGRAVS_KERNEL_NONE = 0,
@@ -208,9 +219,18 @@ int ngravs_create(const ngravs_config_t *cfg, ngravs_ctx **out);
  * NGRAVS_ERR_WIRING and a message in ngravs_last_error(NULL): a user id outside the registry or of the wrong kind for its
  * table; a pair that fails the reference's Newton's-third-law probe F[i][j](1,1,0.5,3,1) == F[j][i](...); an accel or spline
  * law that is not linear in the source mass or depends on the target mass or N (a tree node's monopole is a mass sum); a
- * Green's function that depends on its mass arguments; a user id in a periodic tree-only run (its lattice correction would
- * need the model's own tables).  ngravs_last_error(NULL) is per thread. */
+ * Green's function that depends on its mass arguments; a user accel id in a periodic tree-only run (its lattice correction
+ * needs the model's own tables: ngravs_create_with_lattice).  ngravs_last_error(NULL) is per thread. */
 int ngravs_create_with_laws(const ngravs_config_t *cfg, const ngravs_user_fn_t *fns, int nfns, ngravs_ctx **out);
+/* ngravs_create_with_laws with the model's own lattice corrections, one entry per species pair wired with a user accel id
+ * (the reference's LatticeForce[l][m]); ngravs_create_with_laws is this with nlat = 0.  A periodic tree-only run needs an entry
+ * for every user-accel pair; in a TreePM run the entries are optional, and the periodic direct sum (ngravs_direct_sum[_targets])
+ * needs them all.  Refused with NGRAVS_ERR_WIRING, without GPU work: an entry whose pair is out of range or that has no
+ * function; two entries for one pair; an entry on a pair whose law_accel is not a user id; any entry in a non-periodic
+ * configuration.  The tables are sampled lazily (see ngravs_lattice_fn); a non-finite sample fails that call with
+ * NGRAVS_ERR_WIRING and names the pair and the point. */
+int ngravs_create_with_lattice(const ngravs_config_t *cfg, const ngravs_user_fn_t *fns, int nfns, const ngravs_user_lattice_t *lat,
+                               int nlat, ngravs_ctx **out);
 /* NGRAVS_KERNEL_* of the last walk of the context (0 before the first) */
 int ngravs_last_walk_kernel(ngravs_ctx *ctx);
 /* CUs reserved for PM beside the walk in the last ngravs_compute_accelerations (0: PM and walk ran one after another) */
@@ -337,6 +357,10 @@ int ngravs_shortrange_table_with_laws(const ngravs_config_t *cfg, const ngravs_u
  * relative deviation from the callback the fit saw at its check points. */
 int ngravs_user_table_eval(const ngravs_user_fn_t *fn, double r_lo, double r_hi, double h, const double *r, int64_t n, double *out,
                            double *max_err);
+/* One lattice-correction table as the kernels read it, built on the host (no GPU): out[3][65^3] (x, y, z; point (i, j, k) at
+ * (i * 65 + j) * 65 + k) = fn's samples at x = 0.5 (i, j, k) / 64 divided by box_size^2.  NGRAVS_ERR_WIRING (message in
+ * ngravs_last_error(NULL)) if a sample is not finite. */
+int ngravs_user_lattice_table(ngravs_lattice_fn fn, double box_size, double *out);
 /* force_treeevaluate_direct for targets idx[0..nt) against all particles; with PERIODIC the nearest-image
  * sum plus lattice_corr (Ewald / lattice-sum tables, forcetree.c:3515-3529, 3803-3885), i.e. the truth
  * gravity_forcetest() compares the tree / TreePM force against; result xG into acc[3*nt]. */
