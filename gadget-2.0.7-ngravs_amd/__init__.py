@@ -41,6 +41,7 @@ EXPORTS = [
     "ngravs_dd_leaf_sums_kept", "ngravs_dd_pack_leaves_kept", "ngravs_dd_refresh_halo", "ngravs_dd_update_top", "ngravs_dd_get_kept",
     "ngravs_dd_set_ids", "ngravs_dd_get_ids",
     "ngravs_pm_slab_begin", "ngravs_pm_slab_pack", "ngravs_pm_slab_unpack", "ngravs_pm_slab_bytes",
+    "ngravs_sph_density", "ngravs_sph_kernel",
 ]
 # include/ngravs_host.h (plain-C multi-task drivers over a communicator vtable, linked into the same library)
 HOST_EXPORTS = ["ngravs_host_comm_selftest", "ngravs_host_kept_step", "ngravs_host_toptree_borrow", "ngravs_host_domain_decomposition", "ngravs_host_domain_owners", "ngravs_host_domain_halo",
@@ -127,6 +128,8 @@ def lib():
         L.ngravs_dd_get_ids.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.ngravs_create_with_lattice.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
         L.ngravs_user_lattice_table.argtypes = [abi.LATTICE_FN, C.c_double, C.c_void_p]
+        L.ngravs_sph_density.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ngravs_sph_kernel.argtypes = [C.c_double, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -196,6 +199,17 @@ def user_lattice_table(fn, box_size):
         msg = lib().ngravs_last_error(None)
         raise NgravsError("ngravs_user_lattice_table: %d: %s" % (rc, msg.decode() if msg else ""))
     return out
+
+
+def sph_kernel(h, r):
+    """(wk, dwk): the SPH spline and its derivative at radii r for smoothing length h, as the device code evaluates them
+    (density.c:541-550; 0 where r >= h); no GPU needed"""
+    r = np.ascontiguousarray(r, dtype=np.float64)
+    wk, dwk = np.zeros_like(r), np.zeros_like(r)
+    rc = lib().ngravs_sph_kernel(float(h), r.ctypes.data, r.size, wk.ctypes.data, dwk.ctypes.data)
+    if rc != 0:
+        raise NgravsError("ngravs_sph_kernel: %d" % rc)
+    return wk, dwk
 
 
 def _ptr(a):
@@ -404,6 +418,44 @@ class Engine:
         pm = np.zeros((self.n, 3))
         self._check(lib().ngravs_get_accel(self._h, None, 0, pm.ctypes.data, 24, None, 0, None, 0, 0, 0), "ngravs_get_accel")
         return pm
+
+    def sph_density(self, vel, hsml, des_num_ngb, max_num_ngb_deviation, min_gas_hsml=0.0, out=None):
+        """density() of the reference for one task (density.c:56-441): vel = SphP[].VelPred[N,3], hsml = starting guesses [N], one
+        row per particle of the last hand-over (only rows of active type-0 particles are read as targets and written).  numpy
+        arrays, or torch tensors on the device (float64, contiguous: no copy through the host).  Returns a dict: hsml, density,
+        num_ngb, div_vel, curl_vel, dhsml_factor (rows that are no targets: the given hsml, else 0 -- or what `out`, a dict of
+        arrays of the same kind, held), max_rounds, kernel_ms."""
+        on_device = not isinstance(vel, np.ndarray) and hasattr(vel, "data_ptr")
+        res = {}
+        if on_device:
+            import torch
+            assert vel.dtype == torch.float64 and hsml.dtype == torch.float64 and vel.is_contiguous() and hsml.is_contiguous()
+            res["hsml"] = hsml.clone()
+            for k in abi.SPH_OUT_NAMES:
+                res[k] = out[k] if out and k in out else torch.zeros_like(hsml)
+                assert res[k].dtype == torch.float64 and res[k].is_contiguous()
+            addr = lambda a: a.data_ptr()   # noqa: E731
+            torch.cuda.synchronize()   # the library works on a stream of its own: the tensors above must be complete
+        else:
+            vel = np.ascontiguousarray(vel, dtype=np.float64)
+            res["hsml"] = np.array(hsml, dtype=np.float64)
+            for k in abi.SPH_OUT_NAMES:
+                res[k] = out[k] if out and k in out else np.zeros(self.n)
+                assert res[k].dtype == np.float64 and res[k].flags.c_contiguous
+            addr = lambda a: a.ctypes.data   # noqa: E731
+        assert tuple(vel.shape) == (self.n, 3) and all(tuple(a.shape) == (self.n,) for a in res.values())
+        si, so = abi.SphIn(), abi.SphOut()
+        si.vel_pred, si.vel_stride = addr(vel), 24
+        si.hsml, si.hsml_stride = addr(res["hsml"]), 8
+        si.des_num_ngb, si.max_num_ngb_deviation, si.min_gas_hsml = des_num_ngb, max_num_ngb_deviation, min_gas_hsml
+        si.on_device = int(on_device)
+        for k in abi.SPH_OUT_NAMES:
+            setattr(so, k, addr(res[k]))
+            setattr(so, k + "_stride", 8)
+        rounds, ms = C.c_int32(0), C.c_double(0)
+        self._check(lib().ngravs_sph_density(self._h, C.byref(si), C.byref(so), C.byref(rounds), C.byref(ms)), "ngravs_sph_density")
+        res["max_rounds"], res["kernel_ms"] = int(rounds.value), float(ms.value)
+        return res
 
     def stats(self):
         s = Stats()

@@ -117,6 +117,22 @@ class Stats(C.Structure):
     ]
 
 
+class SphIn(C.Structure):
+    _fields_ = [
+        ("vel_pred", C.c_void_p), ("vel_stride", C.c_int64),
+        ("hsml", C.c_void_p), ("hsml_stride", C.c_int64),
+        ("des_num_ngb", C.c_double), ("max_num_ngb_deviation", C.c_double), ("min_gas_hsml", C.c_double),
+        ("on_device", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
+SPH_OUT_NAMES = ("density", "num_ngb", "div_vel", "curl_vel", "dhsml_factor")
+
+
+class SphOut(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in SPH_OUT_NAMES] + [(k + "_stride", C.c_int64) for k in SPH_OUT_NAMES]
+
+
 def make_config(n_gravs=1, periodic=0, pmgrid=0, box_size=0.0, G=1.0, theta=0.5, err_tol_force_acc=0.005,
                 softening=None, type_to_grav=None, wiring="newton", yukawa_imass=60.0, walk_mode=WALK_STRICT,
                 tree_alloc_factor=0.0, device=0, rank=0, world_size=1, group_reach=0.0):

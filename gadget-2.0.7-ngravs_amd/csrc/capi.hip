@@ -396,6 +396,15 @@ extern "C" void ngravs_destroy(ngravs_ctx *c)
   c->pm_orig.release();
   c->out_tmp.release();
   c->out_tmpf.release();
+  c->sph_vel_in.release();
+  c->sph_h_in.release();
+  c->sph_vel.release();
+  c->sph_tlist.release();
+  c->sph_tmp.release();
+  c->sph_res.release();
+  c->sph_row.release();
+  c->sph_rounds.release();
+  c->sph_counters.release();
   (void)hipEventDestroy(c->ev0);
   (void)hipEventDestroy(c->ev1);
   (void)hipEventDestroy(c->evk0);
@@ -515,6 +524,8 @@ extern "C" int ngravs_set_tuning(ngravs_ctx *c, const char *name, double v)
     t.dd_keep = v;
   else if(k == "pm_cus" && (iv == -1 || (iv >= 0 && iv <= 32 && iv % 8 == 0)))   // multiples of 8: the same share of every XCD
     t.pm_cus = (int)iv;
+  else if(k == "sph_verbose")
+    t.sph_verbose = iv != 0;
   else
     {
       ngravs_report(c, NGRAVS_ERR_ARG, "ngravs_set_tuning: unknown name or value out of range: " + k);
@@ -1880,5 +1891,110 @@ extern "C" int ngravs_pm_slab_bytes(ngravs_ctx *c, double bytes[4])
     return NGRAVS_ERR_ARG;
   for(int k = 0; k < 4; k++)
     bytes[k] = c->pms.bytes_sent[k];
+  return NGRAVS_OK;
+}
+
+// ---- SPH density (density.c:56-441 for one task; kernels_sph.hip) ---------------------------------------------------------
+extern "C" int ngravs_sph_density(ngravs_ctx *c, const ngravs_sph_in_t *in, const ngravs_sph_out_t *out, int32_t *max_rounds, double *kernel_ms)
+{
+  if(!c)
+    return NGRAVS_ERR_ARG;
+  auto refuse = [&](int code, const char *why) {
+    ngravs_report(c, code, std::string("ngravs_sph_density: ") + why);
+    return code;
+  };
+  if(!in || !in->hsml || !in->vel_pred)
+    return refuse(NGRAVS_ERR_ARG, "in, in->hsml and in->vel_pred must not be NULL");
+  if(!(in->des_num_ngb > 0) || !(in->max_num_ngb_deviation >= 0) || !(in->min_gas_hsml >= 0))
+    return refuse(NGRAVS_ERR_ARG, "des_num_ngb must be > 0, max_num_ngb_deviation and min_gas_hsml >= 0");
+  if(c->cfg.world_size > 1 || c->top.on || c->n_local != c->n)
+    return refuse(NGRAVS_ERR_STATE, "single task only (the neighbour search does not cross task boundaries yet)");
+  if(!c->have_order || !c->have_tree)
+    return refuse(NGRAVS_ERR_STATE, "needs a built tree of the current particle set");
+  (void)hipSetDevice(c->cfg.device);
+  int rc;
+  if(c->tree_stale && (rc = ngravs_force_update_tree(c)))   // drifted tree: refit first, as ngravs_gravity_tree does
+    return rc;
+  if(max_rounds)
+    *max_rounds = 0;
+  if(kernel_ms)
+    *kernel_ms = 0;
+  const int64_t n = c->n_local;
+  if(n == 0 || c->nnodes <= 0)
+    return NGRAVS_OK;
+  if(c->sph_vel_in.ensure(3 * n) || c->sph_h_in.ensure(n) || c->sph_vel.ensure(3 * n))
+    return refuse(NGRAVS_ERR_NOMEM, "device allocation failed");
+  if((rc = upload_column_f64(c, in->vel_pred, in->vel_stride, 3, n, in->on_device, c->sph_vel_in.p)))
+    return rc;
+  if((rc = upload_column_f64(c, in->hsml, in->hsml_stride, 1, n, in->on_device, c->sph_h_in.p)))
+    return rc;
+  HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
+  hipLaunchKernelGGL(k_permute_f64, GRID1(n), 0, c->stream, c->s_idx.p, (long long)n, 3, c->sph_vel_in.p, c->sph_vel.p);
+  SphStats st;
+  if((rc = sph_density_run(c, in->des_num_ngb, in->max_num_ngb_deviation, in->min_gas_hsml, &st)))
+    return rc;
+  HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
+  if(kernel_ms)
+    *kernel_ms = ev_ms(c);
+  if(c->tune.sph_verbose && st.targets > 0)   // the reference logs every round of its iteration (density.c:409-414); here one line per call
+    printf("ngravs_sph_density: %lld targets, rounds mean %.3f max %lld, %lld candidates tested, %lld neighbours\n", st.targets,
+           (double)st.sum_rounds / (double)st.targets, st.max_rounds, st.candidates, st.neighbours);
+  if(st.bad_hsml)
+    return refuse(NGRAVS_ERR_ARG, "a target's starting hsml is <= 0 or not finite");
+  if(st.stack_ovf)
+    return refuse(NGRAVS_ERR_TREE, "the tree is deeper than the walk's stack");
+  if(st.failed)
+    {
+      ngravs_report(c, 1155, "failed to converge in neighbour iteration in density()");   // density.c:416-421
+      return NGRAVS_ERR_STATE;
+    }
+  if(max_rounds)
+    *max_rounds = (int32_t)st.max_rounds;
+  const long long nt = st.targets;
+  if(nt == 0)
+    return NGRAVS_OK;
+  // only the targets' rows are written
+  double *dst[SPH_NRES] = {in->hsml, nullptr, nullptr, nullptr, nullptr, nullptr};
+  int64_t stride[SPH_NRES] = {in->hsml_stride, 0, 0, 0, 0, 0};
+  if(out)
+    {
+      dst[SPH_DENSITY] = out->density, stride[SPH_DENSITY] = out->density_stride;
+      dst[SPH_NUMNGB] = out->num_ngb, stride[SPH_NUMNGB] = out->num_ngb_stride;
+      dst[SPH_DIVVEL] = out->div_vel, stride[SPH_DIVVEL] = out->div_vel_stride;
+      dst[SPH_CURLVEL] = out->curl_vel, stride[SPH_CURLVEL] = out->curl_vel_stride;
+      dst[SPH_DHSML] = out->dhsml_factor, stride[SPH_DHSML] = out->dhsml_factor_stride;
+    }
+  if(in->on_device)
+    {
+      for(int k = 0; k < SPH_NRES; k++)
+        if(dst[k] && (rc = sph_scatter(c, c->sph_res.p + k * nt, nt, dst[k], stride[k])))
+          return rc;
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+      return NGRAVS_OK;
+    }
+  c->host_stage.resize((sizeof(double) * SPH_NRES + sizeof(int)) * (size_t)nt);
+  double *hres = reinterpret_cast<double *>(c->host_stage.data());
+  int *hrow = reinterpret_cast<int *>(c->host_stage.data() + sizeof(double) * SPH_NRES * (size_t)nt);
+  HIP_TRY(c, hipMemcpyAsync(hres, c->sph_res.p, sizeof(double) * SPH_NRES * nt, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(hrow, c->sph_row.p, sizeof(int) * nt, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  for(int k = 0; k < SPH_NRES; k++)
+    if(dst[k])
+      for(long long t = 0; t < nt; t++)
+        memcpy(reinterpret_cast<unsigned char *>(dst[k]) + hrow[t] * stride[k], &hres[k * nt + t], sizeof(double));
+  return NGRAVS_OK;
+}
+
+extern "C" int ngravs_sph_kernel(double h, const double *r, int64_t n, double *wk, double *dwk)
+{
+  if(!(h > 0) || n < 0 || (n > 0 && (!r || !wk || !dwk)))
+    return NGRAVS_ERR_ARG;
+  const double h2 = h * h, hinv = 1.0 / h, hinv3 = hinv * hinv * hinv, hinv4 = hinv3 * hinv;
+  for(int64_t i = 0; i < n; i++)
+    {
+      wk[i] = dwk[i] = 0;
+      if(r[i] * r[i] < h2)   // the pair test of density.c:531
+        sph_spline(r[i] * hinv, hinv3, hinv4, &wk[i], &dwk[i]);
+    }
   return NGRAVS_OK;
 }

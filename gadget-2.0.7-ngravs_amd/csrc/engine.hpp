@@ -180,6 +180,7 @@ struct Tuning
   int walk_ring = 1;        // TreePM evaluation through the ring-pool kernel (kernels_eval.hip); 0: k_walk_group2<...,2>
   int walk_ring_k = 0;      // ... with at most this many slots per wave (0: as many as fit, at most 8)
   int pm_cus = -1;          // PM beside the walk on this many reserved CUs (-1: chosen per step, 0: PM and walk one after another)
+  int sph_verbose = 0;      // ngravs_sph_density prints its iteration statistics (targets, rounds, candidates, neighbours) to stdout
 };
 
 // The global top of the tree for multi-task runs (force_exchange_pseudodata / force_treeupdate_pseudos, forcetree.c:766-996):
@@ -354,6 +355,14 @@ struct ngravs_ctx
   DevBuf<int> probe_out;      // ngravs_cu_probe
   DevBuf<double> user_green;  // PM: user Green's functions G(k2) at the integer k2 (GreenParams::ug); empty without a user greens id
   long long user_green_nk2 = 0;
+  // SPH density (ngravs_sph_density, kernels_sph.hip): buffers of its own, the walk's state is not touched
+  DevBuf<double> sph_vel_in, sph_h_in;   // the caller's VelPred[3] and Hsml columns (own rows, caller order)
+  DevBuf<double> sph_vel;                // VelPred in Peano order (sources are read through it)
+  DevBuf<int> sph_tlist;                 // active type-0 own rows, Peano order
+  DevBuf<unsigned char> sph_tmp;
+  DevBuf<double> sph_res;                // [SPH_NRES][targets], list order
+  DevBuf<int> sph_row, sph_rounds;       // per target: caller row, rounds taken
+  DevBuf<unsigned long long> sph_counters;
 };
 
 // Routes the context's launches to stream `s`, whose CU mask leaves them `cus` CUs, until the end of the scope (the kernels
@@ -443,6 +452,39 @@ int direct_run_targets(ngravs_ctx *c, const double4 *d_tpm, const int *d_ttype, 
 int eval_ring_slots(const WalkParams &wp, bool yuk, int waves);
 int launch_eval_ring(ngravs_ctx *c, const TreeView &tv, const WalkParams &wp, bool yuk, int nblk, int waves, int K, const int *region,
                      const int *gcount, long long g0, long long nb, int lcap, int scap, int S, const int *tlist, int SG, long long t_count);
+// ---- kernels_sph.hip
+// The SPH spline and its derivative at u = r/h < 1 (density.c:541-550, coefficients allvars.h:109-115), as host and device evaluate it
+#define SPH_KC1 2.546479089470
+#define SPH_KC2 15.278874536822
+#define SPH_KC3 45.836623610466
+#define SPH_KC4 30.557749073644
+#define SPH_KC5 5.092958178941
+#define SPH_KC6 (-15.278874536822)
+#define SPH_NORM_COEFF 4.188790204786
+#define SPH_MAXITER 150   // allvars.h:97
+__host__ __device__ inline void sph_spline(double u, double hinv3, double hinv4, double *wk, double *dwk)
+{
+  if(u < 0.5)
+    {
+      *wk = hinv3 * (SPH_KC1 + SPH_KC2 * (u - 1) * u * u);
+      *dwk = hinv4 * u * (SPH_KC3 * u - SPH_KC4);
+    }
+  else
+    {
+      *wk = hinv3 * SPH_KC5 * (1.0 - u) * (1.0 - u) * (1.0 - u);
+      *dwk = hinv4 * SPH_KC6 * (1.0 - u) * (1.0 - u);
+    }
+}
+enum { SPH_HSML = 0, SPH_DENSITY, SPH_NUMNGB, SPH_DIVVEL, SPH_CURLVEL, SPH_DHSML, SPH_NRES };
+struct SphStats
+{
+  long long targets, bad_hsml, failed, stack_ovf, max_rounds, sum_rounds, candidates, neighbours;
+};
+// compacts the targets into sph_tlist, then iterates every target's smoothing length to acceptance in one launch: reads sph_vel
+// (Peano order) and sph_h_in (caller order), writes sph_res / sph_row / sph_rounds in list order
+int sph_density_run(ngravs_ctx *c, double des_num_ngb, double max_dev, double min_hsml, SphStats *st);
+// list order -> rows of a strided device column
+int sph_scatter(ngravs_ctx *c, const double *src, long long nt, double *dst, long long stride);
 // ---- kernels_pm.hip
 int pm_run(ngravs_ctx *c);
 int pm_deposit(ngravs_ctx *c);

@@ -262,6 +262,7 @@ int ngravs_get_config(ngravs_ctx *ctx, ngravs_config_t *out);
  *   "sort_full" 1: Peano order by one radix sort on all key bits (default: top 28 to 42 bits + fix-up of the ties, the same order)
  *   "dd_keep" f: decompositions are kept over several steps (ngravs_host_kept_step): leaves are imported for ALL own particles as
  *       targets, whose cells may have grown by f x the domain's side (0 <= f <= 0.25; default 0: import for this step's active targets)
+ *   "sph_verbose" 1: the SPH density call prints one line of iteration statistics (targets, rounds, candidates, neighbours) to stdout
  * Returns NGRAVS_ERR_ARG for an unknown name or a value out of range. */
 int ngravs_set_tuning(ngravs_ctx *ctx, const char *name, double value);
 /* Plain copies for hosts that do not link HIP themselves (a C/MPI host staging exchange buffers through host memory):
@@ -488,6 +489,36 @@ int ngravs_pm_slab_pack(ngravs_ctx *ctx, int stage, const int32_t *all_bbox, int
 int ngravs_pm_slab_unpack(ngravs_ctx *ctx, int stage);
 /* payload this task sent to OTHER tasks in each of the four exchanges of the last step, bytes */
 int ngravs_pm_slab_bytes(ngravs_ctx *ctx, double bytes[4]);
+
+/* ---- SPH density: density() (density.c:56-441) for ONE task -----------------------------------------------------------------
+ * Targets are the caller's own rows of type 0 that the last hand-over marked active (density.c:95, :123); sources are all type-0
+ * particles (ngb.c:221), nearest image in periodic runs.  Every target's smoothing length is iterated to acceptance by the
+ * reference's rules (density.c:314-389: NumNgb inside DesNumNgb +- MaxNumNgbDeviation, or above it with Hsml <= 1.01 MinGasHsml,
+ * or a bracket narrower than 1e-3; bisection in h^3, the Newton-like step, the factor 1.26; clamp to MinGasHsml), and Density,
+ * NumNgb, DivVel, CurlVel, DhsmlDensityFactor come out as after its final operations (density.c:296-303; the pressure line is the
+ * host's: the library holds no entropy).  A target that needs more than MAXITER = 150 repeats is the reference's endrun(1155):
+ * the fatal handler is called with 1155 and the call returns NGRAVS_ERR_STATE.
+ * Needs a built tree of the current particle set (NGRAVS_ERR_STATE otherwise); after ngravs_update_particles the tree is refit
+ * first.  The tree, the walk's state and the stored accelerations are not modified.  NGRAVS_ERR_ARG with a message: NULL in /
+ * hsml / vel_pred, des_num_ngb <= 0, a negative deviation or minimum, a target whose hsml is <= 0 or NaN.  NGRAVS_ERR_STATE,
+ * "single task only": world_size > 1 or a multi-task working set.  No type-0 target: success, nothing written, 0 rounds.
+ * Not provided: hydro forces (hydra.c), TWODIMS, LONG_X/Y/Z. */
+typedef struct {
+  const double *vel_pred; int64_t vel_stride;   /* SphP[].VelPred[3] per own row (rows of other types are not read)      */
+  double *hsml;           int64_t hsml_stride;  /* in: starting guess per own row (> 0 for every target), out: result    */
+  double des_num_ngb, max_num_ngb_deviation, min_gas_hsml;   /* All.DesNumNgb, All.MaxNumNgbDeviation, All.MinGasHsml   */
+  int32_t on_device, reserved;
+} ngravs_sph_in_t;
+typedef struct {   /* any pointer may be NULL; strides in bytes; rows = own rows, only targets are written */
+  double *density, *num_ngb, *div_vel, *curl_vel, *dhsml_factor;
+  int64_t density_stride, num_ngb_stride, div_vel_stride, curl_vel_stride, dhsml_factor_stride;
+} ngravs_sph_out_t;
+/* max_rounds, kernel_ms may be NULL: the most evaluations any target took; device time of the call (HIP events) */
+int ngravs_sph_density(ngravs_ctx *ctx, const ngravs_sph_in_t *in, const ngravs_sph_out_t *out, int32_t *max_rounds,
+                       double *kernel_ms);
+/* GPU-free: the spline and its derivative as the device code evaluates them, wk[i], dwk[i] at r[i] for smoothing length h
+ * (0 where r >= h) */
+int ngravs_sph_kernel(double h, const double *r, int64_t n, double *wk, double *dwk);
 
 #ifdef __cplusplus
 }
