@@ -2400,14 +2400,19 @@ static int ensure_lattice(ngravs_ctx *c)
   return NGRAVS_OK;
 }
 
-template <int NG, bool PM, bool LATT, bool USER = false> static void launch_strict(ngravs_ctx *c, const WalkParams &wp, const LawIds &li)
+// the instantiations of k_walk_strict<NG, PM, LATT, USER>: TreePM, periodic tree-only, tree-only; each with and without a user law
+template <int NG> using StrictRowsNG = Table<Row<NG, 1, 0, 0>, Row<NG, 1, 0, 1>, Row<NG, 0, 1, 0>, Row<NG, 0, 1, 1>, Row<NG, 0, 0, 0>, Row<NG, 0, 0, 1>>;
+using StrictRows = decltype(StrictRowsNG<1>{} + StrictRowsNG<2>{} + StrictRowsNG<3>{});
+
+template <int NG, int PM, int LATT, int USER>
+static int launch_strict(Row<NG, PM, LATT, USER>, ngravs_ctx *c, const WalkParams &wp, const LawIds &li)
 {
-  c->last_walk_kernel = USER ? NGRAVS_KERNEL_STRICT_USER : NGRAVS_KERNEL_STRICT;
   long long ngroups = (c->shard_count + WAVE - 1) / WAVE;
   unsigned nb = (unsigned)((ngroups + 3) / 4);
   hipLaunchKernelGGL((k_walk_strict<NG, PM, LATT, USER>), dim3(nb), dim3(256), 0, c->stream, tree_view(c), c->s_pm.p, c->s_type.p,
                      c->s_oldacc.p, c->s_active.p, LATT ? c->lat.p : c->table.p, wp, li, (long long)c->shard_first,
                      (long long)c->shard_count, c->r_acc.p, c->r_nint.p, c->walk_counters.p + 1);
+  return NGRAVS_OK;
 }
 
 // targets of the group walk: all particles of the shard, or the compacted active ones (walk_select_targets)
@@ -2462,8 +2467,26 @@ static int walk_cus(const ngravs_ctx *c)
   return 256;
 }
 
-template <int NG, bool PM, bool YUK, bool TAB_LDS, bool LATT, bool USR = false>
-static int launch_group2_t(ngravs_ctx *c, const WalkParams &wp, int *glist = nullptr, int nlist = 0)
+// LDS of the evaluating kernels (k_walk_group2, MODE 0 and 2): [tables, if staged] [exp table 32, softening per type 8]
+// [per wave: the chunk pool]; as many waves as fit beside the tables, at most what the kernel's registers allow
+struct EvalLds
+{
+  int waves;
+  size_t bytes;
+};
+static EvalLds eval_lds(const WalkParams &wp, bool tables, int max_waves)
+{
+  const size_t fixed = (tables ? sizeof(double) * (wp.ntab_lds + wp.exp_tab) * NTAB : 0) + 40 * sizeof(double);
+  int waves = (int)((160 * 1024 - fixed) / GW2_WAVE_LDS);
+  if(waves > max_waves)
+    waves = max_waves;
+  if(waves < 1)
+    waves = 1;
+  return {waves, fixed + (size_t)waves * GW2_WAVE_LDS};
+}
+
+template <int NG, int PM, int YUK, int TAB_LDS, int LATT, int USR>
+static int launch_group2_t(Row<NG, PM, YUK, TAB_LDS, LATT, USR>, ngravs_ctx *c, const WalkParams &wp, int *glist, int nlist)
 {
   // lanes per target: the walk's own S, or for the leftover pass (glist) enough to give the few scattered groups many waves
   const int S0 = c->walk_spread > 1 ? c->walk_spread : 1, G0 = (WAVE / S0) * (glist ? c->walk_sg : 1);
@@ -2475,17 +2498,12 @@ static int launch_group2_t(ngravs_ctx *c, const WalkParams &wp, int *glist = nul
     }
   const int G = WAVE / S;
   const int ncu = walk_cus(c);
-  const size_t fixed = ((PM && TAB_LDS) ? sizeof(double) * (wp.ntab_lds + wp.exp_tab) * NTAB : 0) + 40 * sizeof(double);
-  // one persistent workgroup per CU with as many waves as fit beside the tables (or several smaller ones)
-  int waves = (int)((160 * 1024 - fixed) / GW2_WAVE_LDS);
-  int per_cu = 1;
-  if(waves > GW_MAXWAVES)
-    waves = GW_MAXWAVES;   // register-limited: 3 waves per SIMD (__launch_bounds__), one workgroup per CU
-  if(waves < 1)
-    waves = 1;
-  size_t lds = fixed + (size_t)waves * GW2_WAVE_LDS;
+  // one persistent workgroup per CU; register-limited: 3 waves per SIMD (__launch_bounds__)
+  const EvalLds l = eval_lds(wp, PM && TAB_LDS, GW_MAXWAVES);
+  const int waves = l.waves;
+  const size_t lds = l.bytes;
   long long ngroups = glist ? (long long)nlist * (G0 / G) : (walk_tcount(c) + G - 1) / G;
-  long long nblk = (long long)ncu * per_cu;
+  long long nblk = ncu;
   if(nblk > (ngroups + waves - 1) / waves)
     nblk = (ngroups + waves - 1) / waves;
   if(nblk < 1)
@@ -2505,48 +2523,44 @@ static int launch_group2_t(ngravs_ctx *c, const WalkParams &wp, int *glist = nul
   return NGRAVS_OK;
 }
 
+// Groups per traversal unit of a TreePM walk of contiguous targets, from the unit the walk is in (st: 4, 2 or 1) and the last walk's
+// pairs per target relative to a uniform box (r = walk_ia_ratio; 0: not known yet).
+// In a CLUSTERED set the last walk says so: it evaluated more pairs per target than a uniform box of the same mean density
+// holds in the cut sphere (every source inside the sphere a particle: the uniform regime).  A smaller unit has a smaller box,
+// accepts more cells as monopoles, and wins back more than its longer lists cost (2^20 particles, 60 % of them in one clump:
+// 1857 / 1393 / 1079 pairs per target and 8.0 / 7.2 / 5.2 ms for units of 4 / 2 / 1 groups)
+// (walk_ia_ratio is normalised to units of four groups; the unit only changes when the ratio leaves a band around the threshold, so
+// that a set near one does not flip from step to step: down at 1.4 / 2.0, up again below 1.2 / 1.7)
+static int walk_unit_next(int st, double r)
+{
+  if(!(r > 0))
+    return st;
+  if(st == 4)
+    return r > 2.0 ? 1 : (r > 1.4 ? 2 : 4);
+  if(st == 2)
+    return r > 2.0 ? 1 : (r < 1.2 ? 4 : 2);
+  return r < 1.2 ? 4 : (r < 1.7 ? 2 : 1);
+}
+
 // split walk: per batch of groups a high-occupancy traversal kernel (MODE 1) writes the item lists, then the persistent
 // evaluation kernel (MODE 2) consumes them.  Same results as the fused kernel (same lists, same order).
-template <int NG, bool PM, bool YUK, bool TAB_LDS, bool LATT, bool USR = false> static int launch_group3_t(ngravs_ctx *c, const WalkParams &wp)
+template <int NG, int PM, int YUK, int TAB_LDS, int LATT, int USR>
+static int launch_group3_t(Row<NG, PM, YUK, TAB_LDS, LATT, USR>, ngravs_ctx *c, const WalkParams &wp)
 {
   const int ncu = walk_cus(c);
-  const size_t fixed = ((PM && TAB_LDS) ? sizeof(double) * (wp.ntab_lds + wp.exp_tab) * NTAB : 0) + 40 * sizeof(double);
-  int waves = (int)((160 * 1024 - fixed) / GW2_WAVE_LDS);
-  if(waves > GW2_MAXWAVES)
-    waves = GW2_MAXWAVES;   // register-limited: 4 waves per SIMD (__launch_bounds__), one workgroup per CU
-  if(c->tune.walk_waves > 0 && c->tune.walk_waves < waves)
-    waves = c->tune.walk_waves;   // tuning: fewer waves per evaluation workgroup
-  if(waves < 1)
-    waves = 1;
-  const size_t lds = fixed + (size_t)waves * GW2_WAVE_LDS;
+  // register-limited: 4 waves per SIMD (__launch_bounds__), one workgroup per CU; tuning: fewer waves per evaluation workgroup
+  const int max_waves = c->tune.walk_waves > 0 && c->tune.walk_waves < GW2_MAXWAVES ? c->tune.walk_waves : GW2_MAXWAVES;
+  const EvalLds l = eval_lds(wp, PM && TAB_LDS, max_waves);
+  int waves = l.waves;
+  const size_t lds = l.bytes;
   const int S = c->walk_spread > 1 ? c->walk_spread : 1, G = WAVE / S;
   const long long ngroups = (walk_tcount(c) + G - 1) / G;
   // groups per traversal unit: 4 for TreePM walks of Peano-contiguous targets (the short-range region of 256 neighbours is
   // 1.7 x that of 64: lists and traversal work per target fall to ~0.4), 1 for tree-only walks (no cut: a wider box opens more
   // of the tree for every target) and for scattered (compacted / spread) targets
   int SG = (PM && (c->walk_ntargets < 0 || c->walk_dense_tlist)) ? 4 : 1;
-  // ... in a CLUSTERED set the last walk says so: it evaluated more pairs per target than a uniform box of the same mean density
-  // holds in the cut sphere (every source inside the sphere a particle: the uniform regime).  A smaller unit has a smaller box,
-  // accepts more cells as monopoles, and wins back more than its longer lists cost (2^20 particles, 60 % of them in one clump:
-  // 1857 / 1393 / 1079 pairs per target and 8.0 / 7.2 / 5.2 ms for units of 4 / 2 / 1 groups)
-  // (walk_ia_ratio is normalised to units of four groups; the unit only changes when the ratio leaves a band around the threshold, so
-  // that a set near one does not flip from step to step: down at 1.4 / 2.0, up again below 1.2 / 1.7)
   if(SG == 4)
-    {
-      const double r = c->walk_ia_ratio;
-      int st = c->walk_unit_state;
-      if(r > 0)
-        {
-          if(st == 4)
-            st = r > 2.0 ? 1 : (r > 1.4 ? 2 : 4);
-          else if(st == 2)
-            st = r > 2.0 ? 1 : (r < 1.2 ? 4 : 2);
-          else
-            st = r < 1.2 ? 4 : (r < 1.7 ? 2 : 1);
-        }
-      c->walk_unit_state = st;
-      SG = st;
-    }
+    SG = c->walk_unit_state = walk_unit_next(c->walk_unit_state, c->walk_ia_ratio);
   if(c->tune.walk_sg >= 1)
     SG = c->tune.walk_sg;
   if(SG != c->walk_sg)
@@ -2606,9 +2620,7 @@ template <int NG, bool PM, bool YUK, bool TAB_LDS, bool LATT, bool USR = false> 
   if constexpr(PM && TAB_LDS && !LATT && !USR)
     if(c->tune.walk_ring)
       {
-        ring_waves = GW2_MAXWAVES;
-        if(c->tune.walk_waves > 0 && c->tune.walk_waves < ring_waves)
-          ring_waves = c->tune.walk_waves;
+        ring_waves = max_waves;
         ringK = eval_ring_slots(wp, YUK, ring_waves);
         if(c->tune.walk_ring_k >= 4 && c->tune.walk_ring_k < ringK)
           ringK = c->tune.walk_ring_k;
@@ -2658,77 +2670,60 @@ template <int NG, bool PM, bool YUK, bool TAB_LDS, bool LATT, bool USR = false> 
   return NGRAVS_OK;
 }
 
-template <int NG>
-static int launch_group(ngravs_ctx *c, const WalkParams &wp, bool allow_split, bool *used_split, int *glist = nullptr, int nlist = 0)
+// One variant of the group walk: what k_walk_group2<NG, PM, YUK, TAB_LDS, LATT, MODE, USR> is instantiated on (every variant in all
+// three modes) and the NGRAVS_KERNEL_* id the walk reports for it.
+struct GroupVariant
 {
-  *used_split = false;
-  if(!glist)
-    c->walk_batches = 0;
-  const bool pm = c->cfg.pmgrid != 0, yuk = has_yukawa(c);
-  // tables in LDS while they leave room for the pools of 16 waves (three 16 KB tables incl. the exp table; the C5 wiring --
-  // Newton on the diagonal, one law off it -- has two distinct ones); otherwise they are read through L1/L2
-  constexpr bool TL = (NG <= 2);
-  c->last_walk_kernel = NGRAVS_KERNEL_GROUP;
-  if(pm && wp.user)
+  bool pm, yuk, tab, latt, usr;
+  int reports;
+};
+// ... chosen here and nowhere else
+static GroupVariant group_variant(const ngravs_ctx *c, const WalkParams &wp, int ng)
+{
+  const bool yuk = has_yukawa(c), usr = wp.user != 0;
+  const int id = usr ? NGRAVS_KERNEL_GROUP_USER : NGRAVS_KERNEL_GROUP;
+  // a wiring with a user-defined law in a TreePM or periodic tree-only run has its own evaluation variant (USR, without the Yukawa
+  // code; never the ring kernel)
+  if(c->cfg.pmgrid)
     {
-      // TreePM wirings with a user-defined law: their own evaluation variant (USR), never the ring kernel
-      c->last_walk_kernel = NGRAVS_KERNEL_GROUP_USER;
-      if(allow_split && !c->tune.walk_fused && !glist)
-        {
-          *used_split = true;
-          return launch_group3_t<NG, true, false, TL, false, true>(c, wp);
-        }
-      return launch_group2_t<NG, true, false, TL, false, true>(c, wp, glist, nlist);
-    }
-  if constexpr(NG == 3)
-    if(pm && wp.ntab_lds + wp.exp_tab <= 3)
-      {
-        if(allow_split && !c->tune.walk_fused && !glist)
-          {
-            *used_split = true;
-            return has_yukawa(c) ? launch_group3_t<NG, true, true, true, false>(c, wp) : launch_group3_t<NG, true, false, true, false>(c, wp);
-          }
-        return has_yukawa(c) ? launch_group2_t<NG, true, true, true, false>(c, wp, glist, nlist)
-                             : launch_group2_t<NG, true, false, true, false>(c, wp, glist, nlist);
-      }
-  const bool v2 = c->tune.walk_fused != 0;   // fused kernel for the whole walk
-  if(allow_split && !v2 && !glist)
-    {
-      *used_split = true;
-      if(pm)
-        return yuk ? launch_group3_t<NG, true, true, TL, false>(c, wp) : launch_group3_t<NG, true, false, TL, false>(c, wp);
-      if(c->cfg.periodic && wp.user)
-        {
-          c->last_walk_kernel = NGRAVS_KERNEL_GROUP_USER;
-          return launch_group3_t<NG, false, false, false, true, true>(c, wp);
-        }
-      if(c->cfg.periodic)
-        return yuk ? launch_group3_t<NG, false, true, false, true>(c, wp) : launch_group3_t<NG, false, false, false, true>(c, wp);
-      if((!yuk || wp.user) && wp.bam)
-        {
-          c->last_walk_kernel = wp.user ? NGRAVS_KERNEL_GROUP_USER : NGRAVS_KERNEL_GROUP;
-          return launch_group3_t<NG, false, false, true, false>(c, wp);   // the variant with the BAM and the user-defined laws
-        }
-      return yuk ? launch_group3_t<NG, false, true, false, false>(c, wp) : launch_group3_t<NG, false, false, false, false>(c, wp);
-    }
-  if(pm)
-    return yuk ? launch_group2_t<NG, true, true, TL, false>(c, wp, glist, nlist)
-               : launch_group2_t<NG, true, false, TL, false>(c, wp, glist, nlist);
-  if(c->cfg.periodic && wp.user)
-    {
-      c->last_walk_kernel = NGRAVS_KERNEL_GROUP_USER;
-      return launch_group2_t<NG, false, false, false, true, true>(c, wp, glist, nlist);
+      // tables in LDS while they leave room for the pools of 16 waves (three 16 KB tables incl. the exp table; the C5 wiring --
+      // Newton on the diagonal, one law off it -- has two distinct ones); otherwise they are read through L1/L2
+      const bool tab = ng <= 2 || (!usr && wp.ntab_lds + wp.exp_tab <= 3);
+      return {true, yuk && !usr, tab, false, usr, id};
     }
   if(c->cfg.periodic)
-    return yuk ? launch_group2_t<NG, false, true, false, true>(c, wp, glist, nlist)
-               : launch_group2_t<NG, false, false, false, true>(c, wp, glist, nlist);
-  if((!yuk || wp.user) && wp.bam)
+    return {false, yuk && !usr, false, true, usr, id};
+  // Tree-only instantiations stage no tables: their TAB_LDS slot selects the variant that evaluates law ids -- the BAM and the
+  // user-defined laws (k_walk_group2: BAMCAP)
+  const bool bam = wp.bam && (!yuk || usr);
+  return {false, yuk && !bam, bam, false, false, bam ? id : NGRAVS_KERNEL_GROUP};
+}
+// ... and instantiated for these rows <NG, PM, YUK, TAB_LDS, LATT, USR> alone (NG <= 2: the first TreePM line repeats two rows of the second)
+template <int NG>
+using GroupRowsNG = Table<Row<NG, 1, 0, NG <= 2, 0, 1>, Row<NG, 1, 0, NG <= 2, 0, 0>, Row<NG, 1, 1, NG <= 2, 0, 0>,   // TreePM
+                          Row<NG, 1, 0, 1, 0, 0>, Row<NG, 1, 1, 1, 0, 0>,                                            // TreePM, tables in LDS
+                          Row<NG, 0, 0, 0, 1, 1>, Row<NG, 0, 0, 0, 1, 0>, Row<NG, 0, 1, 0, 1, 0>,                     // periodic tree-only
+                          Row<NG, 0, 0, 1, 0, 0>, Row<NG, 0, 0, 0, 0, 0>, Row<NG, 0, 1, 0, 0, 0>>;                    // tree-only: law ids, plain
+using GroupRows = decltype(GroupRowsNG<1>{} + GroupRowsNG<2>{} + GroupRowsNG<3>{});
+
+// the whole walk (split into traversal / evaluation kernel pairs unless the tuning asks for the fused kernel), or the groups of
+// glist again (always the fused kernel)
+static int launch_group(ngravs_ctx *c, const WalkParams &wp, bool *used_split, int *glist = nullptr, int nlist = 0)
+{
+  const bool split = !c->tune.walk_fused && !glist;
+  if(!glist)
     {
-      c->last_walk_kernel = wp.user ? NGRAVS_KERNEL_GROUP_USER : NGRAVS_KERNEL_GROUP;
-      return launch_group2_t<NG, false, false, true, false>(c, wp, glist, nlist);
+      c->walk_batches = 0;
+      *used_split = split;
     }
-  return yuk ? launch_group2_t<NG, false, true, false, false>(c, wp, glist, nlist)
-             : launch_group2_t<NG, false, false, false, false>(c, wp, glist, nlist);
+  const GroupVariant v = group_variant(c, wp, c->cfg.n_gravs);
+  c->last_walk_kernel = v.reports;
+  const int key[] = {c->cfg.n_gravs, v.pm, v.yuk, v.tab, v.latt, v.usr};
+  return dispatch(c, GroupRows{}, key, [&](auto row) {
+    if(split)
+      return launch_group3_t(row, c, wp);
+    return launch_group2_t(row, c, wp, glist, nlist);
+  });
 }
 
 // the largest distance a tree-only walk or direct sum can evaluate a law at: the diagonal of the domain cube (drifted
@@ -2737,6 +2732,49 @@ static int launch_group(ngravs_ctx *c, const WalkParams &wp, bool allow_split, b
 static double user_reach(const ngravs_ctx *c) { return c->cfg.pmgrid ? 1.25 * 6.0 * c->asmth : 1.25 * sqrt(3.0) * c->dom[6]; }
 // periodic tree-only walk and periodic direct sum: the nearest image is at most half a box diagonal away
 static double lattice_reach(const ngravs_ctx *c) { return 1.25 * 0.5 * sqrt(3.0) * c->cfg.box_size; }
+
+// Lanes per target of the group walk (0: one, i.e. 64 targets per wave).
+// sparse active sets: 64 compacted targets span a box much wider than the short-range reach, so the conservative
+// group tests would collect (and then mostly discard) huge lists; walk them in sub-groups of 64/S targets, S lanes
+// per target (k_walk_group2).
+static int walk_spread_choice(const ngravs_ctx *c, const WalkParams &wp, bool latt)
+{
+  const bool pm = c->cfg.pmgrid != 0;
+  const int tuned = c->tune.walk_spread;   // tests / tuning: 1, 2, 4 ... 64 lanes per target (0: the choice below)
+  if(c->walk_ntargets >= 0 && !c->walk_dense_tlist && pm && c->cfg.box_size > 0)
+    {
+      if(tuned >= 1)
+        return tuned > 1 ? tuned : 0;
+      const double vol_per_target = pow(c->cfg.box_size, 3) * (double)c->shard_count / ((double)c->n * (double)(c->walk_ntargets > 0 ? c->walk_ntargets : 1));
+      // measured (16 M particles, 10 % / 1 % / 0.1 % active): S = 1 wins while 64 targets span less than ~2.5 reaches,
+      // beyond that one target per wave does (intermediate S multiply the traversals without shrinking the lists enough)
+      return cbrt(vol_per_target * 64.0) > 2.5 * sqrt(wp.reach2) ? 64 : 0;
+    }
+  if(tuned > 1)
+    return tuned;   // dense target sets: sub-groups of 64/S targets on request (a smaller box accepts more monopoles)
+  if(tuned == 0)
+    {
+      // Measured (tools/spread_sweep.sh, profiles/r04_spread_sweep.json): two lanes per target pay in a strongly clustered TreePM
+      // set once its units are single groups (2^20 particles, 60 % in one clump: 1079 -> 871 pairs per target, 5.15 -> 4.67 ms);
+      // a tree-only set with too few groups to fill the device (GalaxyCollision.IC: 938 groups of 64 for 4096 waves) walks faster
+      // with 4 lanes per target (4.2 -> 1.9 ms); a large one does not (4 M Plummer sphere: 12.5 / 14.8 / 19.5 ms for S = 1 / 2 / 4).
+      const long long g64 = (walk_tcount(c) + WAVE - 1) / WAVE;
+      if(pm && c->walk_unit_state == 1 && c->walk_ia_ratio > 2.0)
+        return 2;
+      if(!pm && !latt && g64 > 0 && g64 < 2048)
+        return g64 < 1024 ? 4 : 2;
+    }
+  return 0;
+}
+
+// flag word and the four statistics sums of the walk kernels, after they have finished
+static int walk_read_back(ngravs_ctx *c, int *flag, unsigned long long (&st64)[4])
+{
+  HIP_TRY(c, hipMemcpyAsync(flag, c->walk_counters.p + 1, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(st64, c->walk_counters.p + 16, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return NGRAVS_OK;
+}
 
 int walk_run(ngravs_ctx *c)
 {
@@ -2792,85 +2830,19 @@ int walk_run(ngravs_ctx *c)
   HIP_TRY(c, hipEventRecord(c->evk0, c->stream));
   int rc = NGRAVS_OK;
   bool used_split = false;
-  auto group_launch = [&](bool allow_split, int *glist, int nlist) -> int {
-    bool us = false;
-    int r;
-    switch(c->cfg.n_gravs)
-      {
-      case 1:
-        r = launch_group<1>(c, wp, allow_split, &us, glist, nlist);
-        break;
-      case 2:
-        r = launch_group<2>(c, wp, allow_split, &us, glist, nlist);
-        break;
-      default:
-        r = launch_group<3>(c, wp, allow_split, &us, glist, nlist);
-        break;
-      }
-    if(!glist)
-      used_split = us;
-    return r;
-  };
-  auto strict_launch = [&]() {
-    switch(c->cfg.n_gravs)
-      {
-      case 1:
-        pm ? (wp.user ? launch_strict<1, true, false, true>(c, wp, li) : launch_strict<1, true, false>(c, wp, li))
-           : (latt ? (wp.user ? launch_strict<1, false, true, true>(c, wp, li) : launch_strict<1, false, true>(c, wp, li))
-                   : (wp.user ? launch_strict<1, false, false, true>(c, wp, li) : launch_strict<1, false, false>(c, wp, li)));
-        break;
-      case 2:
-        pm ? (wp.user ? launch_strict<2, true, false, true>(c, wp, li) : launch_strict<2, true, false>(c, wp, li))
-           : (latt ? (wp.user ? launch_strict<2, false, true, true>(c, wp, li) : launch_strict<2, false, true>(c, wp, li))
-                   : (wp.user ? launch_strict<2, false, false, true>(c, wp, li) : launch_strict<2, false, false>(c, wp, li)));
-        break;
-      default:
-        pm ? (wp.user ? launch_strict<3, true, false, true>(c, wp, li) : launch_strict<3, true, false>(c, wp, li))
-           : (latt ? (wp.user ? launch_strict<3, false, true, true>(c, wp, li) : launch_strict<3, false, true>(c, wp, li))
-                   : (wp.user ? launch_strict<3, false, false, true>(c, wp, li) : launch_strict<3, false, false>(c, wp, li)));
-        break;
-      }
-  };
   if(strict)
     {
       if(c->walk_counters.ensure(32))
         return NGRAVS_ERR_NOMEM;
       HIP_TRY(c, hipMemsetAsync(c->walk_counters.p, 0, sizeof(int) * 32, c->stream));
-      strict_launch();
+      c->last_walk_kernel = wp.user ? NGRAVS_KERNEL_STRICT_USER : NGRAVS_KERNEL_STRICT;
+      const int key[] = {c->cfg.n_gravs, pm, latt, wp.user != 0};
+      rc = dispatch(c, StrictRows{}, key, [&](auto row) { return launch_strict(row, c, wp, li); });
     }
   else
     {
-      // sparse active sets: 64 compacted targets span a box much wider than the short-range reach, so the conservative
-      // group tests would collect (and then mostly discard) huge lists; walk them in sub-groups of 64/S targets, S lanes
-      // per target (k_walk_group2).
-      c->walk_spread = 0;
-      if(c->walk_ntargets >= 0 && !c->walk_dense_tlist && pm && c->cfg.box_size > 0)
-        {
-          const double vol_per_target = pow(c->cfg.box_size, 3) * (double)c->shard_count / ((double)c->n * (double)(c->walk_ntargets > 0 ? c->walk_ntargets : 1));
-          // measured (16 M particles, 10 % / 1 % / 0.1 % active): S = 1 wins while 64 targets span less than ~2.5 reaches,
-          // beyond that one target per wave does (intermediate S multiply the traversals without shrinking the lists enough)
-          const int sp = cbrt(vol_per_target * 64.0) > 2.5 * sqrt(wp.reach2) ? 64 : 1;
-          c->walk_spread = sp;
-          if(c->tune.walk_spread >= 1)   // tests / tuning: 1, 2, 4 ... 64 lanes per target
-            c->walk_spread = c->tune.walk_spread;
-          if(c->walk_spread <= 1)
-            c->walk_spread = 0;
-        }
-      else if(c->tune.walk_spread > 1)
-        c->walk_spread = c->tune.walk_spread;   // dense target sets: sub-groups of 64/S targets on request (a smaller box accepts more monopoles)
-      else if(c->tune.walk_spread == 0)
-        {
-          // Measured (tools/spread_sweep.sh, profiles/r04_spread_sweep.json): two lanes per target pay in a strongly clustered TreePM
-          // set once its units are single groups (2^20 particles, 60 % in one clump: 1079 -> 871 pairs per target, 5.15 -> 4.67 ms);
-          // a tree-only set with too few groups to fill the device (GalaxyCollision.IC: 938 groups of 64 for 4096 waves) walks faster
-          // with 4 lanes per target (4.2 -> 1.9 ms); a large one does not (4 M Plummer sphere: 12.5 / 14.8 / 19.5 ms for S = 1 / 2 / 4).
-          const long long g64 = (walk_tcount(c) + WAVE - 1) / WAVE;
-          if(pm && c->walk_unit_state == 1 && c->walk_ia_ratio > 2.0)
-            c->walk_spread = 2;
-          else if(!pm && !latt && g64 > 0 && g64 < 2048)
-            c->walk_spread = g64 < 1024 ? 4 : 2;
-        }
-      rc = group_launch(true, nullptr, 0);
+      c->walk_spread = walk_spread_choice(c, wp, latt);
+      rc = launch_group(c, wp, &used_split);
     }
   if(rc != NGRAVS_OK)
     return rc;
@@ -2893,9 +2865,8 @@ int walk_run(ngravs_ctx *c)
     {
       int flag = 0;
       unsigned long long st64[4] = {0, 0, 0, 0};
-      HIP_TRY(c, hipMemcpyAsync(&flag, c->walk_counters.p + 1, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(c, hipMemcpyAsync(st64, c->walk_counters.p + 16, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(c, hipStreamSynchronize(c->stream));
+      if((rc = walk_read_back(c, &flag, st64)))
+        return rc;
       if(used_split)
         {
           // groups whose item lists or LIFO outgrew their region of the split walk were skipped by the evaluation kernel.
@@ -2907,14 +2878,13 @@ int walk_run(ngravs_ctx *c)
           HIP_TRY(c, hipMemcpy(ovf, c->walk_counters.p + 2, 2 * sizeof(int), hipMemcpyDeviceToHost));
           if(ovf[0] > 0)
             {
-              rc = group_launch(false, c->walk_ovf.p, ovf[0]);
+              rc = launch_group(c, wp, nullptr, c->walk_ovf.p, ovf[0]);
               if(rc != NGRAVS_OK)
                 return rc;
               HIP_TRY(c, hipEventRecord(c->evk1, c->stream));
               HIP_TRY(c, hipGetLastError());
-              HIP_TRY(c, hipMemcpyAsync(&flag, c->walk_counters.p + 1, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-              HIP_TRY(c, hipMemcpyAsync(st64, c->walk_counters.p + 16, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-              HIP_TRY(c, hipStreamSynchronize(c->stream));
+              if((rc = walk_read_back(c, &flag, st64)))
+                return rc;
               const int Gs = (WAVE / (c->walk_spread > 1 ? c->walk_spread : 1)) * c->walk_sg;
               const long long ng = (walk_tcount(c) + Gs - 1) / Gs;
               if((long long)ovf[0] * 256 > ng)
@@ -2974,8 +2944,11 @@ int walk_finish(ngravs_ctx *c)
   return NGRAVS_OK;
 }
 
-// direct sum for explicit target records over the OWN particles of this task (distributed gravity_forcetest)
-int direct_run_targets(ngravs_ctx *c, const double4 *d_tpm, const int *d_ttype, int64_t nt, double *d_acc, double r_need)
+// The direct sum over the particles of this task: for the targets d_idx (indices), or for explicit target records d_tpm / d_ttype
+// over the OWN particles alone (distributed gravity_forcetest).  The two differ in the kernel's last five arguments only.
+using DirectRows = Table<Row<0>, Row<1>>;   // k_direct<USER>
+template <int USER> static auto direct_kernel(Row<USER>) { return k_direct<USER>; }
+static int direct_launch(ngravs_ctx *c, double r_need, const int *d_idx, int64_t nt, double *d_acc, const double4 *d_tpm, const int *d_ttype)
 {
   if(c->cfg.periodic && !user_lattice_complete(c))
     {
@@ -2983,55 +2956,32 @@ int direct_run_targets(ngravs_ctx *c, const double4 *d_tpm, const int *d_ttype, 
                                           "a pair wired with a user-defined law has no lattice function (ngravs_create_with_lattice)");
       return NGRAVS_ERR_WIRING;
     }
-  {
-    int rcu = user_tables_ensure(c, c->cfg.periodic ? lattice_reach(c) : fmax(r_need, user_reach(c)));
-    if(rcu)
-      return rcu;
-  }
+  const bool latt = c->cfg.periodic != 0;   // forcetree.c:3515-3529: the PERIODIC direct sum adds lattice_corr
+  int rc = user_tables_ensure(c, latt ? lattice_reach(c) : fmax(r_need, user_reach(c)));
+  if(rc)
+    return rc;
   WalkParams wp;
   make_walk_params(c, &wp);
   LawIds li;
   make_law_ids(c, &li);
-  const bool latt = c->cfg.periodic != 0;
-  if(latt)
-    {
-      int rcl = ensure_lattice(c);
-      if(rcl)
-        return rcl;
-    }
-  hipLaunchKernelGGL(wp.user ? k_direct<true> : k_direct<false>, dim3((unsigned)nt), dim3(256), 0, c->stream, c->s_pm.p, c->s_type.p, (long long)c->n, (const int *)nullptr,
-                     (long long)nt, wp, li, c->cfg.G, latt ? c->lat.p : (const double *)nullptr, d_acc, d_tpm, d_ttype, c->s_active.p, 1);
+  if(latt && (rc = ensure_lattice(c)))
+    return rc;
+  const int key[] = {wp.user != 0};
+  rc = dispatch(c, DirectRows{}, key, [&](auto row) {
+    hipLaunchKernelGGL(direct_kernel(row), dim3((unsigned)nt), dim3(256), 0, c->stream, c->s_pm.p, c->s_type.p, (long long)c->n, d_idx, (long long)nt,
+                       wp, li, c->cfg.G, latt ? c->lat.p : (const double *)nullptr, d_acc, d_tpm, d_ttype,
+                       d_tpm ? c->s_active.p : (const unsigned char *)nullptr, d_tpm ? 1 : 0);
+    return NGRAVS_OK;
+  });
+  if(rc)
+    return rc;
   HIP_TRY(c, hipGetLastError());
   return NGRAVS_OK;
 }
 
-int direct_run(ngravs_ctx *c, const int *d_idx, int64_t nt, double *d_acc)
+int direct_run_targets(ngravs_ctx *c, const double4 *d_tpm, const int *d_ttype, int64_t nt, double *d_acc, double r_need)
 {
-  if(c->cfg.periodic && !user_lattice_complete(c))
-    {
-      ngravs_report(c, NGRAVS_ERR_WIRING, "the periodic direct sum adds the lattice correction of the law (forcetree.c:3515-3529): "
-                                          "a pair wired with a user-defined law has no lattice function (ngravs_create_with_lattice)");
-      return NGRAVS_ERR_WIRING;
-    }
-  {
-    int rcu = user_tables_ensure(c, c->cfg.periodic ? lattice_reach(c) : user_reach(c));
-    if(rcu)
-      return rcu;
-  }
-  WalkParams wp;
-  make_walk_params(c, &wp);
-  LawIds li;
-  make_law_ids(c, &li);
-  const bool latt = c->cfg.periodic != 0;   // forcetree.c:3515-3529: the PERIODIC direct sum adds lattice_corr
-  if(latt)
-    {
-      int rcl = ensure_lattice(c);
-      if(rcl)
-        return rcl;
-    }
-  hipLaunchKernelGGL(wp.user ? k_direct<true> : k_direct<false>, dim3((unsigned)nt), dim3(256), 0, c->stream, c->s_pm.p, c->s_type.p, (long long)c->n, d_idx,
-                     (long long)nt, wp, li, c->cfg.G, latt ? c->lat.p : (const double *)nullptr, d_acc, (const double4 *)nullptr,
-                     (const int *)nullptr, (const unsigned char *)nullptr, 0);
-  HIP_TRY(c, hipGetLastError());
-  return NGRAVS_OK;
+  return direct_launch(c, r_need, nullptr, nt, d_acc, d_tpm, d_ttype);
 }
+
+int direct_run(ngravs_ctx *c, const int *d_idx, int64_t nt, double *d_acc) { return direct_launch(c, 0.0, d_idx, nt, d_acc, nullptr, nullptr); }

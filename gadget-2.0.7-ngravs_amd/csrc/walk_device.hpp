@@ -1,4 +1,5 @@
-// walk_device.hpp -- device helpers shared by the walk kernels (kernels_walk.hip, kernels_eval.hip)
+// walk_device.hpp -- device helpers shared by the walk kernels (kernels_walk.hip, kernels_eval.hip) and the one way their
+// launchers choose an instantiation (Row / Table / dispatch, at the end)
 #pragma once
 #include "engine.hpp"
 
@@ -75,3 +76,29 @@ __device__ __forceinline__ double wave_max(double v)
   return v;
 }
 
+// ---- host side: which instantiation of a kernel runs ----------------------------------------------------------------------------
+// The instantiations a kernel has are listed once, as a Table of Rows of template arguments.  dispatch() calls f(Row<...>{}) for
+// the row that equals the runtime key and f -- a launcher -- deduces its template arguments from that tag: a combination that is
+// not listed is never instantiated, it is NGRAVS_ERR_STATE.
+template <int... A> struct Row
+{
+  static bool is(const int (&key)[sizeof...(A)])
+  {
+    const int a[] = {A...};
+    for(size_t i = 0; i < sizeof...(A); i++)
+      if(a[i] != key[i])
+        return false;
+    return true;
+  }
+};
+template <class... R> struct Table
+{
+};
+template <class... A, class... B> constexpr Table<A..., B...> operator+(Table<A...>, Table<B...>) { return {}; }
+template <class... R, size_t N, class F> static int dispatch(ngravs_ctx *c, Table<R...>, const int (&key)[N], F &&f)
+{
+  int rc = NGRAVS_ERR_STATE;
+  if(!((R::is(key) && ((rc = f(R{})), true)) || ...))
+    ngravs_report(c, NGRAVS_ERR_STATE, "no kernel is instantiated for this combination of wiring and walk");
+  return rc;
+}
