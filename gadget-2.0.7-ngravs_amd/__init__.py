@@ -41,7 +41,7 @@ EXPORTS = [
     "ngravs_dd_leaf_sums_kept", "ngravs_dd_pack_leaves_kept", "ngravs_dd_refresh_halo", "ngravs_dd_update_top", "ngravs_dd_get_kept",
     "ngravs_dd_set_ids", "ngravs_dd_get_ids",
     "ngravs_pm_slab_begin", "ngravs_pm_slab_pack", "ngravs_pm_slab_unpack", "ngravs_pm_slab_bytes",
-    "ngravs_sph_density", "ngravs_sph_kernel",
+    "ngravs_sph_density", "ngravs_sph_kernel", "ngravs_sph_hydro",
 ]
 # include/ngravs_host.h (plain-C multi-task drivers over a communicator vtable, linked into the same library)
 HOST_EXPORTS = ["ngravs_host_comm_selftest", "ngravs_host_kept_step", "ngravs_host_toptree_borrow", "ngravs_host_domain_decomposition", "ngravs_host_domain_owners", "ngravs_host_domain_halo",
@@ -130,6 +130,7 @@ def lib():
         L.ngravs_user_lattice_table.argtypes = [abi.LATTICE_FN, C.c_double, C.c_void_p]
         L.ngravs_sph_density.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ngravs_sph_kernel.argtypes = [C.c_double, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        L.ngravs_sph_hydro.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -210,6 +211,17 @@ def sph_kernel(h, r):
     if rc != 0:
         raise NgravsError("ngravs_sph_kernel: %d" % rc)
     return wk, dwk
+
+
+def hydro_factors(time, omega0, omega_lambda, hubble, gamma=5.0 / 3):
+    """(hubble_a2, fac_mu, fac_vsic_fix) of a comoving run at expansion factor `time` (hydra.c:78-97), for
+    Engine.sph_hydro(..., comoving=...); no GPU needed"""
+    hubble_a = omega0 / (time * time * time) + (1 - omega0 - omega_lambda) / (time * time) + omega_lambda
+    hubble_a = hubble * np.sqrt(hubble_a)
+    hubble_a2 = time * time * hubble_a
+    fac_mu = np.power(time, 3 * (gamma - 1) / 2) / time
+    fac_vsic_fix = hubble_a * np.power(time, 3 * (gamma - 1))
+    return float(hubble_a2), float(fac_mu), float(fac_vsic_fix)
 
 
 def _ptr(a):
@@ -455,6 +467,60 @@ class Engine:
         rounds, ms = C.c_int32(0), C.c_double(0)
         self._check(lib().ngravs_sph_density(self._h, C.byref(si), C.byref(so), C.byref(rounds), C.byref(ms)), "ngravs_sph_density")
         res["max_rounds"], res["kernel_ms"] = int(rounds.value), float(ms.value)
+        return res
+
+    def sph_hydro(self, vel, hsml, density, pressure, dhsml_factor, div_vel, curl_vel, *, art_bulk_visc_const, timestep=None,
+                  timebase_interval=0.0, gamma=5.0 / 3, viscosity_limiter=True, comoving=None, out=None):
+        """hydro_force() of the reference for one task (hydra.c:50-346): vel = SphP[].VelPred[N,3]; hsml, density, pressure,
+        dhsml_factor, div_vel, curl_vel [N] as density() and the pressure line left them; timestep = Ti_endstep - Ti_begstep [N]
+        int32 or None (all 0); one row per particle of the last hand-over.  Every type-0 row is read (all gas particles are
+        sources), only rows of active type-0 particles are written.  comoving: None, or hydro_factors(...).  numpy arrays, or
+        torch tensors on the device (float64 / int32, contiguous: no copy through the host).  Returns a dict: hydro_accel [N,3],
+        dt_entropy, max_signal_vel (rows that are no targets: 0 -- or what `out`, a dict of arrays of the same kind, held),
+        kernel_ms."""
+        cols = dict(vel_pred=vel, hsml=hsml, density=density, pressure=pressure, dhsml_factor=dhsml_factor, div_vel=div_vel,
+                    curl_vel=curl_vel)
+        on_device = not isinstance(vel, np.ndarray) and hasattr(vel, "data_ptr")
+        res = {}
+        if on_device:
+            import torch
+            assert all(a.dtype == torch.float64 and a.is_contiguous() for a in cols.values())
+            if timestep is not None:
+                assert timestep.dtype == torch.int32 and timestep.is_contiguous()
+            for k in abi.HYDRO_OUT_NAMES:
+                res[k] = out[k] if out and k in out else torch.zeros((self.n, 3) if k == "hydro_accel" else (self.n,),
+                                                                     dtype=torch.float64, device=vel.device)
+                assert res[k].dtype == torch.float64 and res[k].is_contiguous()
+            addr = lambda a: a.data_ptr()   # noqa: E731
+            torch.cuda.synchronize()   # the library works on a stream of its own: the tensors above must be complete
+        else:
+            cols = {k: np.ascontiguousarray(a, dtype=np.float64) for k, a in cols.items()}
+            if timestep is not None:
+                timestep = np.ascontiguousarray(timestep, dtype=np.int32)
+            for k in abi.HYDRO_OUT_NAMES:
+                res[k] = out[k] if out and k in out else np.zeros((self.n, 3) if k == "hydro_accel" else self.n)
+                assert res[k].dtype == np.float64 and res[k].flags.c_contiguous
+            addr = lambda a: a.ctypes.data   # noqa: E731
+        assert all(tuple(a.shape) == ((self.n, 3) if k == "vel_pred" else (self.n,)) for k, a in cols.items())
+        assert tuple(res["hydro_accel"].shape) == (self.n, 3) and tuple(res["dt_entropy"].shape) == (self.n,)
+        assert tuple(res["max_signal_vel"].shape) == (self.n,) and (timestep is None or tuple(timestep.shape) == (self.n,))
+        hi, ho = abi.HydroIn(), abi.HydroOut()
+        for k, a in cols.items():
+            setattr(hi, k, addr(a))
+            setattr(hi, k + "_stride", 24 if k == "vel_pred" else 8)
+        if timestep is not None:
+            hi.timestep, hi.timestep_stride = addr(timestep), 4
+        hi.art_bulk_visc_const, hi.timebase_interval, hi.gamma = float(art_bulk_visc_const), float(timebase_interval), float(gamma)
+        hi.viscosity_limiter, hi.on_device = int(bool(viscosity_limiter)), int(on_device)
+        if comoving is not None:
+            hi.comoving = 1
+            hi.hubble_a2, hi.fac_mu, hi.fac_vsic_fix = (float(x) for x in comoving)
+        for k in abi.HYDRO_OUT_NAMES:
+            setattr(ho, k, addr(res[k]))
+            setattr(ho, k + "_stride", 24 if k == "hydro_accel" else 8)
+        ms = C.c_double(0)
+        self._check(lib().ngravs_sph_hydro(self._h, C.byref(hi), C.byref(ho), C.byref(ms)), "ngravs_sph_hydro")
+        res["kernel_ms"] = float(ms.value)
         return res
 
     def stats(self):

@@ -133,6 +133,24 @@ class SphOut(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in SPH_OUT_NAMES] + [(k + "_stride", C.c_int64) for k in SPH_OUT_NAMES]
 
 
+HYDRO_IN_NAMES = ("vel_pred", "hsml", "density", "pressure", "dhsml_factor", "div_vel", "curl_vel", "timestep")
+HYDRO_OUT_NAMES = ("hydro_accel", "dt_entropy", "max_signal_vel")
+
+
+class HydroIn(C.Structure):
+    """ngravs_hydro_in_t"""
+    _fields_ = [f for k in HYDRO_IN_NAMES for f in ((k, C.c_void_p), (k + "_stride", C.c_int64))] + [
+        ("art_bulk_visc_const", C.c_double), ("timebase_interval", C.c_double), ("gamma", C.c_double),
+        ("hubble_a2", C.c_double), ("fac_mu", C.c_double), ("fac_vsic_fix", C.c_double),
+        ("viscosity_limiter", C.c_int32), ("comoving", C.c_int32), ("on_device", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
+class HydroOut(C.Structure):
+    """ngravs_hydro_out_t"""
+    _fields_ = [(k, C.c_void_p) for k in HYDRO_OUT_NAMES] + [(k + "_stride", C.c_int64) for k in HYDRO_OUT_NAMES]
+
+
 def make_config(n_gravs=1, periodic=0, pmgrid=0, box_size=0.0, G=1.0, theta=0.5, err_tol_force_acc=0.005,
                 softening=None, type_to_grav=None, wiring="newton", yukawa_imass=60.0, walk_mode=WALK_STRICT,
                 tree_alloc_factor=0.0, device=0, rank=0, world_size=1, group_reach=0.0):

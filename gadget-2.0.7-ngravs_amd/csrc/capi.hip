@@ -70,6 +70,12 @@ __global__ void k_copy_masked_f32(const unsigned char *__restrict__ act, long lo
   if(i < n && (act[i] & 1))
     dst[i] = src[i];
 }
+__global__ void k_pack_strided_i32(const unsigned char *src, long long stride, long long n, int *dst)
+{
+  long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+  if(i < n)
+    dst[i] = *reinterpret_cast<const int *>(src + i * stride);
+}
 __global__ void k_pack_strided_f32_to_f64(const unsigned char *src, long long stride, long long n, double *dst)
 {
   long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
@@ -405,6 +411,10 @@ extern "C" void ngravs_destroy(ngravs_ctx *c)
   c->sph_row.release();
   c->sph_rounds.release();
   c->sph_counters.release();
+  c->sph_col_in.release();
+  c->sph_ts_in.release();
+  c->sph_hsrc.release();
+  c->sph_hmax.release();
   (void)hipEventDestroy(c->ev0);
   (void)hipEventDestroy(c->ev1);
   (void)hipEventDestroy(c->evk0);
@@ -1894,6 +1904,64 @@ extern "C" int ngravs_pm_slab_bytes(ngravs_ctx *c, double bytes[4])
   return NGRAVS_OK;
 }
 
+// ---- SPH: what ngravs_sph_density and ngravs_sph_hydro share ------------------------------------------------------------------
+static int upload_column_i32(ngravs_ctx *c, const void *src, int64_t stride, int64_t n, int on_device, int *dst)
+{
+  if(on_device)
+    {
+      if(stride == (int64_t)sizeof(int))
+        HIP_TRY(c, hipMemcpyAsync(dst, src, sizeof(int) * n, hipMemcpyDeviceToDevice, c->stream));
+      else
+        hipLaunchKernelGGL(k_pack_strided_i32, GRID1(n), 0, c->stream, (const unsigned char *)src, (long long)stride, (long long)n, dst);
+      return NGRAVS_OK;
+    }
+  c->host_stage.resize(sizeof(int) * (size_t)n);
+  int *h = reinterpret_cast<int *>(c->host_stage.data());
+  for(int64_t i = 0; i < n; i++)
+    memcpy(h + i, (const unsigned char *)src + i * stride, sizeof(int));
+  HIP_TRY(c, hipMemcpyAsync(dst, h, sizeof(int) * n, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return NGRAVS_OK;
+}
+
+// one task, a built tree of the current particle set (refit first when the particles drifted, as ngravs_gravity_tree does)
+template <class Refuse> static int sph_ready(ngravs_ctx *c, Refuse refuse)
+{
+  if(c->cfg.world_size > 1 || c->top.on || c->n_local != c->n)
+    return refuse(NGRAVS_ERR_STATE, "single task only (the neighbour search does not cross task boundaries yet)");
+  if(!c->have_order || !c->have_tree)
+    return refuse(NGRAVS_ERR_STATE, "needs a built tree of the current particle set");
+  (void)hipSetDevice(c->cfg.device);
+  if(c->tree_stale)
+    return ngravs_force_update_tree(c);
+  return NGRAVS_OK;
+}
+
+// sph_res [nres][nt] (list order) -> the targets' rows of the caller's strided columns dst[k] (NULL: not wanted)
+static int sph_write_targets(ngravs_ctx *c, int nres, long long nt, double *const *dst, const int64_t *stride, int on_device)
+{
+  int rc;
+  if(on_device)
+    {
+      for(int k = 0; k < nres; k++)
+        if(dst[k] && (rc = sph_scatter(c, c->sph_res.p + k * nt, nt, dst[k], stride[k])))
+          return rc;
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+      return NGRAVS_OK;
+    }
+  c->host_stage.resize((sizeof(double) * nres + sizeof(int)) * (size_t)nt);
+  double *hres = reinterpret_cast<double *>(c->host_stage.data());
+  int *hrow = reinterpret_cast<int *>(c->host_stage.data() + sizeof(double) * nres * (size_t)nt);
+  HIP_TRY(c, hipMemcpyAsync(hres, c->sph_res.p, sizeof(double) * nres * nt, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(hrow, c->sph_row.p, sizeof(int) * nt, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  for(int k = 0; k < nres; k++)
+    if(dst[k])
+      for(long long t = 0; t < nt; t++)
+        memcpy(reinterpret_cast<unsigned char *>(dst[k]) + hrow[t] * stride[k], &hres[k * nt + t], sizeof(double));
+  return NGRAVS_OK;
+}
+
 // ---- SPH density (density.c:56-441 for one task; kernels_sph.hip) ---------------------------------------------------------
 extern "C" int ngravs_sph_density(ngravs_ctx *c, const ngravs_sph_in_t *in, const ngravs_sph_out_t *out, int32_t *max_rounds, double *kernel_ms)
 {
@@ -1907,13 +1975,8 @@ extern "C" int ngravs_sph_density(ngravs_ctx *c, const ngravs_sph_in_t *in, cons
     return refuse(NGRAVS_ERR_ARG, "in, in->hsml and in->vel_pred must not be NULL");
   if(!(in->des_num_ngb > 0) || !(in->max_num_ngb_deviation >= 0) || !(in->min_gas_hsml >= 0))
     return refuse(NGRAVS_ERR_ARG, "des_num_ngb must be > 0, max_num_ngb_deviation and min_gas_hsml >= 0");
-  if(c->cfg.world_size > 1 || c->top.on || c->n_local != c->n)
-    return refuse(NGRAVS_ERR_STATE, "single task only (the neighbour search does not cross task boundaries yet)");
-  if(!c->have_order || !c->have_tree)
-    return refuse(NGRAVS_ERR_STATE, "needs a built tree of the current particle set");
-  (void)hipSetDevice(c->cfg.device);
   int rc;
-  if(c->tree_stale && (rc = ngravs_force_update_tree(c)))   // drifted tree: refit first, as ngravs_gravity_tree does
+  if((rc = sph_ready(c, refuse)))
     return rc;
   if(max_rounds)
     *max_rounds = 0;
@@ -1964,25 +2027,85 @@ extern "C" int ngravs_sph_density(ngravs_ctx *c, const ngravs_sph_in_t *in, cons
       dst[SPH_CURLVEL] = out->curl_vel, stride[SPH_CURLVEL] = out->curl_vel_stride;
       dst[SPH_DHSML] = out->dhsml_factor, stride[SPH_DHSML] = out->dhsml_factor_stride;
     }
-  if(in->on_device)
-    {
-      for(int k = 0; k < SPH_NRES; k++)
-        if(dst[k] && (rc = sph_scatter(c, c->sph_res.p + k * nt, nt, dst[k], stride[k])))
-          return rc;
-      HIP_TRY(c, hipStreamSynchronize(c->stream));
-      return NGRAVS_OK;
-    }
-  c->host_stage.resize((sizeof(double) * SPH_NRES + sizeof(int)) * (size_t)nt);
-  double *hres = reinterpret_cast<double *>(c->host_stage.data());
-  int *hrow = reinterpret_cast<int *>(c->host_stage.data() + sizeof(double) * SPH_NRES * (size_t)nt);
-  HIP_TRY(c, hipMemcpyAsync(hres, c->sph_res.p, sizeof(double) * SPH_NRES * nt, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(hrow, c->sph_row.p, sizeof(int) * nt, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  for(int k = 0; k < SPH_NRES; k++)
-    if(dst[k])
-      for(long long t = 0; t < nt; t++)
-        memcpy(reinterpret_cast<unsigned char *>(dst[k]) + hrow[t] * stride[k], &hres[k * nt + t], sizeof(double));
-  return NGRAVS_OK;
+  return sph_write_targets(c, SPH_NRES, nt, dst, stride, in->on_device);
+}
+
+// ---- SPH hydro force (hydra.c:50-346 for one task; kernels_sph.hip) ---------------------------------------------------------
+static_assert(sizeof(ngravs_hydro_in_t) == 192 && sizeof(ngravs_hydro_out_t) == 48, "the Python mirror (abi.HydroIn / HydroOut) assumes this layout");
+extern "C" int ngravs_sph_hydro(ngravs_ctx *c, const ngravs_hydro_in_t *in, const ngravs_hydro_out_t *out, double *kernel_ms)
+{
+  if(!c)
+    return NGRAVS_ERR_ARG;
+  auto refuse = [&](int code, const char *why) {
+    ngravs_report(c, code, std::string("ngravs_sph_hydro: ") + why);
+    return code;
+  };
+  if(!in || !in->vel_pred || !in->hsml || !in->density || !in->pressure || !in->dhsml_factor || !in->div_vel || !in->curl_vel)
+    return refuse(NGRAVS_ERR_ARG, "in and its vel_pred, hsml, density, pressure, dhsml_factor, div_vel, curl_vel must not be NULL");
+  if(!(in->gamma >= 1) || !(in->art_bulk_visc_const >= 0) || !(in->timebase_interval >= 0))
+    return refuse(NGRAVS_ERR_ARG, "gamma must be >= 1, art_bulk_visc_const and timebase_interval >= 0");
+  if(in->comoving && (!(in->hubble_a2 > 0) || !(in->fac_mu > 0) || !(in->fac_vsic_fix > 0)))
+    return refuse(NGRAVS_ERR_ARG, "comoving: hubble_a2, fac_mu and fac_vsic_fix must be > 0");
+  int rc;
+  if((rc = sph_ready(c, refuse)))
+    return rc;
+  if(kernel_ms)
+    *kernel_ms = 0;
+  const int64_t n = c->n_local;
+  if(n == 0 || c->nnodes <= 0)
+    return NGRAVS_OK;
+  if(c->sph_vel_in.ensure(3 * n) || c->sph_h_in.ensure(n) || c->sph_col_in.ensure(5 * n) || c->sph_ts_in.ensure(n))
+    return refuse(NGRAVS_ERR_NOMEM, "device allocation failed");
+  if((rc = upload_column_f64(c, in->vel_pred, in->vel_pred_stride, 3, n, in->on_device, c->sph_vel_in.p)))
+    return rc;
+  if((rc = upload_column_f64(c, in->hsml, in->hsml_stride, 1, n, in->on_device, c->sph_h_in.p)))
+    return rc;
+  const double *col[5] = {in->density, in->pressure, in->dhsml_factor, in->div_vel, in->curl_vel};
+  const int64_t cstride[5] = {in->density_stride, in->pressure_stride, in->dhsml_factor_stride, in->div_vel_stride, in->curl_vel_stride};
+  for(int k = 0; k < 5; k++)
+    if((rc = upload_column_f64(c, col[k], cstride[k], 1, n, in->on_device, c->sph_col_in.p + k * n)))
+      return rc;
+  if(in->timestep && (rc = upload_column_i32(c, in->timestep, in->timestep_stride, n, in->on_device, c->sph_ts_in.p)))
+    return rc;
+  SphHydroParams hp;
+  hp.periodic = c->cfg.periodic;
+  hp.box = c->cfg.box_size;
+  hp.boxhalf = 0.5 * c->cfg.box_size;
+  hp.comoving = in->comoving != 0;
+  hp.limiter = in->viscosity_limiter != 0;
+  hp.have_ts = in->timestep != nullptr;
+  hp.hubble_a2 = hp.comoving ? in->hubble_a2 : 1.0;   // hydra.c:96-97
+  hp.fac_mu = hp.comoving ? in->fac_mu : 1.0;
+  hp.fac_vsic_fix = hp.comoving ? in->fac_vsic_fix : 1.0;
+  hp.visc = in->art_bulk_visc_const;
+  hp.tbi = in->timebase_interval;
+  hp.gamma = in->gamma;
+  HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
+  SphHydroStats st;
+  if((rc = sph_hydro_run(c, hp, &st)))
+    return rc;
+  HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
+  if(kernel_ms)
+    *kernel_ms = ev_ms(c);
+  if(st.bad_hsml)
+    return refuse(NGRAVS_ERR_ARG, "a type-0 row's hsml is <= 0 or not finite");
+  if(st.bad_density)
+    return refuse(NGRAVS_ERR_ARG, "a type-0 row's density is <= 0 or not finite");
+  if(st.bad_pressure)
+    return refuse(NGRAVS_ERR_ARG, "a type-0 row's pressure is < 0 or not finite");
+  if(c->tune.sph_verbose && st.targets > 0)
+    printf("ngravs_sph_hydro: %lld targets, %lld candidates tested, %lld pairs evaluated\n", st.targets, st.candidates, st.pairs);
+  if(st.stack_ovf)
+    return refuse(NGRAVS_ERR_TREE, "the tree is deeper than the walk's stack");
+  const long long nt = st.targets;
+  if(nt == 0 || !out)
+    return NGRAVS_OK;
+  // only the targets' rows are written
+  double *dst[SPH_HY_NRES] = {out->hydro_accel, out->hydro_accel ? out->hydro_accel + 1 : nullptr, out->hydro_accel ? out->hydro_accel + 2 : nullptr,
+                              out->dt_entropy, out->max_signal_vel};
+  const int64_t stride[SPH_HY_NRES] = {out->hydro_accel_stride, out->hydro_accel_stride, out->hydro_accel_stride, out->dt_entropy_stride,
+                                       out->max_signal_vel_stride};
+  return sph_write_targets(c, SPH_HY_NRES, nt, dst, stride, in->on_device);
 }
 
 extern "C" int ngravs_sph_kernel(double h, const double *r, int64_t n, double *wk, double *dwk)

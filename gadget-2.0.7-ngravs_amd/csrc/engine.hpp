@@ -363,6 +363,11 @@ struct ngravs_ctx
   DevBuf<double> sph_res;                // [SPH_NRES][targets], list order
   DevBuf<int> sph_row, sph_rounds;       // per target: caller row, rounds taken
   DevBuf<unsigned long long> sph_counters;
+  // SPH hydro force (ngravs_sph_hydro): the node hmax lives here, not in n_geo / n_mom, which gravity reads
+  DevBuf<double> sph_col_in;             // the caller's Density, Pressure, DhsmlDensityFactor, DivVel, CurlVel columns, [5][own rows]
+  DevBuf<int> sph_ts_in;                 // the caller's timestep column
+  DevBuf<double> sph_hsrc;               // [SPH_HS_NCOL][n], Peano order: what hydro_evaluate needs of one gas particle
+  DevBuf<double> sph_hmax;               // per tree node: largest Hsml of the type-0 particles below it (0: no gas)
 };
 
 // Routes the context's launches to stream `s`, whose CU mask leaves them `cus` CUs, until the end of the scope (the kernels
@@ -483,6 +488,26 @@ struct SphStats
 // compacts the targets into sph_tlist, then iterates every target's smoothing length to acceptance in one launch: reads sph_vel
 // (Peano order) and sph_h_in (caller order), writes sph_res / sph_row / sph_rounds in list order
 int sph_density_run(ngravs_ctx *c, double des_num_ngb, double max_dev, double min_hsml, SphStats *st);
+// SPH hydro force.  Columns of sph_hsrc: VelPred[3], Hsml (0 for rows of other types), Density, Pressure / Density^2 *
+// DhsmlDensityFactor, the sound speed as a source (hydra.c:441-442), f2 (hydra.c:504-506), the timestep, the sound speed and f1 as
+// a target (hydra.c:379-382)
+enum { SPH_HS_VX = 0, SPH_HS_VY, SPH_HS_VZ, SPH_HS_H, SPH_HS_RHO, SPH_HS_POR2, SPH_HS_CSJ, SPH_HS_F2, SPH_HS_TS, SPH_HS_CSI, SPH_HS_F1,
+       SPH_HS_NCOL };
+enum { SPH_HY_ACCX = 0, SPH_HY_ACCY, SPH_HY_ACCZ, SPH_HY_DTENTR, SPH_HY_MAXSIG, SPH_HY_NRES };
+struct SphHydroParams
+{
+  int periodic, comoving, limiter, have_ts;
+  double box, boxhalf;
+  double hubble_a2, fac_mu, fac_vsic_fix;   // hydra.c:78-97 (1 when not comoving)
+  double visc, tbi, gamma;                  // All.ArtBulkViscConst, All.Timebase_interval, GAMMA
+};
+struct SphHydroStats
+{
+  long long targets, bad_hsml, bad_density, bad_pressure, stack_ovf, candidates, pairs;
+};
+// reads sph_vel_in, sph_h_in, sph_col_in, sph_ts_in (caller order); fills sph_hsrc and sph_hmax, compacts the targets and walks
+// once; writes sph_res [SPH_HY_NRES][targets] / sph_row in list order (nothing when a column held a bad value)
+int sph_hydro_run(ngravs_ctx *c, const SphHydroParams &hp, SphHydroStats *st);
 // list order -> rows of a strided device column
 int sph_scatter(ngravs_ctx *c, const double *src, long long nt, double *dst, long long stride);
 // ---- kernels_pm.hip

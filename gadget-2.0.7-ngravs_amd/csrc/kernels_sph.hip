@@ -14,6 +14,16 @@
 //      reference repeats globally because of its export loop; the trial h of a particle depend on that particle alone, so the
 //      per-lane iteration yields the same sequence.  A lane that was accepted drops out of the hull; the wave ends with its last.
 //      fp64 throughout, no atomics on results (a lane owns its target).
+//
+// SPH hydrodynamic forces, the second half of the gas side (hydra.c:50-346 for one task, hydro_evaluate hydra.c:353-555,
+// force_update_hmax forcetree.c:1134-1203, ngb_treefind_pairs ngb.c:64-185):
+// k_sph_hydro_prep : one thread per particle of the sorted set: the caller's columns of a type-0 row go to Peano order together with
+//      what hydro_evaluate derives from one particle alone (p/rho^2 times the dh/drho factor, both sound speeds, the Balsara
+//      factors f1 / f2, the timestep as a double); rows of other types get Hsml 0 and are not read.  Counts bad rows.
+// k_sph_hmax : per tree node the largest Hsml of the gas below it, bottom-up, one launch per level.
+// k_sph_hydro : the same wave-per-64-targets walk (sph_hull_walk below), ONE walk: a child is opened when its
+//      cube lies within max(largest h_i of the wave, hmax of the child) of the hull of the lanes' positions, the staged entry holds
+//      13 doubles, and every lane applies hydra.c:416-534 to every staged source.
 #include "engine.hpp"
 #include "walk_device.hpp"
 #include <hipcub/hipcub.hpp>
@@ -23,6 +33,8 @@
 #define SPH_STACK 256      // depth-first with eight children per pop: at most 7 * MAX_LEVELS + 1 = 155 pending nodes
 #define SPH_NLEAF 64       // a node with at most this many particles is staged whole (one chunk)
 static_assert(7 * MAX_LEVELS + 8 < SPH_STACK, "the LIFO must hold a depth-first walk of the deepest tree");
+#define SPH_HWAVES 2       // k_sph_hydro: waves per workgroup: 2 x 14.0 KB of LDS, five workgroups per CU
+#define SPH_HFIELDS 13     // doubles of a staged hydro source
 
 struct SphParams
 {
@@ -85,6 +97,115 @@ __device__ __forceinline__ void sph_block(const double (*__restrict__ s)[SPH_STA
             }
         }
     }
+}
+
+// The wave's depth-first walk of k_sph_density for a hull (centre hc, half sides hh) as a function of its own, for k_sph_hydro.
+// k_sph_density keeps its inline copy: called through this template (same arithmetic, same results) the compiler gives it 180
+// instead of 164 VGPRs, which costs the third wave per SIMD, and holding it to three waves spills.  A node is popped from the LDS
+// stack, lanes 0-7 test its eight children (cube against hull, nearest image in periodic runs, with the STORED side: a refit
+// tree's cells may have grown; widen(child) >= 0 is added to the hull's half sides for that child), an overlapping child with at
+// most SPH_NLEAF particles (or a bucket) hands its particle range over, a larger one is pushed.  The type-0 particles of a range
+// are compacted into the wave's staging block by put(slot, particle), and once more than 64 are staged block(count) runs every
+// lane over it.  Returns false when the LIFO would overflow (nothing is written past it).
+template <int STAGE, class Widen, class Put, class Block>
+__device__ __forceinline__ bool sph_hull_walk(const TreeView &tv, const double4 *__restrict__ pm, const unsigned char *__restrict__ type,
+                                              long long n, int periodic, double box, double boxhalf, double hcx, double hcy, double hcz,
+                                              double hhx, double hhy, double hhz, int *stack, int lane, Widen widen, Put put, Block block)
+{
+  static_assert(STAGE >= 128, "a chunk of 64 must fit behind 64 staged entries");
+  int top = 0, fill = 0;
+  if(lane == 0)
+    stack[0] = 0;   // the root is opened unconditionally
+  top = 1;
+  wave_sync();
+  while(top > 0)
+    {
+      const int node = __builtin_amdgcn_readfirstlane(stack[top - 1]);
+      top--;
+      wave_sync();   // the slot is read before a push below reuses it
+      // lanes 0-7: one child each
+      int kind = 0, first = 0, count = 0, ch = -1;   // kind 1: push the child node, 2: hand its particle range over
+      if(lane < 8)
+        {
+          ch = tv.child[8ll * node + lane];
+          double cx = 0, cy = 0, cz = 0, half = 0;
+          if(ch >= 0)
+            {
+              const double4 g = tv.geo[ch];
+              cx = g.x, cy = g.y, cz = g.z, half = 0.5 * g.w;
+            }
+          else if(ch <= -2)
+            {
+              const double4 p = pm[-2 - ch];
+              cx = p.x, cy = p.y, cz = p.z, half = 0;
+            }
+          if(ch != -1)
+            {
+              double dx = cx - hcx, dy = cy - hcy, dz = cz - hcz;
+              if(periodic)
+                {
+                  dx = nearest(dx, box, boxhalf);
+                  dy = nearest(dy, box, boxhalf);
+                  dz = nearest(dz, box, boxhalf);
+                }
+              const double wd = widen(ch);
+              // (ngb.c:146-177 for the hull instead of one particle's box)
+              if(fabs(dx) - half <= hhx + wd && fabs(dy) - half <= hhy + wd && fabs(dz) - half <= hhz + wd)
+                {
+                  if(ch >= 0)
+                    {
+                      first = tv.first[ch];
+                      count = tv.count[ch];
+                      kind = (count <= SPH_NLEAF || (tv.flags[ch] & FLAG_BUCKET)) ? 2 : 1;
+                    }
+                  else
+                    {
+                      first = -2 - ch;
+                      count = 1;
+                      kind = 2;
+                    }
+                }
+            }
+        }
+      const unsigned long long pmask = __ballot(kind == 1 ? 1 : 0);
+      const int npush = __popcll(pmask);
+      if(top + npush > SPH_STACK)   // cannot happen for a tree of at most MAX_LEVELS levels; never write past the LIFO
+        return false;
+      if(kind == 1)
+        stack[top + lane_prefix(pmask)] = ch;
+      top += npush;
+      unsigned long long rmask = __ballot(kind == 2 ? 1 : 0);
+      while(rmask)
+        {
+          const int l = __builtin_ctzll(rmask);
+          rmask &= rmask - 1;
+          const int f0 = __shfl(first, l), cn = __shfl(count, l);
+          for(int o = 0; o < cn; o += 64)
+            {
+              const long long p = (long long)f0 + o + lane;
+              const bool ok = o + lane < cn && p < n && type[p] == 0;   // P[p].Type > 0: not a neighbour (ngb.c:221)
+              const unsigned long long m = __ballot(ok ? 1 : 0);
+              if(ok)
+                put(fill + lane_prefix(m), p);
+              fill += __popcll(m);
+              if(fill > 64)
+                {
+                  wave_sync();
+                  block(fill);
+                  wave_sync();
+                  fill = 0;
+                }
+            }
+        }
+      wave_sync();   // pushes are visible before the next pop
+    }
+  if(fill > 0)
+    {
+      wave_sync();
+      block(fill);
+      wave_sync();
+    }
+  return true;
 }
 
 __global__ __launch_bounds__(64 * SPH_WAVES) void k_sph_density(TreeView tv, const double4 *__restrict__ pm, const unsigned char *__restrict__ type,
@@ -334,14 +455,14 @@ static TreeView sph_tree_view(ngravs_ctx *c)
   return tv;
 }
 
-int sph_density_run(ngravs_ctx *c, double des_num_ngb, double max_dev, double min_hsml, SphStats *st)
+// the targets: active type-0 rows in Peano order (density.c:95, :123; hydra.c:101-105), compacted into sph_tlist as the group
+// walk's list is; clears sph_counters
+static int sph_targets(ngravs_ctx *c, int *count)
 {
-  memset(st, 0, sizeof(*st));
   const int n = (int)c->n;
   if(c->sph_tlist.ensure((size_t)n) || c->sph_counters.ensure(SPH_C_COUNT + 1))
     return NGRAVS_ERR_NOMEM;
   HIP_TRY(c, hipMemsetAsync(c->sph_counters.p, 0, (SPH_C_COUNT + 1) * sizeof(unsigned long long), c->stream));
-  // the targets: active type-0 rows in Peano order (density.c:95, :123), compacted as the group walk's list is
   int *d_cnt = reinterpret_cast<int *>(c->sph_counters.p + SPH_C_COUNT);
   hipcub::CountingInputIterator<int> iota(0);
   SphIsTarget sel = {c->s_type.p, c->s_active.p};
@@ -350,9 +471,17 @@ int sph_density_run(ngravs_ctx *c, double des_num_ngb, double max_dev, double mi
   if(c->sph_tmp.ensure(bytes))
     return NGRAVS_ERR_NOMEM;
   HIP_TRY(c, hipcub::DeviceSelect::If(c->sph_tmp.p, bytes, iota, c->sph_tlist.p, d_cnt, n, sel, c->stream));
-  int cnt = 0;
-  HIP_TRY(c, hipMemcpyAsync(&cnt, d_cnt, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(count, d_cnt, sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return NGRAVS_OK;
+}
+
+int sph_density_run(ngravs_ctx *c, double des_num_ngb, double max_dev, double min_hsml, SphStats *st)
+{
+  memset(st, 0, sizeof(*st));
+  int cnt = 0;
+  if(int rc = sph_targets(c, &cnt))
+    return rc;
   st->targets = cnt;
   if(cnt == 0)
     return NGRAVS_OK;
@@ -382,6 +511,287 @@ int sph_density_run(ngravs_ctx *c, double des_num_ngb, double max_dev, double mi
   st->sum_rounds = (long long)h[SPH_C_SUMR];
   st->candidates = (long long)h[SPH_C_CAND];
   st->neighbours = (long long)h[SPH_C_NGB];
+  return NGRAVS_OK;
+}
+
+// ---- SPH hydro force --------------------------------------------------------------------------------------------------------
+// counters of a hydro call: type-0 rows with a bad Hsml / Density / Pressure, waves whose LIFO was full, candidates, pairs
+#define SPH_H_BADH 0
+#define SPH_H_BADRHO 1
+#define SPH_H_BADP 3
+
+__global__ void k_sph_hydro_prep(const unsigned char *__restrict__ type, const unsigned int *__restrict__ idx, long long n,
+                                 const double *__restrict__ vel_in, const double *__restrict__ h_in, const double *__restrict__ col_in,
+                                 const int *__restrict__ ts_in, SphHydroParams hp, double *__restrict__ hs,
+                                 unsigned long long *__restrict__ counters)
+{
+  const long long p = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+  if(p >= n)
+    return;
+  if(type[p] != 0)
+    {
+      hs[SPH_HS_H * n + p] = 0;   // no gas: nothing for hmax, never staged
+      return;
+    }
+  const long long row = idx[p];
+  const double BIG = 1e300;
+  const double h = h_in[row], rho = col_in[row], pressure = col_in[n + row], dhsml = col_in[2 * n + row];
+  const double adiv = fabs(col_in[3 * n + row]), curl = col_in[4 * n + row];
+  if(!(h > 0) || !(h < BIG))
+    atomicAdd(&counters[SPH_H_BADH], 1ull);
+  if(!(rho > 0) || !(rho < BIG))
+    atomicAdd(&counters[SPH_H_BADRHO], 1ull);
+  if(!(pressure >= 0) || !(pressure < BIG))
+    atomicAdd(&counters[SPH_H_BADP], 1ull);
+  const double por2 = pressure / (rho * rho);                 // hydra.c:441
+  const double cs_j = sqrt(hp.gamma * por2 * rho);            // hydra.c:442
+  const double cs_i = sqrt(hp.gamma * pressure / rho);        // hydra.c:379
+  hs[SPH_HS_VX * n + p] = vel_in[3 * row];
+  hs[SPH_HS_VY * n + p] = vel_in[3 * row + 1];
+  hs[SPH_HS_VZ * n + p] = vel_in[3 * row + 2];
+  hs[SPH_HS_H * n + p] = h;
+  hs[SPH_HS_RHO * n + p] = rho;
+  hs[SPH_HS_POR2 * n + p] = por2 * dhsml;                     // hydra.c:403, :524
+  hs[SPH_HS_CSJ * n + p] = cs_j;
+  hs[SPH_HS_F2 * n + p] = adiv / (adiv + curl + 0.0001 * cs_j / hp.fac_mu / h);   // hydra.c:504-506
+  hs[SPH_HS_TS * n + p] = hp.have_ts ? (double)ts_in[row] : 0.0;
+  hs[SPH_HS_CSI * n + p] = cs_i;
+  hs[SPH_HS_F1 * n + p] = adiv / (adiv + curl + 0.0001 * cs_i / h / hp.fac_mu);   // hydra.c:380-382
+}
+
+// force_update_hmax (forcetree.c:1134-1203, local part): the nodes of one level from their children, the levels bottom-up
+__global__ void k_sph_hmax(const int *__restrict__ n_child, const int *__restrict__ n_first, const int *__restrict__ n_count,
+                           const int *__restrict__ n_flags, const double *__restrict__ sh, long long n, int node0, int nnodes_level,
+                           double *__restrict__ hmax)
+{
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if(t >= nnodes_level)
+    return;
+  const int node = node0 + t;
+  double m = 0;
+  if(n_flags[node] & FLAG_BUCKET)
+    {
+      const long long f = n_first[node], cnt = n_count[node];
+      for(long long p = f; p < f + cnt && p < n; p++)
+        m = fmax(m, sh[p]);
+    }
+  else
+    for(int k = 0; k < 8; k++)
+      {
+        const int ch = n_child[8ll * node + k];
+        if(ch >= 0)
+          m = fmax(m, hmax[ch]);
+        else if(ch <= -2)
+          m = fmax(m, sh[-2 - ch]);
+      }
+  hmax[node] = m;
+}
+
+struct SphHydroLane
+{
+  double x, y, z, vx, vy, vz, mass;
+  double h2, hinv, hinv4, rho, por2, cs, f1, ts;
+  double ax, ay, az, dte, maxsig;
+  unsigned ncand, npair;
+};
+
+// every lane over the staged block (hydra.c:412-536)
+__device__ __forceinline__ void sph_hydro_block(const double (*__restrict__ s)[SPH_STAGE], int cnt, bool live, const SphHydroParams &hp,
+                                                SphHydroLane &L)
+{
+  if(live)
+    L.ncand += (unsigned)cnt;
+  for(int j = 0; j < cnt; j++)
+    {
+      double dx = L.x - s[0][j], dy = L.y - s[1][j], dz = L.z - s[2][j];
+      if(hp.periodic)
+        {
+          dx = nearest(dx, hp.box, hp.boxhalf);
+          dy = nearest(dy, hp.box, hp.boxhalf);
+          dz = nearest(dz, hp.box, hp.boxhalf);
+        }
+      const double r2 = dx * dx + dy * dy + dz * dz;
+      const double h_j = s[7][j], h_j2 = h_j * h_j;
+      if(live && (r2 < L.h2 || r2 < h_j2))
+        {
+          const double r = sqrt(r2);
+          if(r > 0)
+            {
+              L.npair++;
+              const double m_j = s[3][j], cs_j = s[10][j];
+              const double dvx = L.vx - s[4][j], dvy = L.vy - s[5][j], dvz = L.vz - s[6][j];
+              const double vdotr = dx * dvx + dy * dvy + dz * dvz;
+              const double vdotr2 = hp.comoving ? vdotr + hp.hubble_a2 * r2 : vdotr;
+              double dwk_i = 0, dwk_j = 0;
+              if(r2 < L.h2)
+                {
+                  const double u = r * L.hinv;
+                  dwk_i = u < 0.5 ? L.hinv4 * u * (SPH_KC3 * u - SPH_KC4) : L.hinv4 * SPH_KC6 * (1.0 - u) * (1.0 - u);
+                }
+              if(r2 < h_j2)
+                {
+                  const double hinv = 1.0 / h_j, hinv4 = hinv * hinv * hinv * hinv, u = r * hinv;
+                  dwk_j = u < 0.5 ? hinv4 * u * (SPH_KC3 * u - SPH_KC4) : hinv4 * SPH_KC6 * (1.0 - u) * (1.0 - u);
+                }
+              if(L.cs + cs_j > L.maxsig)
+                L.maxsig = L.cs + cs_j;
+              double visc = 0;
+              if(vdotr2 < 0)   // artificial viscosity
+                {
+                  const double mu_ij = hp.fac_mu * vdotr2 / r;   // negative
+                  const double vsig = L.cs + cs_j - 3 * mu_ij;
+                  if(vsig > L.maxsig)
+                    L.maxsig = vsig;
+                  const double rho_ij = 0.5 * (L.rho + s[8][j]);
+                  visc = 0.25 * hp.visc * vsig * (-mu_ij) / rho_ij * (L.f1 + s[11][j]);
+                  if(hp.limiter)   // the viscous acceleration must not be too large
+                    {
+                      const double dt = fmax(L.ts, s[12][j]) * hp.tbi;
+                      if(dt > 0 && (dwk_i + dwk_j) < 0)
+                        {
+                          const double lim = 0.5 * hp.fac_vsic_fix * vdotr2 / (0.5 * (L.mass + m_j) * (dwk_i + dwk_j) * r * dt);
+                          visc = visc < lim ? visc : lim;   // dmin
+                        }
+                    }
+                }
+              const double hfc_visc = 0.5 * m_j * visc * (dwk_i + dwk_j) / r;
+              const double hfc = hfc_visc + m_j * (L.por2 * dwk_i + s[9][j] * dwk_j) / r;
+              L.ax -= hfc * dx;
+              L.ay -= hfc * dy;
+              L.az -= hfc * dz;
+              L.dte += 0.5 * hfc_visc * vdotr2;
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(64 * SPH_HWAVES) void k_sph_hydro(TreeView tv, const double4 *__restrict__ pm, const unsigned char *__restrict__ type,
+                                                               const double *__restrict__ hs, const double *__restrict__ hmax,
+                                                               const unsigned int *__restrict__ idx, const int *__restrict__ tlist,
+                                                               long long nt, long long n, SphHydroParams hp, double *__restrict__ res,
+                                                               int *__restrict__ row, unsigned long long *__restrict__ counters)
+{
+  __shared__ double s_src[SPH_HWAVES][SPH_HFIELDS][SPH_STAGE];
+  __shared__ int s_stack[SPH_HWAVES][SPH_STACK];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const long long t = ((long long)blockIdx.x * SPH_HWAVES + w) * 64 + lane;
+  if(t - lane >= nt)   // the whole wave (no workgroup barrier anywhere below)
+    return;
+  double (*src)[SPH_STAGE] = s_src[w];
+  int *stack = s_stack[w];
+  const double BIG = 1e300;
+  const double *sh = hs + SPH_HS_H * n;
+
+  const bool live = t < nt;
+  SphHydroLane L = {};
+  double h = 0;
+  int myrow = 0;
+  if(live)
+    {
+      const int i = tlist[t];
+      const double4 p = pm[i];
+      L.x = p.x, L.y = p.y, L.z = p.z, L.mass = p.w;
+      L.vx = hs[SPH_HS_VX * n + i], L.vy = hs[SPH_HS_VY * n + i], L.vz = hs[SPH_HS_VZ * n + i];
+      h = sh[i];
+      L.h2 = h * h;
+      L.hinv = 1.0 / h;
+      L.hinv4 = L.hinv * L.hinv * L.hinv * L.hinv;
+      L.rho = hs[SPH_HS_RHO * n + i];
+      L.por2 = hs[SPH_HS_POR2 * n + i];
+      L.cs = hs[SPH_HS_CSI * n + i];
+      L.f1 = hs[SPH_HS_F1 * n + i];
+      L.ts = hs[SPH_HS_TS * n + i];
+      myrow = (int)idx[i];
+    }
+  // the hull of the lanes' positions; a child is tested against it widened by max(largest h_i, hmax of the child) (ngb.c:146-177)
+  const double lx = wave_min(live ? L.x : BIG), ly = wave_min(live ? L.y : BIG), lz = wave_min(live ? L.z : BIG);
+  const double ux = wave_max(live ? L.x : -BIG), uy = wave_max(live ? L.y : -BIG), uz = wave_max(live ? L.z : -BIG);
+  const double hw = wave_uniform(wave_max(live ? h : 0.0));
+  const double hcx = wave_uniform(0.5 * (lx + ux)), hcy = wave_uniform(0.5 * (ly + uy)), hcz = wave_uniform(0.5 * (lz + uz));
+  const double hhx = wave_uniform(0.5 * (ux - lx) * (1 + 1e-12)), hhy = wave_uniform(0.5 * (uy - ly) * (1 + 1e-12)),
+               hhz = wave_uniform(0.5 * (uz - lz) * (1 + 1e-12));
+  const bool ok = sph_hull_walk<SPH_STAGE>(
+    tv, pm, type, n, hp.periodic, hp.box, hp.boxhalf, hcx, hcy, hcz, hhx, hhy, hhz, stack, lane,
+    [&](int ch) { return fmax(hw, ch >= 0 ? hmax[ch] : sh[-2 - ch]) * (1 + 1e-12); },
+    [&](int q, long long p) {
+      const double4 pp = pm[p];
+      src[0][q] = pp.x, src[1][q] = pp.y, src[2][q] = pp.z, src[3][q] = pp.w;
+      src[4][q] = hs[SPH_HS_VX * n + p], src[5][q] = hs[SPH_HS_VY * n + p], src[6][q] = hs[SPH_HS_VZ * n + p];
+      src[7][q] = hs[SPH_HS_H * n + p], src[8][q] = hs[SPH_HS_RHO * n + p], src[9][q] = hs[SPH_HS_POR2 * n + p];
+      src[10][q] = hs[SPH_HS_CSJ * n + p], src[11][q] = hs[SPH_HS_F2 * n + p], src[12][q] = hs[SPH_HS_TS * n + p];
+    },
+    [&](int cnt) { sph_hydro_block(src, cnt, live, hp, L); });
+  if(live && ok)
+    {
+      // final operations (hydra.c:320)
+      const double gm1 = hp.gamma - 1;
+      res[SPH_HY_ACCX * nt + t] = L.ax;
+      res[SPH_HY_ACCY * nt + t] = L.ay;
+      res[SPH_HY_ACCZ * nt + t] = L.az;
+      res[SPH_HY_DTENTR * nt + t] = L.dte * (gm1 / (hp.hubble_a2 * pow(L.rho, gm1)));
+      res[SPH_HY_MAXSIG * nt + t] = L.maxsig;
+      row[t] = myrow;
+    }
+  unsigned long long cand = L.ncand, pairs = L.npair;
+  for(int off = 32; off > 0; off >>= 1)
+    {
+      cand += __shfl_xor(cand, off);
+      pairs += __shfl_xor(pairs, off);
+    }
+  if(lane == 0)
+    {
+      atomicAdd(&counters[SPH_C_CAND], cand);
+      atomicAdd(&counters[SPH_C_NGB], pairs);
+      if(!ok)
+        atomicAdd(&counters[SPH_C_OVF], 1ull);
+    }
+}
+
+int sph_hydro_run(ngravs_ctx *c, const SphHydroParams &hp, SphHydroStats *st)
+{
+  memset(st, 0, sizeof(*st));
+  const long long n = c->n;
+  if(c->sph_hsrc.ensure((size_t)SPH_HS_NCOL * n) || c->sph_hmax.ensure((size_t)c->nnodes))
+    return NGRAVS_ERR_NOMEM;
+  int cnt = 0;
+  if(int rc = sph_targets(c, &cnt))   // (clears the counters)
+    return rc;
+  st->targets = cnt;
+  if(cnt == 0)
+    return NGRAVS_OK;
+  const long long nt = cnt;
+  if(c->sph_res.ensure((size_t)SPH_HY_NRES * nt) || c->sph_row.ensure((size_t)nt))
+    return NGRAVS_ERR_NOMEM;
+  hipLaunchKernelGGL(k_sph_hydro_prep, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->s_type.p, c->s_idx.p, n, c->sph_vel_in.p,
+                     c->sph_h_in.p, c->sph_col_in.p, c->sph_ts_in.p, hp, c->sph_hsrc.p, c->sph_counters.p);
+  HIP_TRY(c, hipGetLastError());
+  unsigned long long h[SPH_C_COUNT];
+  HIP_TRY(c, hipMemcpyAsync(h, c->sph_counters.p, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  st->bad_hsml = (long long)h[SPH_H_BADH];
+  st->bad_density = (long long)h[SPH_H_BADRHO];
+  st->bad_pressure = (long long)h[SPH_H_BADP];
+  if(st->bad_hsml || st->bad_density || st->bad_pressure)
+    return NGRAVS_OK;   // the caller refuses; nothing is walked with such a column
+  for(int l = c->nlevels - 1; l >= 0; l--)
+    {
+      const long long l0 = c->level_start[l], lc = c->level_start[l + 1] - l0;
+      if(lc <= 0)
+        continue;
+      hipLaunchKernelGGL(k_sph_hmax, dim3((unsigned)((lc + 127) / 128)), dim3(128), 0, c->stream, c->n_child.p, c->n_first.p, c->n_count.p,
+                         c->n_flags.p, c->sph_hsrc.p + SPH_HS_H * n, n, (int)l0, (int)lc, c->sph_hmax.p);
+    }
+  HIP_TRY(c, hipGetLastError());
+  const long long nwaves = (nt + 63) / 64;
+  const unsigned nb = (unsigned)((nwaves + SPH_HWAVES - 1) / SPH_HWAVES);
+  hipLaunchKernelGGL(k_sph_hydro, dim3(nb), dim3(64 * SPH_HWAVES), 0, c->stream, sph_tree_view(c), c->s_pm.p, c->s_type.p, c->sph_hsrc.p,
+                     c->sph_hmax.p, c->s_idx.p, c->sph_tlist.p, nt, n, hp, c->sph_res.p, c->sph_row.p, c->sph_counters.p);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(h, c->sph_counters.p, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  st->stack_ovf = (long long)h[SPH_C_OVF];
+  st->candidates = (long long)h[SPH_C_CAND];
+  st->pairs = (long long)h[SPH_C_NGB];
   return NGRAVS_OK;
 }
 

@@ -262,7 +262,8 @@ int ngravs_get_config(ngravs_ctx *ctx, ngravs_config_t *out);
  *   "sort_full" 1: Peano order by one radix sort on all key bits (default: top 28 to 42 bits + fix-up of the ties, the same order)
  *   "dd_keep" f: decompositions are kept over several steps (ngravs_host_kept_step): leaves are imported for ALL own particles as
  *       targets, whose cells may have grown by f x the domain's side (0 <= f <= 0.25; default 0: import for this step's active targets)
- *   "sph_verbose" 1: the SPH density call prints one line of iteration statistics (targets, rounds, candidates, neighbours) to stdout
+ *   "sph_verbose" 1: the SPH density call prints one line of iteration statistics (targets, rounds, candidates, neighbours) to stdout,
+ *       the SPH hydro call one line (targets, candidates tested, pairs evaluated)
  * Returns NGRAVS_ERR_ARG for an unknown name or a value out of range. */
 int ngravs_set_tuning(ngravs_ctx *ctx, const char *name, double value);
 /* Plain copies for hosts that do not link HIP themselves (a C/MPI host staging exchange buffers through host memory):
@@ -502,7 +503,7 @@ int ngravs_pm_slab_bytes(ngravs_ctx *ctx, double bytes[4]);
  * first.  The tree, the walk's state and the stored accelerations are not modified.  NGRAVS_ERR_ARG with a message: NULL in /
  * hsml / vel_pred, des_num_ngb <= 0, a negative deviation or minimum, a target whose hsml is <= 0 or NaN.  NGRAVS_ERR_STATE,
  * "single task only": world_size > 1 or a multi-task working set.  No type-0 target: success, nothing written, 0 rounds.
- * Not provided: hydro forces (hydra.c), TWODIMS, LONG_X/Y/Z. */
+ * Not provided: several tasks, TWODIMS, LONG_X/Y/Z (hydro forces: ngravs_sph_hydro below). */
 typedef struct {
   const double *vel_pred; int64_t vel_stride;   /* SphP[].VelPred[3] per own row (rows of other types are not read)      */
   double *hsml;           int64_t hsml_stride;  /* in: starting guess per own row (> 0 for every target), out: result    */
@@ -519,6 +520,43 @@ int ngravs_sph_density(ngravs_ctx *ctx, const ngravs_sph_in_t *in, const ngravs_
 /* GPU-free: the spline and its derivative as the device code evaluates them, wk[i], dwk[i] at r[i] for smoothing length h
  * (0 where r >= h) */
 int ngravs_sph_kernel(double h, const double *r, int64_t n, double *wk, double *dwk);
+
+/* ---- SPH hydro force: hydro_force() (hydra.c:50-346) for ONE task -----------------------------------------------------------------
+ * The second half of the gas side of compute_accelerations(): after ngravs_sph_density and the host's pressure line, HydroAccel,
+ * DtEntropy and MaxSignalVel of every target (own active type-0 row) from hydro_evaluate (hydra.c:353-555) over the symmetric
+ * neighbour set r < h_i or r < h_j (ngb_treefind_pairs, ngb.c:64-185; the tree nodes' hmax, forcetree.c:1134-1203, is recomputed
+ * from the hsml column on every call and kept apart from what gravity reads), nearest image in periodic runs, with the final
+ * operation DtEntropy *= (gamma - 1) / (hubble_a2 Density^(gamma - 1)) (hydra.c:320).  One walk, no iteration.
+ * The columns are read for EVERY own type-0 row (every gas particle is a source), rows of other types are not read.  timestep is
+ * Ti_endstep - Ti_begstep per row (NULL: all 0, which switches the viscosity limiter off through dt > 0, as at the reference's
+ * first step).  What the reference fixes at compile time is an input: gamma (5/3; 1 is ISOTHERM_EQS), viscosity_limiter (1; 0 is
+ * NOVISCOSITYLIMITER).  comoving != 0: the caller passes hubble_a2, fac_mu, fac_vsic_fix as hydra.c:78-97 gives them; otherwise
+ * the three are taken as 1 whatever was passed.
+ * Needs a built tree of the current particle set (NGRAVS_ERR_STATE otherwise); after ngravs_update_particles the tree is refit
+ * first.  The tree, the walk's state and the stored accelerations are not modified.  NGRAVS_ERR_ARG with a message: NULL in or
+ * a NULL column other than timestep, gamma < 1, a negative constant, a type-0 row whose hsml or density is <= 0 or not finite or
+ * whose pressure is < 0 or not finite (the message names the column; nothing is written).  NGRAVS_ERR_STATE, "single task only":
+ * world_size > 1 or a multi-task working set.  No type-0 target: success, nothing written.
+ * Not provided: several tasks, TWODIMS, LONG_X/Y/Z, SPH_BND_PARTICLES; there is no neighbour list, hence no MAX_NGB second loop. */
+typedef struct {   /* strides in bytes; rows = own rows */
+  const double *vel_pred;     int64_t vel_pred_stride;      /* SphP[].VelPred[3]                                            */
+  const double *hsml;         int64_t hsml_stride;          /* SphP[].Hsml                                                  */
+  const double *density;      int64_t density_stride;       /* SphP[].Density                                               */
+  const double *pressure;     int64_t pressure_stride;      /* SphP[].Pressure                                              */
+  const double *dhsml_factor; int64_t dhsml_factor_stride;  /* SphP[].DhsmlDensityFactor                                    */
+  const double *div_vel;      int64_t div_vel_stride;       /* SphP[].DivVel                                                */
+  const double *curl_vel;     int64_t curl_vel_stride;      /* SphP[].CurlVel                                               */
+  const int32_t *timestep;    int64_t timestep_stride;      /* P[].Ti_endstep - P[].Ti_begstep, or NULL                     */
+  double art_bulk_visc_const, timebase_interval, gamma;     /* All.ArtBulkViscConst, All.Timebase_interval, GAMMA           */
+  double hubble_a2, fac_mu, fac_vsic_fix;                   /* hydra.c:78-97, read when comoving != 0                       */
+  int32_t viscosity_limiter, comoving, on_device, reserved;
+} ngravs_hydro_in_t;
+typedef struct {   /* any pointer may be NULL; strides in bytes; rows = own rows, only targets are written */
+  double *hydro_accel, *dt_entropy, *max_signal_vel;   /* SphP[].HydroAccel[3], DtEntropy, MaxSignalVel */
+  int64_t hydro_accel_stride, dt_entropy_stride, max_signal_vel_stride;
+} ngravs_hydro_out_t;
+/* kernel_ms may be NULL: device time of the call (HIP events) */
+int ngravs_sph_hydro(ngravs_ctx *ctx, const ngravs_hydro_in_t *in, const ngravs_hydro_out_t *out, double *kernel_ms);
 
 #ifdef __cplusplus
 }
