@@ -3,9 +3,10 @@
  * Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may load this library.
  * Nothing under gadget-2.0.7-ngravs_amd/ links, imports or calls it.
  *
- * PINNING (see DESIGN.md "Oracle"): the reference itself cannot be built in this image without
- * writing stand-ins for GSL and FFTW-2 headers/libraries (allvars.h:20, ngravs.h:3-11), which
- * this build's rules forbid, so there is no oracle/_ref.  The restatement is pinned by
+ * PINNING (see DESIGN.md "Oracle"): the reference's gravity path cannot be built in this image
+ * (TreePM needs a real FFTW-2, the drift tables GSL; allvars.h:20, ngravs.h:3-11), so no reference
+ * output pins it; oracle/_ref holds the reference's SPH path only (Makefile, target ref), which
+ * this library has no part in.  The restatement is pinned by
  *   - the Peano-Hilbert known answers recorded from the reference in SURVEY.md 8(c),
  *   - the reference's recorded tree statistics on its own shipped IC GalaxyCollision.IC
  *     (29 325 nodes, 176 top leaves, 1178.53 / 598.546 interactions per particle)

@@ -1,8 +1,9 @@
 """SPH density and smoothing lengths (ngravs_sph_density, csrc/kernels_sph.hip) against a numpy restatement of the reference.
 
-The oracle cannot be extended and the reference does not build without GSL / FFTW-2, so the truth is restated here by hand from
-density.c / ngb.c (line citations below): brute-force O(N^2) pair sums in chunks (distances of a chunk of targets to ALL gas
-particles, then the pairs with r2 < h2 exactly as density.c:531), and the iteration rules of density.c:314-389 applied per particle.
+The truth is restated here by hand from density.c / ngb.c (line citations below): brute-force O(N^2) pair sums in chunks
+(distances of a chunk of targets to ALL gas particles, then the pairs with r2 < h2 exactly as density.c:531), and the iteration
+rules of density.c:314-389 applied per particle.  The restatement itself, and the device directly, are held to the reference's
+own output in tests/test_sph_reference.py (the reference's SPH path builds for one task: oracle/_ref/).
 
 Tolerance: the device sums differ from numpy's by summation order (and fused multiply-adds) only: TOL = 1e-11 relative, the
 project's figure for kernels against the oracle; DivVel / CurlVel are measured against sum|terms| / rho, not against the result

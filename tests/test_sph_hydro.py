@@ -1,9 +1,10 @@
 """SPH hydro force (ngravs_sph_hydro, csrc/kernels_sph.hip) against a numpy restatement of the reference's hydro_evaluate.
 
-The oracle cannot be extended and the reference does not build without GSL / FFTW-2, so the truth is restated here by hand from
-hydra.c (line citations below): brute-force all pairs in chunks, membership r2 < h_i^2 | r2 < h_j^2 (hydra.c:436), every branch a
-np.where.  The restatement is itself checked on the CPU against a plain double loop over pairs written straight from
-hydro_evaluate (test_restatement_against_a_plain_double_loop).
+The truth is restated here by hand from hydra.c (line citations below): brute-force all pairs in chunks, membership
+r2 < h_i^2 | r2 < h_j^2 (hydra.c:436), every branch a np.where.  The restatement is itself checked on the CPU against a plain
+double loop over pairs written straight from hydro_evaluate (test_restatement_against_a_plain_double_loop), and, like the device
+directly, against the reference's own output in tests/test_sph_reference.py (the reference's SPH path builds for one task:
+oracle/_ref/).
 
 Inputs: hsml, density, dhsml_factor, div_vel, curl_vel come from the density restatement of tests/test_sph_density.py on the CPU, so
 nothing here rests on the device's density (except the 2^20 chain, which is fed with the device's density on both sides).
