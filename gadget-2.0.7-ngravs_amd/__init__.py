@@ -41,7 +41,7 @@ EXPORTS = [
     "ngravs_dd_leaf_sums_kept", "ngravs_dd_pack_leaves_kept", "ngravs_dd_refresh_halo", "ngravs_dd_update_top", "ngravs_dd_get_kept",
     "ngravs_dd_set_ids", "ngravs_dd_get_ids",
     "ngravs_pm_slab_begin", "ngravs_pm_slab_pack", "ngravs_pm_slab_unpack", "ngravs_pm_slab_bytes",
-    "ngravs_sph_density", "ngravs_sph_kernel", "ngravs_sph_hydro",
+    "ngravs_sph_density", "ngravs_sph_kernel", "ngravs_sph_hydro", "ngravs_sph_accelerations",
 ]
 # include/ngravs_host.h (plain-C multi-task drivers over a communicator vtable, linked into the same library)
 HOST_EXPORTS = ["ngravs_host_comm_selftest", "ngravs_host_kept_step", "ngravs_host_toptree_borrow", "ngravs_host_domain_decomposition", "ngravs_host_domain_owners", "ngravs_host_domain_halo",
@@ -131,6 +131,7 @@ def lib():
         L.ngravs_sph_density.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ngravs_sph_kernel.argtypes = [C.c_double, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         L.ngravs_sph_hydro.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ngravs_sph_accelerations.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -521,6 +522,60 @@ class Engine:
         ms = C.c_double(0)
         self._check(lib().ngravs_sph_hydro(self._h, C.byref(hi), C.byref(ho), C.byref(ms)), "ngravs_sph_hydro")
         res["kernel_ms"] = float(ms.value)
+        return res
+
+    def sph_accelerations(self, vel, entropy, hsml, density, pressure, dhsml_factor, div_vel, curl_vel, *, dt_entropy=None,
+                          ti_begstep=None, ti_endstep=None, ti_current=0, timebase_interval=0.0, des_num_ngb, max_num_ngb_deviation,
+                          min_gas_hsml=0.0, art_bulk_visc_const, gamma=5.0 / 3, viscosity_limiter=True, comoving=None, out=None):
+        """The gas side of compute_accelerations() for one task in one call that stays on the device: density() with its pressure
+        line (density.c:305-308), force_update_hmax(), hydro_force().  vel = SphP[].VelPred[N,3], entropy = SphP[].Entropy [N],
+        dt_entropy = SphP[].DtEntropy of the step before or None (0), ti_begstep / ti_endstep int32 [N] or both None (dt_entr and
+        every timestep 0); one row per particle of the last hand-over.  hsml, density, pressure, dhsml_factor, div_vel, curl_vel
+        [N] are SphP[] as the reference holds it and are UPDATED IN PLACE: read for gas rows that are no targets, overwritten for
+        the targets (a target's hsml is its starting guess).  numpy float64 C-contiguous arrays, or torch tensors on the device
+        (float64 / int32, contiguous: no copy through the host).  comoving: None, or hydro_factors(...).  Returns a dict: num_ngb,
+        hydro_accel [N,3], dt_entropy_out, max_signal_vel (rows that are no targets: 0 -- or what `out`, a dict of arrays of the
+        same kind, held), max_rounds, kernel_ms (density walk, pressure line + hydro sources + hmax, hydro walk)."""
+        ins = dict(vel_pred=vel, entropy=entropy, dt_entropy=dt_entropy, ti_begstep=ti_begstep, ti_endstep=ti_endstep)
+        inout = dict(hsml=hsml, density=density, pressure=pressure, dhsml_factor=dhsml_factor, div_vel=div_vel, curl_vel=curl_vel)
+        on_device = not isinstance(vel, np.ndarray) and hasattr(vel, "data_ptr")
+        shape = lambda k: (self.n, 3) if k in ("vel_pred", "hydro_accel") else (self.n,)   # noqa: E731
+        res = {}
+        if on_device:
+            import torch
+            f64, i32 = torch.float64, torch.int32
+            ok = lambda a, t: a.dtype == t and a.is_contiguous() and a.is_cuda   # noqa: E731
+            for k in abi.GAS_OUT_NAMES:
+                res[k] = out[k] if out and k in out else torch.zeros(shape(k), dtype=f64, device=vel.device)
+            addr = lambda a: a.data_ptr()   # noqa: E731
+            torch.cuda.synchronize()   # the library works on a stream of its own: the tensors above must be complete
+        else:
+            f64, i32 = np.float64, np.int32
+            ok = lambda a, t: isinstance(a, np.ndarray) and a.dtype == t and a.flags.c_contiguous   # noqa: E731
+            ins = {k: a if a is None else np.ascontiguousarray(a, dtype=i32 if k.startswith("ti_") else f64) for k, a in ins.items()}
+            for k in abi.GAS_OUT_NAMES:
+                res[k] = out[k] if out and k in out else np.zeros(shape(k))
+            addr = lambda a: a.ctypes.data   # noqa: E731
+        for k, a in list(ins.items()) + list(inout.items()) + list(res.items()):
+            # (the in/out columns are written through: they must be the caller's own arrays, never converted copies)
+            assert a is None or (ok(a, i32 if k.startswith("ti_") else f64) and tuple(a.shape) == shape(k)), k
+        gi, go = abi.GasIn(), abi.GasOut()
+        for k, a in list(ins.items()) + list(inout.items()):
+            if a is not None:
+                setattr(gi, k, addr(a))
+                setattr(gi, k + "_stride", 24 if k == "vel_pred" else 4 if k.startswith("ti_") else 8)
+        gi.des_num_ngb, gi.max_num_ngb_deviation, gi.min_gas_hsml = float(des_num_ngb), float(max_num_ngb_deviation), float(min_gas_hsml)
+        gi.art_bulk_visc_const, gi.timebase_interval, gi.gamma = float(art_bulk_visc_const), float(timebase_interval), float(gamma)
+        gi.ti_current, gi.viscosity_limiter, gi.on_device = int(ti_current), int(bool(viscosity_limiter)), int(on_device)
+        if comoving is not None:
+            gi.comoving = 1
+            gi.hubble_a2, gi.fac_mu, gi.fac_vsic_fix = (float(x) for x in comoving)
+        for k in abi.GAS_OUT_NAMES:
+            setattr(go, k, addr(res[k]))
+            setattr(go, k + "_stride", 24 if k == "hydro_accel" else 8)
+        rounds, ms = C.c_int32(0), (C.c_double * 3)()
+        self._check(lib().ngravs_sph_accelerations(self._h, C.byref(gi), C.byref(go), C.byref(rounds), ms), "ngravs_sph_accelerations")
+        res["max_rounds"], res["kernel_ms"] = int(rounds.value), [float(x) for x in ms]
         return res
 
     def stats(self):

@@ -151,6 +151,26 @@ class HydroOut(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in HYDRO_OUT_NAMES] + [(k + "_stride", C.c_int64) for k in HYDRO_OUT_NAMES]
 
 
+GAS_IN_NAMES = ("vel_pred", "entropy", "dt_entropy", "ti_begstep", "ti_endstep")
+GAS_INOUT_NAMES = ("hsml", "density", "pressure", "dhsml_factor", "div_vel", "curl_vel")
+GAS_OUT_NAMES = ("num_ngb", "hydro_accel", "dt_entropy_out", "max_signal_vel")
+
+
+class GasIn(C.Structure):
+    """ngravs_gas_in_t"""
+    _fields_ = [f for k in GAS_IN_NAMES + GAS_INOUT_NAMES for f in ((k, C.c_void_p), (k + "_stride", C.c_int64))] + [
+        ("des_num_ngb", C.c_double), ("max_num_ngb_deviation", C.c_double), ("min_gas_hsml", C.c_double),
+        ("art_bulk_visc_const", C.c_double), ("timebase_interval", C.c_double), ("gamma", C.c_double),
+        ("hubble_a2", C.c_double), ("fac_mu", C.c_double), ("fac_vsic_fix", C.c_double),
+        ("ti_current", C.c_int32), ("viscosity_limiter", C.c_int32), ("comoving", C.c_int32), ("on_device", C.c_int32),
+    ]
+
+
+class GasOut(C.Structure):
+    """ngravs_gas_out_t"""
+    _fields_ = [(k, C.c_void_p) for k in GAS_OUT_NAMES] + [(k + "_stride", C.c_int64) for k in GAS_OUT_NAMES]
+
+
 def make_config(n_gravs=1, periodic=0, pmgrid=0, box_size=0.0, G=1.0, theta=0.5, err_tol_force_acc=0.005,
                 softening=None, type_to_grav=None, wiring="newton", yukawa_imass=60.0, walk_mode=WALK_STRICT,
                 tree_alloc_factor=0.0, device=0, rank=0, world_size=1, group_reach=0.0):

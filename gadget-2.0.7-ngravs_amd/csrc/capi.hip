@@ -415,6 +415,9 @@ extern "C" void ngravs_destroy(ngravs_ctx *c)
   c->sph_ts_in.release();
   c->sph_hsrc.release();
   c->sph_hmax.release();
+  c->sph_gas_in.release();
+  c->sph_ti_in.release();
+  c->sph_tpos.release();
   (void)hipEventDestroy(c->ev0);
   (void)hipEventDestroy(c->ev1);
   (void)hipEventDestroy(c->evk0);
@@ -2106,6 +2109,153 @@ extern "C" int ngravs_sph_hydro(ngravs_ctx *c, const ngravs_hydro_in_t *in, cons
   const int64_t stride[SPH_HY_NRES] = {out->hydro_accel_stride, out->hydro_accel_stride, out->hydro_accel_stride, out->dt_entropy_stride,
                                        out->max_signal_vel_stride};
   return sph_write_targets(c, SPH_HY_NRES, nt, dst, stride, in->on_device);
+}
+
+// ---- the gas side in one call: density() with its pressure line, force_update_hmax(), hydro_force() (kernels_sph.hip) ---------------
+static_assert(sizeof(ngravs_gas_in_t) == 264 && sizeof(ngravs_gas_out_t) == 64, "the Python mirror (abi.GasIn / GasOut) assumes this layout");
+extern "C" int ngravs_sph_accelerations(ngravs_ctx *c, const ngravs_gas_in_t *in, const ngravs_gas_out_t *out, int32_t *max_rounds,
+                                        double *kernel_ms)
+{
+  if(!c)
+    return NGRAVS_ERR_ARG;
+  auto refuse = [&](int code, const char *why) {
+    ngravs_report(c, code, std::string("ngravs_sph_accelerations: ") + why);
+    return code;
+  };
+  if(!in || !in->vel_pred || !in->entropy || !in->hsml || !in->density || !in->pressure || !in->dhsml_factor || !in->div_vel || !in->curl_vel)
+    return refuse(NGRAVS_ERR_ARG, "in and its vel_pred, entropy, hsml, density, pressure, dhsml_factor, div_vel, curl_vel must not be NULL");
+  if(!in->ti_begstep != !in->ti_endstep)
+    return refuse(NGRAVS_ERR_ARG, "ti_begstep and ti_endstep must both be given or both be NULL");
+  if(!(in->des_num_ngb > 0) || !(in->max_num_ngb_deviation >= 0) || !(in->min_gas_hsml >= 0))
+    return refuse(NGRAVS_ERR_ARG, "des_num_ngb must be > 0, max_num_ngb_deviation and min_gas_hsml >= 0");
+  if(!(in->gamma >= 1) || !(in->art_bulk_visc_const >= 0) || !(in->timebase_interval >= 0))
+    return refuse(NGRAVS_ERR_ARG, "gamma must be >= 1, art_bulk_visc_const and timebase_interval >= 0");
+  if(in->comoving && (!(in->hubble_a2 > 0) || !(in->fac_mu > 0) || !(in->fac_vsic_fix > 0)))
+    return refuse(NGRAVS_ERR_ARG, "comoving: hubble_a2, fac_mu and fac_vsic_fix must be > 0");
+  int rc;
+  if((rc = sph_ready(c, refuse)))
+    return rc;
+  if(max_rounds)
+    *max_rounds = 0;
+  if(kernel_ms)
+    kernel_ms[0] = kernel_ms[1] = kernel_ms[2] = 0;
+  const int64_t n = c->n_local;
+  if(n == 0 || c->nnodes <= 0)
+    return NGRAVS_OK;
+  if(c->sph_vel_in.ensure(3 * n) || c->sph_h_in.ensure(n) || c->sph_vel.ensure(3 * n) || c->sph_col_in.ensure(5 * n) ||
+     c->sph_gas_in.ensure(2 * n) || c->sph_ti_in.ensure(2 * n))
+    return refuse(NGRAVS_ERR_NOMEM, "device allocation failed");
+  if((rc = upload_column_f64(c, in->vel_pred, in->vel_pred_stride, 3, n, in->on_device, c->sph_vel_in.p)))
+    return rc;
+  if((rc = upload_column_f64(c, in->hsml, in->hsml_stride, 1, n, in->on_device, c->sph_h_in.p)))
+    return rc;
+  const double *col[5] = {in->density, in->pressure, in->dhsml_factor, in->div_vel, in->curl_vel};
+  const int64_t cstride[5] = {in->density_stride, in->pressure_stride, in->dhsml_factor_stride, in->div_vel_stride, in->curl_vel_stride};
+  for(int k = 0; k < 5; k++)
+    if((rc = upload_column_f64(c, col[k], cstride[k], 1, n, in->on_device, c->sph_col_in.p + k * n)))
+      return rc;
+  if((rc = upload_column_f64(c, in->entropy, in->entropy_stride, 1, n, in->on_device, c->sph_gas_in.p)))
+    return rc;
+  if(in->dt_entropy && (rc = upload_column_f64(c, in->dt_entropy, in->dt_entropy_stride, 1, n, in->on_device, c->sph_gas_in.p + n)))
+    return rc;
+  if(in->ti_begstep && ((rc = upload_column_i32(c, in->ti_begstep, in->ti_begstep_stride, n, in->on_device, c->sph_ti_in.p)) ||
+                        (rc = upload_column_i32(c, in->ti_endstep, in->ti_endstep_stride, n, in->on_device, c->sph_ti_in.p + n))))
+    return rc;
+  SphGasParams gp;
+  gp.des = in->des_num_ngb;
+  gp.dev = in->max_num_ngb_deviation;
+  gp.minh = in->min_gas_hsml;
+  gp.ti_current = in->ti_current;
+  gp.have_dte = in->dt_entropy != nullptr;
+  SphHydroParams hp;
+  hp.periodic = c->cfg.periodic;
+  hp.box = c->cfg.box_size;
+  hp.boxhalf = 0.5 * c->cfg.box_size;
+  hp.comoving = in->comoving != 0;
+  hp.limiter = in->viscosity_limiter != 0;
+  hp.have_ts = in->ti_begstep != nullptr;
+  hp.hubble_a2 = hp.comoving ? in->hubble_a2 : 1.0;   // hydra.c:96-97
+  hp.fac_mu = hp.comoving ? in->fac_mu : 1.0;
+  hp.fac_vsic_fix = hp.comoving ? in->fac_vsic_fix : 1.0;
+  hp.visc = in->art_bulk_visc_const;
+  hp.tbi = in->timebase_interval;
+  hp.gamma = in->gamma;
+  HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
+  HIP_TRY(c, hipEventRecord(c->ev1, c->stream));    // (recorded again where the stages end: a call that ends early reads 0)
+  HIP_TRY(c, hipEventRecord(c->evk0, c->stream));
+  hipLaunchKernelGGL(k_permute_f64, GRID1(n), 0, c->stream, c->s_idx.p, (long long)n, 3, c->sph_vel_in.p, c->sph_vel.p);
+  SphStats ds;
+  SphHydroStats hs;
+  if((rc = sph_gas_run(c, gp, hp, &ds, &hs, c->ev1, c->evk0)))
+    return rc;
+  HIP_TRY(c, hipEventRecord(c->evk1, c->stream));
+  HIP_TRY(c, hipEventSynchronize(c->evk1));
+  const bool density_only = ds.bad_hsml || ds.stack_ovf || ds.failed;
+  if(kernel_ms && ds.targets > 0)
+    {
+      float ms[3] = {0, 0, 0};
+      (void)hipEventElapsedTime(&ms[0], c->ev0, c->ev1);
+      if(!density_only)
+        {
+          (void)hipEventElapsedTime(&ms[1], c->ev1, c->evk0);
+          (void)hipEventElapsedTime(&ms[2], c->evk0, c->evk1);
+        }
+      for(int k = 0; k < 3; k++)
+        kernel_ms[k] = ms[k];
+    }
+  if(c->tune.sph_verbose && ds.targets > 0)
+    printf("ngravs_sph_density: %lld targets, rounds mean %.3f max %lld, %lld candidates tested, %lld neighbours\n", ds.targets,
+           (double)ds.sum_rounds / (double)ds.targets, ds.max_rounds, ds.candidates, ds.neighbours);
+  if(ds.bad_hsml)
+    return refuse(NGRAVS_ERR_ARG, "a target's starting hsml is <= 0 or not finite");
+  if(ds.stack_ovf)
+    return refuse(NGRAVS_ERR_TREE, "the tree is deeper than the walk's stack");
+  if(ds.failed)
+    {
+      ngravs_report(c, 1155, "failed to converge in neighbour iteration in density()");   // density.c:416-421
+      return NGRAVS_ERR_STATE;
+    }
+  if(hs.bad_hsml)
+    return refuse(NGRAVS_ERR_ARG, "a type-0 row's hsml is <= 0 or not finite");
+  if(hs.bad_density)
+    return refuse(NGRAVS_ERR_ARG, "a type-0 row's density is <= 0 or not finite");
+  if(hs.bad_pressure)
+    return refuse(NGRAVS_ERR_ARG, "a type-0 row's pressure is < 0 or not finite");
+  if(c->tune.sph_verbose && hs.targets > 0)
+    printf("ngravs_sph_hydro: %lld targets, %lld candidates tested, %lld pairs evaluated\n", hs.targets, hs.candidates, hs.pairs);
+  if(hs.stack_ovf)
+    return refuse(NGRAVS_ERR_TREE, "the tree is deeper than the walk's stack");
+  if(max_rounds)
+    *max_rounds = (int32_t)ds.max_rounds;
+  const long long nt = ds.targets;
+  if(nt == 0)
+    return NGRAVS_OK;
+  // only the targets' rows are written, all columns in one pass
+  double *dst[SPH_GAS_NRES] = {};
+  int64_t stride[SPH_GAS_NRES] = {};
+  dst[SPH_HSML] = in->hsml, stride[SPH_HSML] = in->hsml_stride;
+  dst[SPH_DENSITY] = in->density, stride[SPH_DENSITY] = in->density_stride;
+  dst[SPH_DIVVEL] = in->div_vel, stride[SPH_DIVVEL] = in->div_vel_stride;
+  dst[SPH_CURLVEL] = in->curl_vel, stride[SPH_CURLVEL] = in->curl_vel_stride;
+  dst[SPH_DHSML] = in->dhsml_factor, stride[SPH_DHSML] = in->dhsml_factor_stride;
+  dst[SPH_GAS_PRESSURE] = in->pressure, stride[SPH_GAS_PRESSURE] = in->pressure_stride;
+  if(out)
+    {
+      dst[SPH_NUMNGB] = out->num_ngb, stride[SPH_NUMNGB] = out->num_ngb_stride;
+      for(int k = 0; k < 3; k++)
+        dst[SPH_GAS_HYDRO + SPH_HY_ACCX + k] = out->hydro_accel ? out->hydro_accel + k : nullptr, stride[SPH_GAS_HYDRO + SPH_HY_ACCX + k] = out->hydro_accel_stride;
+      dst[SPH_GAS_HYDRO + SPH_HY_DTENTR] = out->dt_entropy_out, stride[SPH_GAS_HYDRO + SPH_HY_DTENTR] = out->dt_entropy_out_stride;
+      dst[SPH_GAS_HYDRO + SPH_HY_MAXSIG] = out->max_signal_vel, stride[SPH_GAS_HYDRO + SPH_HY_MAXSIG] = out->max_signal_vel_stride;
+    }
+  if(!in->on_device)
+    return sph_write_targets(c, SPH_GAS_NRES, nt, dst, stride, 0);
+  SphScatterCols cols;
+  for(int k = 0; k < SPH_GAS_NRES; k++)
+    cols.dst[k] = reinterpret_cast<unsigned char *>(dst[k]), cols.stride[k] = stride[k];
+  if((rc = sph_scatter_cols(c, nt, cols)))
+    return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return NGRAVS_OK;
 }
 
 extern "C" int ngravs_sph_kernel(double h, const double *r, int64_t n, double *wk, double *dwk)

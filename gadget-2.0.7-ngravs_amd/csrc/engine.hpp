@@ -368,6 +368,10 @@ struct ngravs_ctx
   DevBuf<int> sph_ts_in;                 // the caller's timestep column
   DevBuf<double> sph_hsrc;               // [SPH_HS_NCOL][n], Peano order: what hydro_evaluate needs of one gas particle
   DevBuf<double> sph_hmax;               // per tree node: largest Hsml of the type-0 particles below it (0: no gas)
+  // the gas side in one call (ngravs_sph_accelerations); empty until it is used
+  DevBuf<double> sph_gas_in;             // the caller's Entropy and DtEntropy columns, [2][own rows]
+  DevBuf<int> sph_ti_in;                 // the caller's Ti_begstep and Ti_endstep columns, [2][own rows]
+  DevBuf<int> sph_tpos;                  // per sorted particle: its place in sph_tlist, -1 when it is no target
 };
 
 // Routes the context's launches to stream `s`, whose CU mask leaves them `cus` CUs, until the end of the scope (the kernels
@@ -508,6 +512,26 @@ struct SphHydroStats
 // reads sph_vel_in, sph_h_in, sph_col_in, sph_ts_in (caller order); fills sph_hsrc and sph_hmax, compacts the targets and walks
 // once; writes sph_res [SPH_HY_NRES][targets] / sph_row in list order (nothing when a column held a bad value)
 int sph_hydro_run(ngravs_ctx *c, const SphHydroParams &hp, SphHydroStats *st);
+// The gas side in one call: sph_res [SPH_GAS_NRES][targets] = the density columns, the pressure, the hydro columns
+enum { SPH_GAS_PRESSURE = SPH_NRES, SPH_GAS_HYDRO, SPH_GAS_NRES = SPH_GAS_HYDRO + SPH_HY_NRES };
+struct SphGasParams
+{
+  double des, dev, minh;   // All.DesNumNgb, All.MaxNumNgbDeviation, All.MinGasHsml
+  int ti_current, have_dte;   // All.Ti_Current; whether sph_gas_in holds a DtEntropy column
+};
+// reads sph_vel (Peano order), sph_h_in, sph_col_in, sph_gas_in, sph_ti_in (caller order); compacts the targets once, walks for
+// the density, derives pressure and hydro sources on the device, walks for the forces; writes sph_res [SPH_GAS_NRES][targets] /
+// sph_row in list order.  Returns after the density walk (ds says why) when a target's hsml was bad or MAXITER was reached.
+// ev_density / ev_prep are recorded after the density walk and after the hmax pass.
+int sph_gas_run(ngravs_ctx *c, const SphGasParams &gp, const SphHydroParams &hp, SphStats *ds, SphHydroStats *hs, hipEvent_t ev_density,
+                hipEvent_t ev_prep);
+struct SphScatterCols
+{
+  unsigned char *dst[SPH_GAS_NRES];   // NULL: not wanted
+  long long stride[SPH_GAS_NRES];
+};
+// list order -> the targets' rows of every wanted strided device column, one launch
+int sph_scatter_cols(ngravs_ctx *c, long long nt, const SphScatterCols &cols);
 // list order -> rows of a strided device column
 int sph_scatter(ngravs_ctx *c, const double *src, long long nt, double *dst, long long stride);
 // ---- kernels_pm.hip

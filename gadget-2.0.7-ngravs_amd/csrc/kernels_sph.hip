@@ -24,6 +24,10 @@
 // k_sph_hydro : the same wave-per-64-targets walk (sph_hull_walk below), ONE walk: a child is opened when its
 //      cube lies within max(largest h_i of the wave, hmax of the child) of the hull of the lanes' positions, the staged entry holds
 //      13 doubles, and every lane applies hydra.c:416-534 to every staged source.
+//
+// The gas side in one call (ngravs_sph_accelerations): k_sph_density, then k_sph_gas_prep in the place of k_sph_hydro_prep (the
+//      pressure line of density.c:305-308 and the hydro sources, a target's from the density results where they lie), k_sph_hmax,
+//      k_sph_hydro, and one k_sph_scatter_cols for all columns.  The two walks are the kernels above, unchanged.
 #include "engine.hpp"
 #include "walk_device.hpp"
 #include <hipcub/hipcub.hpp>
@@ -476,18 +480,9 @@ static int sph_targets(ngravs_ctx *c, int *count)
   return NGRAVS_OK;
 }
 
-int sph_density_run(ngravs_ctx *c, double des_num_ngb, double max_dev, double min_hsml, SphStats *st)
+// k_sph_density over the nt targets of sph_tlist (sph_res, sph_row, sph_rounds are allocated), then its counters
+static int sph_density_walk(ngravs_ctx *c, double des_num_ngb, double max_dev, double min_hsml, long long nt, SphStats *st)
 {
-  memset(st, 0, sizeof(*st));
-  int cnt = 0;
-  if(int rc = sph_targets(c, &cnt))
-    return rc;
-  st->targets = cnt;
-  if(cnt == 0)
-    return NGRAVS_OK;
-  const long long nt = cnt;
-  if(c->sph_res.ensure((size_t)SPH_NRES * nt) || c->sph_row.ensure((size_t)nt) || c->sph_rounds.ensure((size_t)nt))
-    return NGRAVS_ERR_NOMEM;
   SphParams sp;
   sp.periodic = c->cfg.periodic;
   sp.box = c->cfg.box_size;
@@ -514,11 +509,68 @@ int sph_density_run(ngravs_ctx *c, double des_num_ngb, double max_dev, double mi
   return NGRAVS_OK;
 }
 
+int sph_density_run(ngravs_ctx *c, double des_num_ngb, double max_dev, double min_hsml, SphStats *st)
+{
+  memset(st, 0, sizeof(*st));
+  int cnt = 0;
+  if(int rc = sph_targets(c, &cnt))
+    return rc;
+  st->targets = cnt;
+  if(cnt == 0)
+    return NGRAVS_OK;
+  const long long nt = cnt;
+  if(c->sph_res.ensure((size_t)SPH_NRES * nt) || c->sph_row.ensure((size_t)nt) || c->sph_rounds.ensure((size_t)nt))
+    return NGRAVS_ERR_NOMEM;
+  return sph_density_walk(c, des_num_ngb, max_dev, min_hsml, nt, st);
+}
+
 // ---- SPH hydro force --------------------------------------------------------------------------------------------------------
 // counters of a hydro call: type-0 rows with a bad Hsml / Density / Pressure, waves whose LIFO was full, candidates, pairs
 #define SPH_H_BADH 0
 #define SPH_H_BADRHO 1
 #define SPH_H_BADP 3
+
+// One gas particle's columns of sph_hsrc from its SphP values: what hydro_evaluate derives from one particle alone.  The one place
+// these expressions stand, for k_sph_hydro_prep and k_sph_gas_prep.  Counts a bad Hsml / Density / Pressure; returns whether
+// the row is good.
+__device__ __forceinline__ bool sph_hydro_source(double *__restrict__ hs, long long n, long long p, double vx, double vy, double vz, double h,
+                                                 double rho, double pressure, double dhsml, double div, double curl, double ts,
+                                                 const SphHydroParams &hp, unsigned long long *__restrict__ counters)
+{
+  const double BIG = 1e300;
+  const double adiv = fabs(div);
+  bool good = true;
+  if(!(h > 0) || !(h < BIG))
+    {
+      atomicAdd(&counters[SPH_H_BADH], 1ull);
+      good = false;
+    }
+  if(!(rho > 0) || !(rho < BIG))
+    {
+      atomicAdd(&counters[SPH_H_BADRHO], 1ull);
+      good = false;
+    }
+  if(!(pressure >= 0) || !(pressure < BIG))
+    {
+      atomicAdd(&counters[SPH_H_BADP], 1ull);
+      good = false;
+    }
+  const double por2 = pressure / (rho * rho);                 // hydra.c:441
+  const double cs_j = sqrt(hp.gamma * por2 * rho);            // hydra.c:442
+  const double cs_i = sqrt(hp.gamma * pressure / rho);        // hydra.c:379
+  hs[SPH_HS_VX * n + p] = vx;
+  hs[SPH_HS_VY * n + p] = vy;
+  hs[SPH_HS_VZ * n + p] = vz;
+  hs[SPH_HS_H * n + p] = h;
+  hs[SPH_HS_RHO * n + p] = rho;
+  hs[SPH_HS_POR2 * n + p] = por2 * dhsml;                     // hydra.c:403, :524
+  hs[SPH_HS_CSJ * n + p] = cs_j;
+  hs[SPH_HS_F2 * n + p] = adiv / (adiv + curl + 0.0001 * cs_j / hp.fac_mu / h);   // hydra.c:504-506
+  hs[SPH_HS_TS * n + p] = ts;
+  hs[SPH_HS_CSI * n + p] = cs_i;
+  hs[SPH_HS_F1 * n + p] = adiv / (adiv + curl + 0.0001 * cs_i / h / hp.fac_mu);   // hydra.c:380-382
+  return good;
+}
 
 __global__ void k_sph_hydro_prep(const unsigned char *__restrict__ type, const unsigned int *__restrict__ idx, long long n,
                                  const double *__restrict__ vel_in, const double *__restrict__ h_in, const double *__restrict__ col_in,
@@ -534,29 +586,58 @@ __global__ void k_sph_hydro_prep(const unsigned char *__restrict__ type, const u
       return;
     }
   const long long row = idx[p];
-  const double BIG = 1e300;
-  const double h = h_in[row], rho = col_in[row], pressure = col_in[n + row], dhsml = col_in[2 * n + row];
-  const double adiv = fabs(col_in[3 * n + row]), curl = col_in[4 * n + row];
-  if(!(h > 0) || !(h < BIG))
-    atomicAdd(&counters[SPH_H_BADH], 1ull);
-  if(!(rho > 0) || !(rho < BIG))
-    atomicAdd(&counters[SPH_H_BADRHO], 1ull);
-  if(!(pressure >= 0) || !(pressure < BIG))
-    atomicAdd(&counters[SPH_H_BADP], 1ull);
-  const double por2 = pressure / (rho * rho);                 // hydra.c:441
-  const double cs_j = sqrt(hp.gamma * por2 * rho);            // hydra.c:442
-  const double cs_i = sqrt(hp.gamma * pressure / rho);        // hydra.c:379
-  hs[SPH_HS_VX * n + p] = vel_in[3 * row];
-  hs[SPH_HS_VY * n + p] = vel_in[3 * row + 1];
-  hs[SPH_HS_VZ * n + p] = vel_in[3 * row + 2];
-  hs[SPH_HS_H * n + p] = h;
-  hs[SPH_HS_RHO * n + p] = rho;
-  hs[SPH_HS_POR2 * n + p] = por2 * dhsml;                     // hydra.c:403, :524
-  hs[SPH_HS_CSJ * n + p] = cs_j;
-  hs[SPH_HS_F2 * n + p] = adiv / (adiv + curl + 0.0001 * cs_j / hp.fac_mu / h);   // hydra.c:504-506
-  hs[SPH_HS_TS * n + p] = hp.have_ts ? (double)ts_in[row] : 0.0;
-  hs[SPH_HS_CSI * n + p] = cs_i;
-  hs[SPH_HS_F1 * n + p] = adiv / (adiv + curl + 0.0001 * cs_i / h / hp.fac_mu);   // hydra.c:380-382
+  sph_hydro_source(hs, n, p, vel_in[3 * row], vel_in[3 * row + 1], vel_in[3 * row + 2], h_in[row], col_in[row], col_in[n + row],
+                   col_in[2 * n + row], col_in[3 * n + row], col_in[4 * n + row], hp.have_ts ? (double)ts_in[row] : 0.0, hp, counters);
+}
+
+// ngravs_sph_accelerations, between its two walks: the pressure line of density() (density.c:305-308) for the targets, whose
+// density results are read where k_sph_density left them (res, list order, through tpos: sorted position -> list index, -1 for a
+// particle that is no target), and the hydro stage's sph_hsrc for every gas particle -- a target's from those results, another
+// gas particle's from the caller's columns as k_sph_hydro_prep takes them.  vel is VelPred in Peano order (sph_vel).  A bad row
+// gets Hsml 0 here: the call is refused after the walk, which must not open the whole tree for an infinite length meanwhile.
+__global__ void k_sph_gas_prep(const unsigned char *__restrict__ type, const unsigned int *__restrict__ idx, const int *__restrict__ tpos,
+                               long long n, long long nt, const double *__restrict__ vel, const double *__restrict__ h_in,
+                               const double *__restrict__ col_in, const double *__restrict__ entropy, const double *__restrict__ dt_entropy,
+                               const int *__restrict__ ti_beg, const int *__restrict__ ti_end, int ti_current, SphHydroParams hp,
+                               double *__restrict__ res, double *__restrict__ hs, unsigned long long *__restrict__ counters)
+{
+  const long long p = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+  if(p >= n)
+    return;
+  if(type[p] != 0)
+    {
+      hs[SPH_HS_H * n + p] = 0;   // no gas: nothing for hmax, never staged
+      return;
+    }
+  const long long row = idx[p];
+  const long long t = tpos[p];
+  const int beg = hp.have_ts ? ti_beg[row] : 0, end = hp.have_ts ? ti_end[row] : 0;
+  double h, rho, pressure, dhsml, div, curl;
+  if(t >= 0 && t < nt)
+    {
+      h = res[SPH_HSML * nt + t], rho = res[SPH_DENSITY * nt + t], dhsml = res[SPH_DHSML * nt + t];
+      div = res[SPH_DIVVEL * nt + t], curl = res[SPH_CURLVEL * nt + t];
+      // density.c:305: the midpoint by the reference's integer division
+      const double dt_entr = hp.have_ts ? (double)((long long)ti_current - ((long long)beg + end) / 2) * hp.tbi : 0.0;
+      pressure = (entropy[row] + (dt_entropy ? dt_entropy[row] : 0.0) * dt_entr) * pow(rho, hp.gamma);   // density.c:307-308
+      res[SPH_GAS_PRESSURE * nt + t] = pressure;
+    }
+  else
+    {
+      h = h_in[row], rho = col_in[row], pressure = col_in[n + row], dhsml = col_in[2 * n + row];
+      div = col_in[3 * n + row], curl = col_in[4 * n + row];
+    }
+  if(!sph_hydro_source(hs, n, p, vel[3 * p], vel[3 * p + 1], vel[3 * p + 2], h, rho, pressure, dhsml, div, curl,
+                       hp.have_ts ? (double)(end - beg) : 0.0, hp, counters))
+    hs[SPH_HS_H * n + p] = 0;
+}
+
+// sorted position -> list index of the targets (tpos is -1 everywhere before)
+__global__ void k_sph_tpos(const int *__restrict__ tlist, long long nt, long long n, int *__restrict__ tpos)
+{
+  const long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+  if(t < nt && tlist[t] >= 0 && tlist[t] < n)
+    tpos[tlist[t]] = (int)t;
 }
 
 // force_update_hmax (forcetree.c:1134-1203, local part): the nodes of one level from their children, the levels bottom-up
@@ -747,6 +828,34 @@ __global__ __launch_bounds__(64 * SPH_HWAVES) void k_sph_hydro(TreeView tv, cons
     }
 }
 
+// force_update_hmax from the Hsml column of sph_hsrc
+static int sph_hmax_levels(ngravs_ctx *c)
+{
+  const long long n = c->n;
+  for(int l = c->nlevels - 1; l >= 0; l--)
+    {
+      const long long l0 = c->level_start[l], lc = c->level_start[l + 1] - l0;
+      if(lc <= 0)
+        continue;
+      hipLaunchKernelGGL(k_sph_hmax, dim3((unsigned)((lc + 127) / 128)), dim3(128), 0, c->stream, c->n_child.p, c->n_first.p, c->n_count.p,
+                         c->n_flags.p, c->sph_hsrc.p + SPH_HS_H * n, n, (int)l0, (int)lc, c->sph_hmax.p);
+    }
+  HIP_TRY(c, hipGetLastError());
+  return NGRAVS_OK;
+}
+
+// k_sph_hydro over the nt targets of sph_tlist: res [SPH_HY_NRES][nt] and sph_row in list order
+static int sph_hydro_walk(ngravs_ctx *c, const SphHydroParams &hp, long long nt, double *res)
+{
+  const long long n = c->n;
+  const long long nwaves = (nt + 63) / 64;
+  const unsigned nb = (unsigned)((nwaves + SPH_HWAVES - 1) / SPH_HWAVES);
+  hipLaunchKernelGGL(k_sph_hydro, dim3(nb), dim3(64 * SPH_HWAVES), 0, c->stream, sph_tree_view(c), c->s_pm.p, c->s_type.p, c->sph_hsrc.p,
+                     c->sph_hmax.p, c->s_idx.p, c->sph_tlist.p, nt, n, hp, res, c->sph_row.p, c->sph_counters.p);
+  HIP_TRY(c, hipGetLastError());
+  return NGRAVS_OK;
+}
+
 int sph_hydro_run(ngravs_ctx *c, const SphHydroParams &hp, SphHydroStats *st)
 {
   memset(st, 0, sizeof(*st));
@@ -773,25 +882,66 @@ int sph_hydro_run(ngravs_ctx *c, const SphHydroParams &hp, SphHydroStats *st)
   st->bad_pressure = (long long)h[SPH_H_BADP];
   if(st->bad_hsml || st->bad_density || st->bad_pressure)
     return NGRAVS_OK;   // the caller refuses; nothing is walked with such a column
-  for(int l = c->nlevels - 1; l >= 0; l--)
-    {
-      const long long l0 = c->level_start[l], lc = c->level_start[l + 1] - l0;
-      if(lc <= 0)
-        continue;
-      hipLaunchKernelGGL(k_sph_hmax, dim3((unsigned)((lc + 127) / 128)), dim3(128), 0, c->stream, c->n_child.p, c->n_first.p, c->n_count.p,
-                         c->n_flags.p, c->sph_hsrc.p + SPH_HS_H * n, n, (int)l0, (int)lc, c->sph_hmax.p);
-    }
-  HIP_TRY(c, hipGetLastError());
-  const long long nwaves = (nt + 63) / 64;
-  const unsigned nb = (unsigned)((nwaves + SPH_HWAVES - 1) / SPH_HWAVES);
-  hipLaunchKernelGGL(k_sph_hydro, dim3(nb), dim3(64 * SPH_HWAVES), 0, c->stream, sph_tree_view(c), c->s_pm.p, c->s_type.p, c->sph_hsrc.p,
-                     c->sph_hmax.p, c->s_idx.p, c->sph_tlist.p, nt, n, hp, c->sph_res.p, c->sph_row.p, c->sph_counters.p);
-  HIP_TRY(c, hipGetLastError());
+  if(int rc = sph_hmax_levels(c))
+    return rc;
+  if(int rc = sph_hydro_walk(c, hp, nt, c->sph_res.p))
+    return rc;
   HIP_TRY(c, hipMemcpyAsync(h, c->sph_counters.p, sizeof(h), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   st->stack_ovf = (long long)h[SPH_C_OVF];
   st->candidates = (long long)h[SPH_C_CAND];
   st->pairs = (long long)h[SPH_C_NGB];
+  return NGRAVS_OK;
+}
+
+// ---- the gas side in one call (ngravs_sph_accelerations): density(), its pressure line, force_update_hmax(), hydro_force() ----
+// One target list, no host synchronisation between the stages but the read-back of the density walk's counters (MAXITER and the
+// other error flags), after which nothing runs when one is set.  sph_res holds [SPH_GAS_NRES][targets]: the density columns, the
+// pressure, the hydro columns.
+int sph_gas_run(ngravs_ctx *c, const SphGasParams &gp, const SphHydroParams &hp, SphStats *ds, SphHydroStats *hs, hipEvent_t ev_density,
+                hipEvent_t ev_prep)
+{
+  memset(ds, 0, sizeof(*ds));
+  memset(hs, 0, sizeof(*hs));
+  const long long n = c->n;
+  int cnt = 0;
+  if(int rc = sph_targets(c, &cnt))   // (clears the counters)
+    return rc;
+  ds->targets = hs->targets = cnt;
+  if(cnt == 0)
+    return NGRAVS_OK;
+  const long long nt = cnt;
+  if(c->sph_res.ensure((size_t)SPH_GAS_NRES * nt) || c->sph_row.ensure((size_t)nt) || c->sph_rounds.ensure((size_t)nt) ||
+     c->sph_tpos.ensure((size_t)n) || c->sph_hsrc.ensure((size_t)SPH_HS_NCOL * n) || c->sph_hmax.ensure((size_t)c->nnodes))
+    return NGRAVS_ERR_NOMEM;
+  HIP_TRY(c, hipMemsetAsync(c->sph_tpos.p, 0xff, sizeof(int) * n, c->stream));   // -1
+  hipLaunchKernelGGL(k_sph_tpos, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, c->stream, c->sph_tlist.p, nt, n, c->sph_tpos.p);
+  HIP_TRY(c, hipGetLastError());
+  if(int rc = sph_density_walk(c, gp.des, gp.dev, gp.minh, nt, ds))
+    return rc;
+  HIP_TRY(c, hipEventRecord(ev_density, c->stream));
+  if(ds->bad_hsml || ds->stack_ovf || ds->failed)
+    return NGRAVS_OK;   // the caller refuses; nothing of the hydro stage runs
+  // the hydro stage counts in the same words
+  HIP_TRY(c, hipMemsetAsync(c->sph_counters.p, 0, SPH_C_COUNT * sizeof(unsigned long long), c->stream));
+  hipLaunchKernelGGL(k_sph_gas_prep, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->s_type.p, c->s_idx.p, c->sph_tpos.p, n, nt,
+                     c->sph_vel.p, c->sph_h_in.p, c->sph_col_in.p, c->sph_gas_in.p, gp.have_dte ? c->sph_gas_in.p + n : nullptr,
+                     c->sph_ti_in.p, c->sph_ti_in.p + n, gp.ti_current, hp, c->sph_res.p, c->sph_hsrc.p, c->sph_counters.p);
+  HIP_TRY(c, hipGetLastError());
+  if(int rc = sph_hmax_levels(c))
+    return rc;
+  HIP_TRY(c, hipEventRecord(ev_prep, c->stream));
+  if(int rc = sph_hydro_walk(c, hp, nt, c->sph_res.p + SPH_GAS_HYDRO * nt))
+    return rc;
+  unsigned long long h[SPH_C_COUNT];
+  HIP_TRY(c, hipMemcpyAsync(h, c->sph_counters.p, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  hs->bad_hsml = (long long)h[SPH_H_BADH];
+  hs->bad_density = (long long)h[SPH_H_BADRHO];
+  hs->bad_pressure = (long long)h[SPH_H_BADP];
+  hs->stack_ovf = (long long)h[SPH_C_OVF];
+  hs->candidates = (long long)h[SPH_C_CAND];
+  hs->pairs = (long long)h[SPH_C_NGB];
   return NGRAVS_OK;
 }
 
@@ -801,6 +951,26 @@ __global__ void k_sph_scatter(const int *__restrict__ row, long long nt, const d
   const long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x;
   if(t < nt)
     *reinterpret_cast<double *>(dst + row[t] * stride) = src[t];
+}
+
+// every wanted column of sph_res [SPH_GAS_NRES][nt] in one pass
+__global__ void k_sph_scatter_cols(const int *__restrict__ row, long long nt, const double *__restrict__ res, SphScatterCols cols)
+{
+  const long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+  if(t >= nt)
+    return;
+  const long long r = row[t];
+#pragma unroll
+  for(int k = 0; k < SPH_GAS_NRES; k++)
+    if(cols.dst[k])
+      *reinterpret_cast<double *>(cols.dst[k] + r * cols.stride[k]) = res[k * nt + t];
+}
+
+int sph_scatter_cols(ngravs_ctx *c, long long nt, const SphScatterCols &cols)
+{
+  hipLaunchKernelGGL(k_sph_scatter_cols, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, c->stream, c->sph_row.p, nt, c->sph_res.p, cols);
+  HIP_TRY(c, hipGetLastError());
+  return NGRAVS_OK;
 }
 
 int sph_scatter(ngravs_ctx *c, const double *src, long long nt, double *dst, long long stride)

@@ -496,8 +496,8 @@ int ngravs_pm_slab_bytes(ngravs_ctx *ctx, double bytes[4]);
  * particles (ngb.c:221), nearest image in periodic runs.  Every target's smoothing length is iterated to acceptance by the
  * reference's rules (density.c:314-389: NumNgb inside DesNumNgb +- MaxNumNgbDeviation, or above it with Hsml <= 1.01 MinGasHsml,
  * or a bracket narrower than 1e-3; bisection in h^3, the Newton-like step, the factor 1.26; clamp to MinGasHsml), and Density,
- * NumNgb, DivVel, CurlVel, DhsmlDensityFactor come out as after its final operations (density.c:296-303; the pressure line is the
- * host's: the library holds no entropy).  A target that needs more than MAXITER = 150 repeats is the reference's endrun(1155):
+ * NumNgb, DivVel, CurlVel, DhsmlDensityFactor come out as after its final operations (density.c:296-303; this call leaves the pressure line,
+ * density.c:305-308, to its caller -- ngravs_sph_accelerations below takes the entropy and computes it).  A target that needs more than MAXITER = 150 repeats is the reference's endrun(1155):
  * the fatal handler is called with 1155 and the call returns NGRAVS_ERR_STATE.
  * Needs a built tree of the current particle set (NGRAVS_ERR_STATE otherwise); after ngravs_update_particles the tree is refit
  * first.  The tree, the walk's state and the stored accelerations are not modified.  NGRAVS_ERR_ARG with a message: NULL in /
@@ -557,6 +557,52 @@ typedef struct {   /* any pointer may be NULL; strides in bytes; rows = own rows
 } ngravs_hydro_out_t;
 /* kernel_ms may be NULL: device time of the call (HIP events) */
 int ngravs_sph_hydro(ngravs_ctx *ctx, const ngravs_hydro_in_t *in, const ngravs_hydro_out_t *out, double *kernel_ms);
+
+/* ---- The gas side of compute_accelerations() (accel.c:60-96) for ONE task, in one device-resident call ------------------------------
+ * density() INCLUDING its pressure line (density.c:305-308), then force_update_hmax(), then hydro_force(): what ngravs_sph_density,
+ * the host's pressure line and ngravs_sph_hydro give one after the other, bit for bit (the two walks are the same kernels), with one
+ * target list, one upload of the velocities and no trip through the host between the stages other than the read-back of the
+ * density walk's error flags.  Targets are the own active type-0 rows, sources all type-0 rows.
+ * The SphP columns hsml, density, pressure, dhsml_factor, div_vel, curl_vel are IN/OUT, as SphP[] is in the reference: read for
+ * every type-0 row that is no target (an inactive gas particle is a source with its values of the step before), overwritten for the
+ * targets only; a target's hsml is its starting guess on entry, its other five are not read.  Rows of other types are not read.
+ * Pressure = (entropy + dt_entropy * dt_entr) * pow(Density, gamma) with dt_entr = (ti_current - (ti_begstep + ti_endstep) / 2) *
+ * timebase_interval, the / 2 being the reference's integer division; the hydro timestep of a row is ti_endstep - ti_begstep.
+ * dt_entropy NULL: 0.  ti_begstep and ti_endstep both NULL: dt_entr and every timestep are 0.  gamma, viscosity_limiter, comoving and
+ * its factors: as in ngravs_hydro_in_t.
+ * Refusals are those of the two calls above, code and message: single task only; needs a built tree (refit first when the particles
+ * drifted); NGRAVS_ERR_ARG for NULL in, a NULL column other than dt_entropy / the ti pair, only one of the ti pair, des_num_ngb <= 0,
+ * a negative deviation, minimum or constant, gamma < 1, a target whose hsml is <= 0 or not finite, a type-0 row whose hsml or
+ * density is <= 0 or not finite or whose pressure is < 0 or not finite (of a row that is no target: the value given; of a target:
+ * the value computed, e.g. from an entropy that is not finite); MAXITER: the fatal handler is called with 1155, NGRAVS_ERR_STATE,
+ * and nothing of the hydro stage has run.  Nothing is written unless the whole call succeeds.  No type-0 target: success, nothing
+ * written, 0 rounds.  The tree, the walk's state and the stored accelerations are not modified.
+ * Not provided: several tasks, TWODIMS, LONG_X/Y/Z, SPH_BND_PARTICLES. */
+typedef struct {   /* strides in bytes; rows = own rows */
+  const double *vel_pred;      int64_t vel_pred_stride;      /* SphP[].VelPred[3]                                            */
+  const double *entropy;       int64_t entropy_stride;       /* SphP[].Entropy                                               */
+  const double *dt_entropy;    int64_t dt_entropy_stride;    /* SphP[].DtEntropy of the step before, or NULL                 */
+  const int32_t *ti_begstep;   int64_t ti_begstep_stride;    /* P[].Ti_begstep, or NULL (then ti_endstep is NULL too)        */
+  const int32_t *ti_endstep;   int64_t ti_endstep_stride;    /* P[].Ti_endstep                                               */
+  double *hsml;                int64_t hsml_stride;          /* in/out: SphP[].Hsml (a target's: the starting guess, > 0)    */
+  double *density;             int64_t density_stride;       /* in/out: SphP[].Density                                       */
+  double *pressure;            int64_t pressure_stride;      /* in/out: SphP[].Pressure                                      */
+  double *dhsml_factor;        int64_t dhsml_factor_stride;  /* in/out: SphP[].DhsmlDensityFactor                            */
+  double *div_vel;             int64_t div_vel_stride;       /* in/out: SphP[].DivVel                                        */
+  double *curl_vel;            int64_t curl_vel_stride;      /* in/out: SphP[].CurlVel                                       */
+  double des_num_ngb, max_num_ngb_deviation, min_gas_hsml;   /* All.DesNumNgb, All.MaxNumNgbDeviation, All.MinGasHsml        */
+  double art_bulk_visc_const, timebase_interval, gamma;      /* All.ArtBulkViscConst, All.Timebase_interval, GAMMA           */
+  double hubble_a2, fac_mu, fac_vsic_fix;                    /* hydra.c:78-97, read when comoving != 0                       */
+  int32_t ti_current, viscosity_limiter, comoving, on_device;   /* All.Ti_Current                                            */
+} ngravs_gas_in_t;
+typedef struct {   /* any pointer may be NULL; strides in bytes; rows = own rows, only targets are written */
+  double *num_ngb, *hydro_accel, *dt_entropy_out, *max_signal_vel;   /* SphP[].NumNgb, HydroAccel[3], DtEntropy, MaxSignalVel */
+  int64_t num_ngb_stride, hydro_accel_stride, dt_entropy_out_stride, max_signal_vel_stride;
+} ngravs_gas_out_t;
+/* max_rounds, kernel_ms may be NULL: the most evaluations any target took; device time (HIP events) of the density walk, of the
+ * pressure line + hydro sources + hmax, and of the hydro walk */
+int ngravs_sph_accelerations(ngravs_ctx *ctx, const ngravs_gas_in_t *in, const ngravs_gas_out_t *out, int32_t *max_rounds,
+                             double *kernel_ms /* [3] */);
 
 #ifdef __cplusplus
 }
