@@ -42,6 +42,7 @@ EXPORTS = [
     "ngravs_dd_set_ids", "ngravs_dd_get_ids",
     "ngravs_pm_slab_begin", "ngravs_pm_slab_pack", "ngravs_pm_slab_unpack", "ngravs_pm_slab_bytes",
     "ngravs_sph_density", "ngravs_sph_kernel", "ngravs_sph_hydro", "ngravs_sph_accelerations",
+    "ngravs_sph_hsml_guess",
 ]
 # include/ngravs_host.h (plain-C multi-task drivers over a communicator vtable, linked into the same library)
 HOST_EXPORTS = ["ngravs_host_comm_selftest", "ngravs_host_kept_step", "ngravs_host_toptree_borrow", "ngravs_host_domain_decomposition", "ngravs_host_domain_owners", "ngravs_host_domain_halo",
@@ -132,6 +133,7 @@ def lib():
         L.ngravs_sph_kernel.argtypes = [C.c_double, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         L.ngravs_sph_hydro.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ngravs_sph_accelerations.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ngravs_sph_hsml_guess.argtypes = abi.SPH_HSML_GUESS_ARGTYPES
         _LIB = L
     return _LIB
 
@@ -468,6 +470,28 @@ class Engine:
         rounds, ms = C.c_int32(0), C.c_double(0)
         self._check(lib().ngravs_sph_density(self._h, C.byref(si), C.byref(so), C.byref(rounds), C.byref(ms)), "ngravs_sph_density")
         res["max_rounds"], res["kernel_ms"] = int(rounds.value), float(ms.value)
+        return res
+
+    def sph_hsml_guess(self, des_num_ngb, hsml=None, only_unset=False):
+        """the first guess of the smoothing lengths, setup_smoothinglengths() of the reference for one task (init.c:229-247), from
+        the built tree.  Returns the hsml column over all rows of the last hand-over: the guess in every type-0 row (only_unset:
+        in those whose given value is not > 0), what `hsml` held in the others -- NaN when nothing was passed.  A numpy array, or
+        a torch tensor on the device (float64, contiguous), is copied, not written."""
+        on_device = hsml is not None and not isinstance(hsml, np.ndarray) and hasattr(hsml, "data_ptr")
+        if on_device:
+            import torch
+            assert hsml.dtype == torch.float64 and hsml.is_contiguous()
+            res = hsml.clone()
+            torch.cuda.synchronize()
+            addr = res.data_ptr()
+        else:
+            res = np.full(self.n, np.nan) if hsml is None else np.array(hsml, dtype=np.float64)
+            addr = res.ctypes.data
+        assert tuple(res.shape) == (self.n,)
+        ms = C.c_double(0)
+        self._check(lib().ngravs_sph_hsml_guess(self._h, float(des_num_ngb), addr, 8, int(bool(only_unset)), int(on_device), C.byref(ms)),
+                    "ngravs_sph_hsml_guess")
+        self.last_hsml_guess_ms = float(ms.value)
         return res
 
     def sph_hydro(self, vel, hsml, density, pressure, dhsml_factor, div_vel, curl_vel, *, art_bulk_visc_const, timestep=None,

@@ -133,6 +133,10 @@ class SphOut(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in SPH_OUT_NAMES] + [(k + "_stride", C.c_int64) for k in SPH_OUT_NAMES]
 
 
+# int ngravs_sph_hsml_guess(ctx, des_num_ngb, hsml, hsml_stride, only_unset, on_device, kernel_ms)
+SPH_HSML_GUESS_ARGTYPES = [C.c_void_p, C.c_double, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]
+
+
 HYDRO_IN_NAMES = ("vel_pred", "hsml", "density", "pressure", "dhsml_factor", "div_vel", "curl_vel", "timestep")
 HYDRO_OUT_NAMES = ("hydro_accel", "dt_entropy", "max_signal_vel")
 

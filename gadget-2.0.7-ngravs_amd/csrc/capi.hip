@@ -418,6 +418,8 @@ extern "C" void ngravs_destroy(ngravs_ctx *c)
   c->sph_gas_in.release();
   c->sph_ti_in.release();
   c->sph_tpos.release();
+  c->sph_gmass.release();
+  c->sph_gcount.release();
   (void)hipEventDestroy(c->ev0);
   (void)hipEventDestroy(c->ev1);
   (void)hipEventDestroy(c->evk0);
@@ -2031,6 +2033,49 @@ extern "C" int ngravs_sph_density(ngravs_ctx *c, const ngravs_sph_in_t *in, cons
       dst[SPH_DHSML] = out->dhsml_factor, stride[SPH_DHSML] = out->dhsml_factor_stride;
     }
   return sph_write_targets(c, SPH_NRES, nt, dst, stride, in->on_device);
+}
+
+// ---- the first smoothing-length guess (setup_smoothinglengths, init.c:229-247, for one task; kernels_sph.hip) -----------------
+extern "C" int ngravs_sph_hsml_guess(ngravs_ctx *c, double des_num_ngb, double *hsml, int64_t hsml_stride, int32_t only_unset, int32_t on_device,
+                                     double *kernel_ms)
+{
+  if(!c)
+    return NGRAVS_ERR_ARG;
+  auto refuse = [&](int code, const char *why) {
+    ngravs_report(c, code, std::string("ngravs_sph_hsml_guess: ") + why);
+    return code;
+  };
+  if(!hsml || !(des_num_ngb > 0))
+    return refuse(NGRAVS_ERR_ARG, "hsml must not be NULL and des_num_ngb must be > 0");
+  int rc;
+  if((rc = sph_ready(c, refuse)))
+    return rc;
+  if(kernel_ms)
+    *kernel_ms = 0;
+  const int64_t n = c->n_local;
+  if(n == 0 || c->nnodes <= 0)
+    return NGRAVS_OK;
+  if(only_unset)
+    {
+      if(c->sph_h_in.ensure(n))
+        return refuse(NGRAVS_ERR_NOMEM, "device allocation failed");
+      if((rc = upload_column_f64(c, hsml, hsml_stride, 1, n, on_device, c->sph_h_in.p)))
+        return rc;
+    }
+  HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
+  long long rows = 0, bad_mass = 0;
+  if((rc = sph_hsml_guess_run(c, des_num_ngb, only_unset != 0, &rows, &bad_mass)))
+    return rc;
+  HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
+  if(kernel_ms)
+    *kernel_ms = ev_ms(c);
+  if(bad_mass)
+    return refuse(NGRAVS_ERR_ARG, "a type-0 row's mass is <= 0 or not finite");
+  if(rows == 0)
+    return NGRAVS_OK;
+  double *dst[1] = {hsml};
+  const int64_t stride[1] = {hsml_stride};
+  return sph_write_targets(c, 1, rows, dst, stride, on_device);
 }
 
 // ---- SPH hydro force (hydra.c:50-346 for one task; kernels_sph.hip) ---------------------------------------------------------

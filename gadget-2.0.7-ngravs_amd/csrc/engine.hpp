@@ -372,6 +372,9 @@ struct ngravs_ctx
   DevBuf<double> sph_gas_in;             // the caller's Entropy and DtEntropy columns, [2][own rows]
   DevBuf<int> sph_ti_in;                 // the caller's Ti_begstep and Ti_endstep columns, [2][own rows]
   DevBuf<int> sph_tpos;                  // per sorted particle: its place in sph_tlist, -1 when it is no target
+  // the first smoothing-length guess (ngravs_sph_hsml_guess); empty until it is used
+  DevBuf<double> sph_gmass;              // [n + 1], Peano order: gas mass of the rows before a row (inclusive scan shifted by one)
+  DevBuf<int> sph_gcount;                // [n + 1]: gas rows before a row
 };
 
 // Routes the context's launches to stream `s`, whose CU mask leaves them `cus` CUs, until the end of the scope (the kernels
@@ -492,6 +495,10 @@ struct SphStats
 // compacts the targets into sph_tlist, then iterates every target's smoothing length to acceptance in one launch: reads sph_vel
 // (Peano order) and sph_h_in (caller order), writes sph_res / sph_row / sph_rounds in list order
 int sph_density_run(ngravs_ctx *c, double des_num_ngb, double max_dev, double min_hsml, SphStats *st);
+// setup_smoothinglengths (init.c:229-247) on the device tree: lists the type-0 rows (only_unset: those whose sph_h_in value is not
+// > 0), writes their guesses to sph_res [rows] / sph_row in list order.  bad_mass: type-0 rows whose mass is <= 0 or not finite
+// (nothing is computed then).
+int sph_hsml_guess_run(ngravs_ctx *c, double des_num_ngb, int only_unset, long long *rows, long long *bad_mass);
 // SPH hydro force.  Columns of sph_hsrc: VelPred[3], Hsml (0 for rows of other types), Density, Pressure / Density^2 *
 // DhsmlDensityFactor, the sound speed as a source (hydra.c:441-442), f2 (hydra.c:504-506), the timestep, the sound speed and f1 as
 // a target (hydra.c:379-382)

@@ -25,6 +25,11 @@
 //      cube lies within max(largest h_i of the wave, hmax of the child) of the hull of the lanes' positions, the staged entry holds
 //      13 doubles, and every lane applies hydra.c:416-534 to every staged source.
 //
+// The first guess of the smoothing lengths (ngravs_sph_hsml_guess; setup_smoothinglengths, init.c:229-247):
+// k_sph_gas_cols : one thread per sorted particle: gas mass and gas flag, the inputs of two prefix scans over the Peano-ordered rows
+// k_sph_hsml_guess : one lane per gas row: from the root down the cells that hold the particle, a node's gas mass and count as
+//      differences of the scans, below the deepest level by halving the bucket's cell; no LDS, no scratch.
+//
 // The gas side in one call (ngravs_sph_accelerations): k_sph_density, then k_sph_gas_prep in the place of k_sph_hydro_prep (the
 //      pressure line of density.c:305-308 and the hydro sources, a target's from the density results where they lie), k_sph_hmax,
 //      k_sph_hydro, and one k_sph_scatter_cols for all columns.  The two walks are the kernels above, unchanged.
@@ -522,6 +527,160 @@ int sph_density_run(ngravs_ctx *c, double des_num_ngb, double max_dev, double mi
   if(c->sph_res.ensure((size_t)SPH_NRES * nt) || c->sph_row.ensure((size_t)nt) || c->sph_rounds.ensure((size_t)nt))
     return NGRAVS_ERR_NOMEM;
   return sph_density_walk(c, des_num_ngb, max_dev, min_hsml, nt, st);
+}
+
+// ---- the first guess of the smoothing lengths (setup_smoothinglengths, init.c:229-247, 3-D branch) ----------------------------
+// The reference climbs its GAS-ONLY tree (ngb_treebuild -> force_treebuild(N_gas), ngb.c:408) from Father[i] while
+// 10 DesNumNgb m_i > mass(no).  The masses of nested cells never decrease going up, so the same cell is found from the root:
+// descend along the cells containing i while the next one holds at least two gas particles (it is a node of the gas-only tree)
+// and at least 10 DesNumNgb m_i of gas.  The device tree holds all types; a node is a contiguous range of the Peano-ordered rows,
+// so its gas mass and gas count are differences of two values of an inclusive scan over (type == 0 ? mass : 0) and (type == 0).
+// k_sph_gas_cols   : one thread per row: the two scan inputs, shifted by one ([0] = 0); counts type-0 rows with a bad mass
+// k_sph_hsml_guess : one lane per listed gas row, Peano order (neighbouring lanes follow the same path and load the same nodes)
+__global__ void k_sph_gas_cols(const double4 *__restrict__ pm, const unsigned char *__restrict__ type, long long n, double *__restrict__ gm,
+                               int *__restrict__ gc, unsigned long long *__restrict__ counters)
+{
+  const long long p = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+  if(p == 0)
+    {
+      gm[0] = 0;
+      gc[0] = 0;
+    }
+  if(p >= n)
+    return;
+  const bool gas = type[p] == 0;
+  const double m = pm[p].w;
+  if(gas && !(m > 0 && m <= 1.79769313486231570e308))
+    atomicAdd(&counters[SPH_C_BAD], 1ull);
+  gm[p + 1] = gas ? m : 0.0;
+  gc[p + 1] = gas ? 1 : 0;
+}
+
+struct SphIsUnsetGas
+{
+  const unsigned char *type;
+  const unsigned int *idx;
+  const double *h_in;   // caller order; null: every gas row
+  __host__ __device__ __forceinline__ bool operator()(const int &i) const { return type[i] == 0 && !(h_in && h_in[idx[i]] > 0); }
+};
+
+#define SPH_GUESS_SUB 30   // halvings below a bucket: 21 + 30 bits of a coordinate are exact in a double and fit a long long
+
+__global__ void k_sph_hsml_guess(const int *__restrict__ n_first, const int *__restrict__ n_count, const int *__restrict__ n_child,
+                                 const int *__restrict__ n_flags, int nnodes, const double4 *__restrict__ pm,
+                                 const unsigned char *__restrict__ type, const unsigned int *__restrict__ idx, const int *__restrict__ list,
+                                 long long nl, long long n, const double *__restrict__ gm, const int *__restrict__ gc, double des, double cx,
+                                 double cy, double cz, double fac21, double len0, double *__restrict__ res, int *__restrict__ row)
+{
+  const long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+  if(t >= nl)
+    return;
+  const long long p = list[t];
+  if(p < 0 || p >= n)
+    return;
+  const double4 me = pm[p];
+  const double thr = 10 * des * me.w;   // init.c:235
+  int node = 0, level = 0;
+  double mass = gm[n] - gm[0];          // the root is used even when it fails the mass test (init.c:239-240)
+  while(level < TREE_BITS && !(n_flags[node] & FLAG_BUCKET))
+    {
+      int nxt = -1;
+      long long f = 0, e = 0;
+      for(int k = 0; k < 8; k++)
+        {
+          const int ch = n_child[8ll * node + k];
+          if(ch < 0 || ch >= nnodes)
+            continue;   // empty, or one particle: no node of the gas-only tree either
+          const long long cf = n_first[ch], ce = cf + n_count[ch];
+          if(p >= cf && p < ce && cf >= 0 && ce <= n)
+            nxt = ch, f = cf, e = ce;
+        }
+      if(nxt < 0 || gc[e] - gc[f] < 2)
+        break;
+      const double m = gm[e] - gm[f];
+      if(!(m >= thr))
+        break;
+      node = nxt;
+      mass = m;
+      level++;
+    }
+  if(n_flags[node] & FLAG_BUCKET)
+    {
+      // below the deepest device level the reference's gas-only tree may go on: halve the cell, keep the half that holds this
+      // particle, with the tree build's own cell coordinates (k_keys) extended by exact powers of two
+      const long long f = n_first[node], e = f + n_count[node];
+      const double ux = __dmul_rn(__dsub_rn(me.x, cx), fac21), uy = __dmul_rn(__dsub_rn(me.y, cy), fac21),
+                   uz = __dmul_rn(__dsub_rn(me.z, cz), fac21);
+      for(int k = 1; k <= SPH_GUESS_SUB && f >= 0 && e <= n; k++)
+        {
+          const double s = (double)(1ll << k);
+          const long long ix = (long long)(ux * s), iy = (long long)(uy * s), iz = (long long)(uz * s);
+          int cnt = 0;
+          double m = 0;
+          for(long long q = f; q < e; q++)
+            {
+              if(type[q] != 0)
+                continue;
+              const double4 o = pm[q];
+              if((long long)(__dmul_rn(__dsub_rn(o.x, cx), fac21) * s) == ix && (long long)(__dmul_rn(__dsub_rn(o.y, cy), fac21) * s) == iy &&
+                 (long long)(__dmul_rn(__dsub_rn(o.z, cz), fac21) * s) == iz)
+                {
+                  cnt++;
+                  m += o.w;
+                }
+            }
+          if(cnt < 2 || !(m >= thr))
+            break;
+          mass = m;
+          level = TREE_BITS + k;
+        }
+    }
+  res[t] = cbrt(3.0 / (4 * M_PI) * des * me.w / mass) * ldexp(len0, -level);   // init.c:246-247
+  row[t] = (int)idx[p];
+}
+
+int sph_hsml_guess_run(ngravs_ctx *c, double des_num_ngb, int only_unset, long long *rows, long long *bad_mass)
+{
+  const long long n = c->n;
+  *rows = *bad_mass = 0;
+  if(c->sph_tlist.ensure((size_t)n) || c->sph_counters.ensure(SPH_C_COUNT + 1) || c->sph_gmass.ensure((size_t)n + 1) ||
+     c->sph_gcount.ensure((size_t)n + 1))
+    return NGRAVS_ERR_NOMEM;
+  HIP_TRY(c, hipMemsetAsync(c->sph_counters.p, 0, (SPH_C_COUNT + 1) * sizeof(unsigned long long), c->stream));
+  hipLaunchKernelGGL(k_sph_gas_cols, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->s_pm.p, c->s_type.p, n, c->sph_gmass.p,
+                     c->sph_gcount.p, c->sph_counters.p);
+  HIP_TRY(c, hipGetLastError());
+  int *d_cnt = reinterpret_cast<int *>(c->sph_counters.p + SPH_C_COUNT);
+  hipcub::CountingInputIterator<int> iota(0);
+  SphIsUnsetGas sel = {c->s_type.p, c->s_idx.p, only_unset ? c->sph_h_in.p : nullptr};
+  size_t b0 = 0, b1 = 0, b2 = 0;
+  HIP_TRY(c, hipcub::DeviceSelect::If(nullptr, b0, iota, c->sph_tlist.p, d_cnt, (int)n, sel, c->stream));
+  HIP_TRY(c, hipcub::DeviceScan::InclusiveSum(nullptr, b1, c->sph_gmass.p + 1, c->sph_gmass.p + 1, (int)n, c->stream));
+  HIP_TRY(c, hipcub::DeviceScan::InclusiveSum(nullptr, b2, c->sph_gcount.p + 1, c->sph_gcount.p + 1, (int)n, c->stream));
+  const size_t bytes = b0 > b1 ? (b0 > b2 ? b0 : b2) : (b1 > b2 ? b1 : b2);
+  if(c->sph_tmp.ensure(bytes))
+    return NGRAVS_ERR_NOMEM;
+  HIP_TRY(c, hipcub::DeviceSelect::If(c->sph_tmp.p, b0, iota, c->sph_tlist.p, d_cnt, (int)n, sel, c->stream));
+  HIP_TRY(c, hipcub::DeviceScan::InclusiveSum(c->sph_tmp.p, b1, c->sph_gmass.p + 1, c->sph_gmass.p + 1, (int)n, c->stream));
+  HIP_TRY(c, hipcub::DeviceScan::InclusiveSum(c->sph_tmp.p, b2, c->sph_gcount.p + 1, c->sph_gcount.p + 1, (int)n, c->stream));
+  unsigned long long h[SPH_C_COUNT + 1];
+  HIP_TRY(c, hipMemcpyAsync(h, c->sph_counters.p, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  *bad_mass = (long long)h[SPH_C_BAD];
+  int cnt;
+  memcpy(&cnt, &h[SPH_C_COUNT], sizeof(int));
+  if(*bad_mass || cnt <= 0)
+    return NGRAVS_OK;   // the caller refuses, or there is nothing to write
+  const long long nl = cnt;
+  if(c->sph_res.ensure((size_t)nl) || c->sph_row.ensure((size_t)nl))
+    return NGRAVS_ERR_NOMEM;
+  const double fac21 = c->dom[7] * (double)(1 << (TREE_BITS - NGRAVS_BITS_PER_DIMENSION));
+  hipLaunchKernelGGL(k_sph_hsml_guess, dim3((unsigned)((nl + 255) / 256)), dim3(256), 0, c->stream, c->n_first.p, c->n_count.p, c->n_child.p,
+                     c->n_flags.p, (int)c->nnodes, c->s_pm.p, c->s_type.p, c->s_idx.p, c->sph_tlist.p, nl, n, c->sph_gmass.p, c->sph_gcount.p,
+                     des_num_ngb, c->dom[0], c->dom[1], c->dom[2], fac21, c->dom[6], c->sph_res.p, c->sph_row.p);
+  HIP_TRY(c, hipGetLastError());
+  *rows = nl;
+  return NGRAVS_OK;
 }
 
 // ---- SPH hydro force --------------------------------------------------------------------------------------------------------

@@ -26,6 +26,11 @@
  * (domain.c:76) and drifts/kicks the node moments instead (predict.c:79-91, timestep.c:331-344); here those steps hand the
  * drifted positions over with ngravs_update_particles() and the library refits the nodes (ngravs_force_update_tree), so
  * force_update_len() and the node drift/kick loops become no-ops (single task only; several tasks always re-decompose).
+ *
+ * -DNGRAVS_GLUE_SPH (gas runs on one task): density.o, hydra.o and ngb.o leave OBJS as well, and this file defines density(),
+ * hydro_force(), ngb_treeallocate(), ngb_treefree() and ngb_treebuild() on ngravs_sph_hsml_guess / ngravs_sph_density /
+ * ngravs_sph_hydro (the section at the end of the file).  init.c stays as it is: see force_treeallocate().  Without the macro
+ * none of this is compiled.
  */
 #ifdef NGRAVS_BUILD_INSIDE_REFERENCE
 
@@ -49,6 +54,23 @@ static ngravs_rccl *Rccl = NULL;
 #endif
 #ifndef UNEQUALSOFTENINGS
 #error "libngravs_hip applies per-type softening lengths: build the reference with -DUNEQUALSOFTENINGS"
+#endif
+#ifdef NGRAVS_GLUE_SPH
+#ifdef TWODIMS
+#error "NGRAVS_GLUE_SPH: TWODIMS is not provided (the SPH calls of libngravs_hip have the 3-D kernel only)"
+#endif
+#ifdef LONG_X
+#error "NGRAVS_GLUE_SPH: LONG_X is not provided (the SPH calls of libngravs_hip wrap a cubic box only)"
+#endif
+#ifdef LONG_Y
+#error "NGRAVS_GLUE_SPH: LONG_Y is not provided (the SPH calls of libngravs_hip wrap a cubic box only)"
+#endif
+#ifdef LONG_Z
+#error "NGRAVS_GLUE_SPH: LONG_Z is not provided (the SPH calls of libngravs_hip wrap a cubic box only)"
+#endif
+#ifdef SPH_BND_PARTICLES
+#error "NGRAVS_GLUE_SPH: SPH_BND_PARTICLES is not provided (ngravs_sph_hydro has no boundary particles, hydra.c:321-327)"
+#endif
 #endif
 
 static ngravs_ctx *Ctx = NULL;
@@ -552,20 +574,48 @@ int force_treebuild(int npart)
   return (int)ngravs_force_treebuild(Ctx);	/* the node count is only reported; Numnodestree (host-side nodes) stays 0 */
 }
 
-/* proto.h:77, :86 -- the device library owns the tree memory */
+/* proto.h:77, :86 -- the device library owns the tree memory.
+ * -DNGRAVS_GLUE_SPH: the kept init.c runs setup_smoothinglengths() (init.c:218-256), whose loop reads Nodes[Father[i]] of every gas
+ * particle before the first density().  Until that density() every Father[i] names ONE host node, DummyNode: father -1, masses 1,
+ * len 0, so the loop breaks at once (init.c:237-240) and leaves Hsml = 0 * pow(...) = 0; density() below finds Hsml unset and asks
+ * the device for the guess (ngravs_sph_hsml_guess).  The node is only read.  The other two host loops over nodes:
+ *   timestep.c:333-343 starts at Father[i] and WRITES Extnodes[no] while no >= 0: it must see Father[i] = -1.  density() sets
+ *     Father[] back to -1 before it does anything else, and advance_and_find_timesteps() runs only after a density() -- of init()
+ *     (init.c:255) or, after a restart from restart files, of the first compute_accelerations() (run.c);
+ *   predict.c:83-86 runs over Numnodestree = 0 nodes: empty. */
+#ifdef NGRAVS_GLUE_SPH
+static struct NODE DummyNode;
+static int FatherLen = 0, FatherOnDummy = 0;
+#endif
 void force_treeallocate(int maxnodes, int maxpart)
 {
   int i;
   (void)maxnodes;
   Father = malloc(sizeof(int) * (maxpart > 0 ? maxpart : 1));	/* timestep.c:333 reads Father[i]: no host-side parents */
+#ifdef NGRAVS_GLUE_SPH
+  memset(&DummyNode, 0, sizeof(DummyNode));
+  for(i = 0; i < N_GRAVS; i++)
+    DummyNode.u.d.mass[i] = 1;
+  DummyNode.u.d.father = -1;
+  DummyNode.len = 0;
+  Nodes = &DummyNode - maxpart;	/* Nodes[maxpart] is the node (forcetree.c: Nodes = Nodes_base - All.MaxPart) */
+  for(i = 0; i < maxpart; i++)
+    Father[i] = maxpart;
+  FatherLen = maxpart;
+  FatherOnDummy = 1;
+#else
   for(i = 0; i < maxpart; i++)
     Father[i] = -1;
+#endif
   Numnodestree = 0;		/* predict.c:83: no host-side nodes to drift */
 }
 void force_treefree(void)
 {
   free(Father);
   Father = NULL;
+#ifdef NGRAVS_GLUE_SPH
+  FatherLen = FatherOnDummy = 0;
+#endif
 }
 
 /* proto.h:184 -- gravtree.c:468-518: the softening table of the six particle types, comoving lengths capped at their
@@ -594,9 +644,10 @@ void set_softenings(void)
     must(ngravs_set_softening(Ctx, All.ForceSoftening), 1069);
 }
 
-/* proto.h:88 -- forcetree.c:1134: hmax of tree nodes that hold SPH particles, for the hydro neighbour search (accel.c:74).  The
- * device tree holds no gas (ensure_ctx refuses SphP[] with several tasks; density()/hydro_force() walk the host-side ngb tree,
- * which this glue does not provide): nothing to update. */
+/* proto.h:88 -- forcetree.c:1134: hmax of tree nodes that hold SPH particles, for the hydro neighbour search (accel.c:74).
+ * ngravs_sph_hydro recomputes the device nodes' hmax from the Hsml column it is handed on every call (hydro_force() below, with
+ * -DNGRAVS_GLUE_SPH; without it the reference's own density.o / hydra.o would need the host-side ngb tree, which this glue does not
+ * provide): nothing to update here. */
 void force_update_hmax(void)
 {
 }
@@ -921,5 +972,230 @@ void peano_hilbert_order(void)
    * gone with pm_periodic.o (the device PM selects species by TypeToGrav[P[].Type]), and count_types() above still maintains
    * NgravLocal[] / NtypeLocal[] / Ntype[] for the kept units that print them. */
 }
+
+#ifdef NGRAVS_GLUE_SPH
+/* ---- gas on one task: density() (density.c:56), hydro_force() (hydra.c:50) and the ngb tree entry points (ngb.c:358-412) ----------
+ * Rows: P[i] and SphP[i] belong together and the gas particles are the first N_gas rows of P[] (the reference's invariant).  SphP[]
+ * holds N_gas rows only (All.MaxPartSph), while the library's columns have one row per particle of P[]: the SphP columns are copied
+ * to columns of NumPart rows (rows of other types: 0, never read as targets or sources) and the targets' results copied back. */
+static double *SphCol = NULL;
+static int32_t *SphTs = NULL;
+static size_t SphColLen = 0;
+static double *sph_columns(int ncol)
+{
+  const size_t n = NumPart > 0 ? (size_t)NumPart : 1, want = n * (size_t)ncol;
+  if(want > SphColLen)
+    {
+      free(SphCol);
+      free(SphTs);
+      SphCol = malloc(sizeof(double) * want);
+      SphTs = malloc(sizeof(int32_t) * n);
+      SphColLen = want;
+      if(!SphCol || !SphTs)
+	{
+	  printf("ngravs-hip: no memory for the SPH columns\n");
+	  endrun(1077);
+	}
+    }
+  memset(SphCol, 0, sizeof(double) * want);
+  memset(SphTs, 0, sizeof(int32_t) * n);
+  return SphCol;
+}
+
+static void sph_begin(void)
+{
+  int i;
+  ensure_ctx();			/* (ends the run for gas on several tasks) */
+  for(i = 0; i < NumPart; i++)
+    if((P[i].Type == 0) != (i < N_gas))
+      {
+	printf("ngravs-hip: row %d of P[] has type %d, N_gas = %d: the gas particles must be the first N_gas rows\n", i, P[i].Type, N_gas);
+	endrun(1078);
+      }
+  if(FatherOnDummy)		/* setup_smoothinglengths() has read the node; timestep.c:333 must find no parents (force_treeallocate) */
+    {
+      for(i = 0; i < FatherLen; i++)
+	Father[i] = -1;
+      FatherOnDummy = 0;
+    }
+}
+
+/* proto.h:138, :142, :139 -- the neighbour search runs on the device tree; Ngblist stays a valid small allocation */
+void ngb_treeallocate(int npart)
+{
+  (void)npart;
+  Ngblist = malloc(sizeof(int));
+}
+void ngb_treefree(void)
+{
+  free(Ngblist);
+  Ngblist = NULL;
+}
+void ngb_treebuild(void)
+{
+  if(ThisTask == 0)
+    printf("Begin Ngb-tree construction.\n");
+  force_treebuild(N_gas);
+  if(ThisTask == 0)
+    printf("Ngb-Tree contruction finished \n");
+}
+
+/* proto.h:27.  Targets are the active type-0 rows (the active flags of the last hand-over, push_particles). */
+void density(void)
+{
+  const double t0 = second();
+  ngravs_sph_in_t in;
+  ngravs_sph_out_t out;
+  double *hsml, *vel, *rho, *nngb, *divv, *curl, *dhs, ms_guess = 0, ms = 0, dev;
+  int32_t rounds = 0;
+  int i, k, unset = 0;
+  size_t n;
+  sph_begin();
+  n = NumPart > 0 ? (size_t)NumPart : 1;
+  hsml = sph_columns(9);
+  vel = hsml + n;
+  rho = vel + 3 * n;
+  nngb = rho + n;
+  divv = nngb + n;
+  curl = divv + n;
+  dhs = curl + n;
+  for(i = 0; i < N_gas; i++)
+    {
+      SphP[i].Left = SphP[i].Right = 0;	/* density.c:95-99 (the iteration's bounds live on the device) */
+      hsml[i] = SphP[i].Hsml;
+      for(k = 0; k < 3; k++)
+	vel[3 * i + k] = SphP[i].VelPred[k];
+      if(P[i].Ti_endstep == All.Ti_Current && !(SphP[i].Hsml > 0))
+	unset++;
+    }
+  /* the state init() leaves (setup_smoothinglengths() on the dummy node, force_treeallocate): the first guess from the device tree */
+  if(unset > 0)
+    must(ngravs_sph_hsml_guess(Ctx, All.DesNumNgb, hsml, sizeof(double), 1, 0, &ms_guess), 1079);
+  memset(&in, 0, sizeof(in));
+  memset(&out, 0, sizeof(out));
+  in.vel_pred = vel;
+  in.vel_stride = 3 * sizeof(double);
+  in.hsml = hsml;
+  in.hsml_stride = sizeof(double);
+  in.des_num_ngb = All.DesNumNgb;
+  in.max_num_ngb_deviation = All.MaxNumNgbDeviation;
+  in.min_gas_hsml = All.MinGasHsml;
+  out.density = rho;
+  out.num_ngb = nngb;
+  out.div_vel = divv;
+  out.curl_vel = curl;
+  out.dhsml_factor = dhs;
+  out.density_stride = out.num_ngb_stride = out.div_vel_stride = out.curl_vel_stride = out.dhsml_factor_stride = sizeof(double);
+  /* more than MAXITER rounds: the library calls on_fatal with 1155, the reference's endrun(1155) (density.c:416-421) */
+  must(ngravs_sph_density(Ctx, &in, &out, &rounds, &ms), 1080);
+  for(i = 0; i < N_gas; i++)
+    if(P[i].Ti_endstep == All.Ti_Current)
+      {
+	double dt_entr;
+	SphP[i].Hsml = hsml[i];
+	SphP[i].Density = rho[i];
+	SphP[i].NumNgb = nngb[i];
+	SphP[i].DivVel = divv[i];
+	SphP[i].CurlVel = curl[i];	/* (SphP[].Rot is not filled: only density() itself reads it) */
+	SphP[i].DhsmlDensityFactor = dhs[i];
+	dt_entr = (All.Ti_Current - (P[i].Ti_begstep + P[i].Ti_endstep) / 2) * All.Timebase_interval;	/* density.c:305-308 */
+	SphP[i].Pressure = (SphP[i].Entropy + SphP[i].DtEntropy * dt_entr) * pow(SphP[i].Density, GAMMA);
+      }
+  /* density.c:454-457.  Device time is the walk; what the call spends beside it (columns to the device and back) is booked as
+   * communication; one task has no imbalance; the library does not report the share of the rounds after the first, so
+   * CPU_EnsureNgb gets 0 */
+  dev = 1e-3 * (ms_guess + ms);
+  All.CPU_HydCompWalk += dev;
+  All.CPU_HydCommSumm += timediff(t0, second()) > dev ? timediff(t0, second()) - dev : 0;
+  All.CPU_HydImbalance += 0;
+  All.CPU_EnsureNgb += 0;
+}
+
+/* proto.h:120 */
+void hydro_force(void)
+{
+  const double t0 = second();
+  ngravs_hydro_in_t in;
+  ngravs_hydro_out_t out;
+  double *vel, *hsml, *rho, *press, *dhs, *divv, *curl, *acc, *dte, *msv, ms = 0, dev;
+  int i, k;
+  size_t n;
+  sph_begin();
+  n = NumPart > 0 ? (size_t)NumPart : 1;
+  vel = sph_columns(14);
+  hsml = vel + 3 * n;
+  rho = hsml + n;
+  press = rho + n;
+  dhs = press + n;
+  divv = dhs + n;
+  curl = divv + n;
+  acc = curl + n;
+  dte = acc + 3 * n;
+  msv = dte + n;
+  for(i = 0; i < N_gas; i++)
+    {
+      for(k = 0; k < 3; k++)
+	vel[3 * i + k] = SphP[i].VelPred[k];
+      hsml[i] = SphP[i].Hsml;
+      rho[i] = SphP[i].Density;
+      press[i] = SphP[i].Pressure;
+      dhs[i] = SphP[i].DhsmlDensityFactor;
+      divv[i] = SphP[i].DivVel;
+      curl[i] = SphP[i].CurlVel;
+      SphTs[i] = P[i].Ti_endstep - P[i].Ti_begstep;	/* hydra.c:372 */
+    }
+  memset(&in, 0, sizeof(in));
+  memset(&out, 0, sizeof(out));
+  in.vel_pred = vel;
+  in.vel_pred_stride = 3 * sizeof(double);
+  in.hsml = hsml;
+  in.density = rho;
+  in.pressure = press;
+  in.dhsml_factor = dhs;
+  in.div_vel = divv;
+  in.curl_vel = curl;
+  in.hsml_stride = in.density_stride = in.pressure_stride = in.dhsml_factor_stride = in.div_vel_stride = in.curl_vel_stride = sizeof(double);
+  in.timestep = SphTs;
+  in.timestep_stride = sizeof(int32_t);
+  in.art_bulk_visc_const = All.ArtBulkViscConst;
+  in.timebase_interval = All.Timebase_interval;
+  in.gamma = GAMMA;		/* 1 under ISOTHERM_EQS, else 5/3 (allvars.h:49-55) */
+#ifdef NOVISCOSITYLIMITER
+  in.viscosity_limiter = 0;
+#else
+  in.viscosity_limiter = 1;
+#endif
+  if(All.ComovingIntegrationOn)	/* hydra.c:78-97 */
+    {
+      double hubble_a = All.Omega0 / (All.Time * All.Time * All.Time) + (1 - All.Omega0 - All.OmegaLambda) / (All.Time * All.Time) + All.OmegaLambda;
+      hubble_a = All.Hubble * sqrt(hubble_a);
+      in.comoving = 1;
+      in.hubble_a2 = All.Time * All.Time * hubble_a;
+      in.fac_mu = pow(All.Time, 3 * (GAMMA - 1) / 2) / All.Time;
+      in.fac_vsic_fix = hubble_a * pow(All.Time, 3 * GAMMA_MINUS1);
+    }
+  else
+    in.hubble_a2 = in.fac_mu = in.fac_vsic_fix = 1.0;
+  out.hydro_accel = acc;
+  out.hydro_accel_stride = 3 * sizeof(double);
+  out.dt_entropy = dte;
+  out.max_signal_vel = msv;
+  out.dt_entropy_stride = out.max_signal_vel_stride = sizeof(double);
+  must(ngravs_sph_hydro(Ctx, &in, &out, &ms), 1081);
+  for(i = 0; i < N_gas; i++)
+    if(P[i].Ti_endstep == All.Ti_Current)
+      {
+	for(k = 0; k < 3; k++)
+	  SphP[i].HydroAccel[k] = acc[3 * i + k];
+	SphP[i].DtEntropy = dte[i];	/* with the final factor of hydra.c:320 */
+	SphP[i].MaxSignalVel = msv[i];
+      }
+  /* hydra.c:342-344, as in density() */
+  dev = 1e-3 * ms;
+  All.CPU_HydCompWalk += dev;
+  All.CPU_HydCommSumm += timediff(t0, second()) > dev ? timediff(t0, second()) - dev : 0;
+  All.CPU_HydImbalance += 0;
+}
+#endif /* NGRAVS_GLUE_SPH */
 
 #endif /* NGRAVS_BUILD_INSIDE_REFERENCE */

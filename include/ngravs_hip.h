@@ -517,6 +517,17 @@ typedef struct {   /* any pointer may be NULL; strides in bytes; rows = own rows
 /* max_rounds, kernel_ms may be NULL: the most evaluations any target took; device time of the call (HIP events) */
 int ngravs_sph_density(ngravs_ctx *ctx, const ngravs_sph_in_t *in, const ngravs_sph_out_t *out, int32_t *max_rounds,
                        double *kernel_ms);
+/* The first guess of the smoothing lengths: the loop of setup_smoothinglengths() (init.c:229-247, 3-D branch) for ONE task, on the
+ * device tree.  The reference's rule, on its gas-only tree in the domain cube of all particles: from the deepest cell that holds
+ * particle i and at least one more gas particle, climb while 10 DesNumNgb m_i > (gas mass of the cell), stop at the root; then
+ * Hsml = cbrt(3 / (4 pi) DesNumNgb m_i / mass) * (side of the cell).  hsml (stride in bytes, own rows) is written for every own
+ * type-0 row; with only_unset != 0 only for those whose current value is not > 0.  hsml addresses one value per own row; those
+ * of rows of other types are never used and never written.  Needs a built tree of the current particle set (NGRAVS_ERR_STATE otherwise; after ngravs_update_particles the tree is
+ * refit first); NGRAVS_ERR_STATE, "single task only": world_size > 1 or a multi-task working set.  NGRAVS_ERR_ARG: hsml NULL,
+ * des_num_ngb <= 0, a type-0 row whose mass is <= 0 or not finite (nothing is written then).  No type-0 row: success, nothing
+ * written.  The tree, the walk's state and the stored accelerations are not modified.  kernel_ms may be NULL. */
+int ngravs_sph_hsml_guess(ngravs_ctx *ctx, double des_num_ngb, double *hsml, int64_t hsml_stride, int32_t only_unset, int32_t on_device,
+                          double *kernel_ms);
 /* GPU-free: the spline and its derivative as the device code evaluates them, wk[i], dwk[i] at r[i] for smoothing length h
  * (0 where r >= h) */
 int ngravs_sph_kernel(double h, const double *r, int64_t n, double *wk, double *dwk);

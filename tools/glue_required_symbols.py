@@ -9,6 +9,9 @@ reference lines where they are defined / used -- and tests/test_host_glue.py ass
 every one of them, for each option set.
 
 usage: python tools/glue_required_symbols.py [/root/reference] > tests/golden/glue_required_symbols.json
+       python tools/glue_required_symbols.py --sph [/root/reference] > tests/golden/glue_required_symbols_sph.json
+
+--sph: the extended recipe of a gas run (-DNGRAVS_GLUE_SPH): density.o, hydra.o and ngb.o are dropped as well.
 """
 import json
 import os
@@ -16,6 +19,7 @@ import re
 import sys
 
 DROPPED = ["gravtree.c", "forcetree.c", "pm_periodic.c", "domain.c", "peano.c", "gravtree_forcetest.c"]
+DROPPED_SPH = DROPPED + ["density.c", "hydra.c", "ngb.c"]
 # units of Makefile.reference's OBJS (Makefile.reference:164-171); pm_nonperiodic.c is compiled but ngravs disables it
 NOT_UNITS = {"allvars.c"}   # globals live here; it defines no functions
 
@@ -61,11 +65,13 @@ def definitions(path):
 
 
 def main():
-    ref = sys.argv[1] if len(sys.argv) > 1 else "/root/reference"
+    args = [a for a in sys.argv[1:] if a != "--sph"]
+    dropped = DROPPED_SPH if "--sph" in sys.argv[1:] else DROPPED
+    ref = args[0] if args else "/root/reference"
     units = sorted(f for f in os.listdir(ref) if f.endswith(".c") and f not in NOT_UNITS)
-    kept = [u for u in units if u not in DROPPED]
+    kept = [u for u in units if u not in dropped]
     defs = {}
-    for u in DROPPED:
+    for u in dropped:
         for name, (line, guard) in definitions(os.path.join(ref, u)).items():
             defs.setdefault(name, {"defined": "%s:%d" % (u, line), "guards": guard, "used_by": []})
     for u in kept:
@@ -78,7 +84,7 @@ def main():
                     rec["used_by"].append("%s:%d" % (u, no))
                     break
     need = {k: v for k, v in sorted(defs.items()) if v["used_by"]}
-    json.dump({"recipe_drops": DROPPED, "kept_units": kept,
+    json.dump({"recipe_drops": dropped, "kept_units": kept,
                "note": "non-static functions the dropped units define and a kept unit calls; names + reference lines only",
                "required": need}, sys.stdout, indent=1)
     sys.stdout.write("\n")

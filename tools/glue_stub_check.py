@@ -9,6 +9,10 @@ signature would compile and test green.  This script reads the reference's heade
 every struct field, global and prototype the stubs declare, what the reference declares under that name:
 
   python tools/glue_stub_check.py [/root/reference] > tests/golden/glue_stub_check.json
+  python tools/glue_stub_check.py --sph [/root/reference] > tests/golden/glue_stub_sph_check.json
+
+--sph: the stubs of a gas run, tests/glue_stub_sph/{allvars,proto}.h (ngravs.h still comes from tests/glue_stub/), with struct
+sph_particle_data and struct NODE next to the two structs above.
 
 It runs in the build container (/root/reference is not on the GPU box); the output is data (names, types, array extents, the
 order of struct fields, reference line numbers).  tests/test_host_glue.py::test_stubs_declare_what_the_reference_declares
@@ -121,14 +125,23 @@ def read(path):
 
 
 STRUCTS = {"allvars.h": ["global_data_all_processes", "particle_data"]}
+STUB_SPH = os.path.join(ROOT, "tests", "glue_stub_sph")
+STRUCTS_SPH = {"allvars.h": ["global_data_all_processes", "particle_data", "sph_particle_data", "NODE"]}
 
 
-def describe(ref_dir):
+def stub_header(stub_dir, hdr):
+    """a header the directory does not hold comes from tests/glue_stub/ (the second -I of the compile line)"""
+    path = os.path.join(stub_dir, hdr)
+    return path if os.path.exists(path) else os.path.join(STUB, hdr)
+
+
+def describe(ref_dir, stub_dir=STUB, structs=None):
     """what the reference declares under every name the stubs declare"""
+    structs = STRUCTS if structs is None else structs
     out = {"reference": "names, types, extents and line numbers only", "structs": {}, "globals": {}, "prototypes": {}, "missing_in_reference": []}
     for hdr in ("allvars.h", "proto.h", "ngravs.h"):
-        stub, ref = read(os.path.join(STUB, hdr)), read(os.path.join(ref_dir, hdr))
-        for sname in STRUCTS.get(hdr, []):
+        stub, ref = read(stub_header(stub_dir, hdr)), read(os.path.join(ref_dir, hdr))
+        for sname in structs.get(hdr, []):
             rf = struct_fields(ref, sname)
             rmap = {}
             for k, f in enumerate(rf):   # a field declared under several #ifdef branches: all its forms, the first one's place
@@ -159,12 +172,13 @@ def describe(ref_dir):
     return out
 
 
-def stub_view():
+def stub_view(stub_dir=STUB, structs=None):
     """the stubs parsed the same way (the test compares this with the committed JSON)"""
+    structs = STRUCTS if structs is None else structs
     out = {"structs": {}, "globals": {}, "prototypes": {}}
     for hdr in ("allvars.h", "proto.h", "ngravs.h"):
-        stub = read(os.path.join(STUB, hdr))
-        for sname in STRUCTS.get(hdr, []):
+        stub = read(stub_header(stub_dir, hdr))
+        for sname in structs.get(hdr, []):
             out["structs"][sname] = [(f[0], f[1], f[2]) for f in struct_fields(stub, sname)]
         for name, (t, ext, _) in globals_(stub).items():
             out["globals"][name] = (t, ext)
@@ -174,6 +188,8 @@ def stub_view():
 
 
 if __name__ == "__main__":
-    ref = sys.argv[1] if len(sys.argv) > 1 else "/root/reference"
-    json.dump(describe(ref), sys.stdout, indent=1, sort_keys=True)
+    args = [a for a in sys.argv[1:] if a != "--sph"]
+    ref = args[0] if args else "/root/reference"
+    sph = "--sph" in sys.argv[1:]
+    json.dump(describe(ref, STUB_SPH, STRUCTS_SPH) if sph else describe(ref), sys.stdout, indent=1, sort_keys=True)
     sys.stdout.write("\n")
