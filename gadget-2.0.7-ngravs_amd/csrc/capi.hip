@@ -1047,9 +1047,14 @@ static bool overlap_eligible(const ngravs_ctx *c)
          c->n > 0 && c->n_local > 0;
 }
 
-// The walk (traversal, evaluation, k_finish).  pm_done: PM was enqueued on pm_stream beside it, and k_finish waits for that event.
-static int gravity_tree_impl(ngravs_ctx *c, hipEvent_t pm_done)
+// The walk (traversal, evaluation, k_finish) in two halves, so that the host can enqueue PM on pm_stream between them: the walk
+// needs nothing from PM, and its first kernel should be in the queue when the tree is done, not behind the host's work on PM's
+// launches.
+// First half: tree and tables made sure of, every launch of the walk enqueued.  beside_pm: PM runs on pm_stream beside it.
+// *masked: the walk went to walk_stream; *empty: this task has no targets (nothing enqueued, nothing to finish).
+static int gravity_tree_begin(ngravs_ctx *c, bool beside_pm, bool *masked, bool *empty)
 {
+  *masked = *empty = false;
   if(!c || !c->have_order)
     return NGRAVS_ERR_STATE;
   (void)hipSetDevice(c->cfg.device);
@@ -1071,23 +1076,36 @@ static int gravity_tree_impl(ngravs_ctx *c, hipEvent_t pm_done)
       c->stats.interactions = 0;
       c->stats.n_active = 0;
       c->have_acc = true;
+      *empty = true;
       return NGRAVS_OK;
     }
   HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
   // the walk alone on walk_stream: beside PM, or (stand-alone calls) when the pm_cus knob forces the masked streams
-  const bool masked = (pm_done || (c->tune.pm_cus > 0 && overlap_eligible(c))) && masked_streams(c, pm_done ? c->pm_stream_cus : c->tune.pm_cus) == NGRAVS_OK;
-  if(masked)
+  *masked = (beside_pm || (c->tune.pm_cus > 0 && overlap_eligible(c))) && masked_streams(c, beside_pm ? c->pm_stream_cus : c->tune.pm_cus) == NGRAVS_OK;
+  if(*masked)
     {
       HIP_TRY(c, hipStreamWaitEvent(c->walk_stream, c->ev0, 0));
+      OnStream on(c, c->walk_stream, c->device_cus - c->pm_stream_cus);
+      return walk_enqueue(c);
+    }
+  return walk_enqueue(c);
+}
+
+// Second half: waits for the walk, then k_finish.  pm_done: PM was enqueued on pm_stream beside it, and k_finish waits for that event.
+static int gravity_tree_end(ngravs_ctx *c, bool masked, hipEvent_t pm_done)
+{
+  int rc;
+  if(masked)
+    {
       {
         OnStream on(c, c->walk_stream, c->device_cus - c->pm_stream_cus);
-        if((rc = walk_run(c)))
+        if((rc = walk_complete(c)))
           return rc;
       }
       HIP_TRY(c, hipEventRecord(c->ev_walk, c->walk_stream));
       HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_walk, 0));
     }
-  else if((rc = walk_run(c)))
+  else if((rc = walk_complete(c)))
     return rc;
   if(pm_done)
     HIP_TRY(c, hipStreamWaitEvent(c->stream, pm_done, 0));
@@ -1129,7 +1147,12 @@ static int gravity_tree_impl(ngravs_ctx *c, hipEvent_t pm_done)
   return NGRAVS_OK;
 }
 
-extern "C" int ngravs_gravity_tree(ngravs_ctx *c) { return gravity_tree_impl(c, nullptr); }
+extern "C" int ngravs_gravity_tree(ngravs_ctx *c)
+{
+  bool masked, empty;
+  const int rc = gravity_tree_begin(c, false, &masked, &empty);
+  return (rc || empty) ? rc : gravity_tree_end(c, masked, nullptr);
+}
 
 // PM on pm_stream, after what c->stream holds so far; the span is timed by ev_pm0 / ev_pm1
 static int pm_on_masked_stream(ngravs_ctx *c)
@@ -1232,9 +1255,13 @@ extern "C" int ngravs_compute_accelerations(ngravs_ctx *c, int pm_step)
       int64_t nn = ngravs_force_treebuild(c);
       if(nn < 0)
         return (int)nn;
+      // the walk's launches first: its traversal starts when the tree is done, while the host is still enqueuing PM
+      bool masked, empty;
+      if((rc = gravity_tree_begin(c, true, &masked, &empty)))
+        return rc;
       if((rc = pm_on_masked_stream(c)))
         return rc;
-      if((rc = gravity_tree_impl(c, c->ev_pm1)))
+      if(!empty && (rc = gravity_tree_end(c, masked, c->ev_pm1)))
         return rc;
       float ms = 0;
       (void)hipEventElapsedTime(&ms, c->ev_pm0, c->ev_pm1);   // (complete: k_finish waited for it)

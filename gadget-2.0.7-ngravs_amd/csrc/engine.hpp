@@ -6,7 +6,7 @@
 //                                   s_active[n] u8  s_key[n] u64 (21 bits/dim)  s_idx[n] u32
 //   tree (breadth-first, level-contiguous): n_first/n_count (particle range), n_child[8*nodes]
 //       (>=0 node, -1 empty, <=-2 particle -2-p), n_geo = double4{cx,cy,cz,len},
-//       n_mom[nodes*NG] = double4{sx,sy,sz,mass}, n_flags (reference bitflags bits 2-5), n_level
+//       n_mom[nodes*NG] = double4{sx,sy,sz,mass}, n_flags (reference bitflags bits 2-5, FLAG_*), n_level
 //   results, Peano order          : r_acc[3n] r_nint[n] r_pm[3n] r_oldacc[n]
 #pragma once
 #include <hip/hip_runtime.h>
@@ -15,6 +15,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 #include "../../include/ngravs_host.h"
 
@@ -25,6 +26,12 @@
 #define FLAG_BUCKET 64     // bit 6: the node holds its particles directly (deepest level)
 #define FLAG_PSEUDO 128    // bit 7: top-level cell whose particles live on another task: global monopoles, no children
 #define FLAG_PARTIAL 256   // bit 8: the cell contains particles that are not on this task (never handed over as a leaf)
+// bits 9-24: source species (type_to_grav & 3) of up to 8 particles, 2 bits each, written by k_moments for the group walk.
+//   range-coded node (FLAG_BUCKET, or at most FLAG_SPECIES_SLOTS particles and not FLAG_PARTIAL): field q = particle first + q
+//   any other node: field q = the particle in child slot q (child <= -2)
+#define FLAG_SPECIES_SHIFT 9
+#define FLAG_SPECIES_SLOTS 8
+#define FLAG_SPECIES_MASK (0xffff << FLAG_SPECIES_SHIFT)
 #define MAX_LEVELS (TREE_BITS + 1)
 
 struct ngravs_ctx;
@@ -333,6 +340,11 @@ struct ngravs_ctx
   int walk_batches = 0;               // batches of the last split walk (0: fused kernel)
   int walk_lcap = 0;                  // split walk: item-list capacity per group and species (grown on overflow)
   int walk_scap = 0;                  // split walk: LIFO capacity per group (grown on overflow)
+  bool walk_used_split = false;       // walk_enqueue -> walk_complete: the split kernels ran (leftover units may follow)
+  long long walk_cap_n = -1;          // split walk: scratch budget from hipMemGetInfo, asked again only when the particle count or
+  size_t walk_cap_stack = 0;          // the size of the scratch itself has changed
+  size_t walk_cap_bytes = 0;
+  std::vector<std::pair<const void *, size_t>> walk_lds_set;   // walk kernels whose dynamic-LDS limit is set, and to what
   std::string last_error;
   // user-defined laws (ngravs_create_with_laws)
   std::vector<ngravs_user_fn_t> user_fns;
@@ -456,7 +468,9 @@ int user_green_ensure(ngravs_ctx *c);   // PM: the G(k2) tables of the user gree
 double user_normed(const ngravs_user_fn_t *fns, int nfns, int law, double k2);
 // ---- kernels_walk.hip
 void make_walk_params(const ngravs_ctx *c, WalkParams *wp);
-int walk_run(ngravs_ctx *c);
+int walk_run(ngravs_ctx *c);        // walk_enqueue + walk_complete
+int walk_enqueue(ngravs_ctx *c);
+int walk_complete(ngravs_ctx *c);
 int walk_finish(ngravs_ctx *c);
 int direct_run(ngravs_ctx *c, const int *d_idx, int64_t nt, double *d_acc);
 int direct_run_targets(ngravs_ctx *c, const double4 *d_tpm, const int *d_ttype, int64_t nt, double *d_acc, double r_need = 0);

@@ -567,6 +567,10 @@ __global__ void k_moments(const double4 *__restrict__ s_pm, const unsigned char 
   sa.diff = 0;
   int cnt_acc = 0;   // particles below this node (one-pass build: the counts are not known before this pass)
   int fl = n_flags[node];
+  // source species of the node's particles for the group walk (FLAG_SPECIES_*), in both orders: by child slot, and by position
+  // in the particle range (the children are visited in key order, which is the order of the range)
+  unsigned sp_slot = 0, sp_range = 0;
+  auto species = [&](const int ty) { return (wp.t2g_packed >> (2 * ty)) & 3u; };
   // refit of a drifted tree (geo_rw != 0): the node keeps its centre but its side grows to enclose whatever its particles
   // and (already grown) child cells now reach, the role of force_update_len() (forcetree.c:1005-1122)
   const double4 geo0 = n_geo[node];
@@ -588,7 +592,7 @@ __global__ void k_moments(const double4 *__restrict__ s_pm, const unsigned char 
     soft_merge(sa, ty, 0, wp.fsoft);
     cnt_acc++;
   };
-  auto add_particle = [&](int p) {
+  auto add_particle = [&](int p) -> int {
     double4 v = s_pm[p];
     if(geo_rw)
       need = fmax(need, fmax(fabs(v.x - geo0.x), fmax(fabs(v.y - geo0.y), fabs(v.z - geo0.z))));
@@ -606,12 +610,17 @@ __global__ void k_moments(const double4 *__restrict__ s_pm, const unsigned char 
         }
     soft_merge(sa, ty, 0, wp.fsoft);
     cnt_acc++;
+    return ty;
   };
   if(fl & FLAG_BUCKET)
     {
       int f = n_first[node], cnt = n_count[node];
       for(int p = f; p < f + cnt; p++)
-        add_particle(p);
+        {
+          const int ty = add_particle(p);
+          if(NG > 1 && p - f < FLAG_SPECIES_SLOTS)
+            sp_range |= species(ty) << (2 * (p - f));
+        }
     }
   else
     {
@@ -644,8 +653,7 @@ __global__ void k_moments(const double4 *__restrict__ s_pm, const unsigned char 
                   for(int g = 0; g < NG; g++)
                     rec[q][g] = n_mom[(long long)c * NG + g];
                   aux[q] = n_flags[c];
-                  if(n_count_rw)
-                    cnt_c[q] = n_count_rw[c];
+                  cnt_c[q] = n_count[c];   // (one-pass build: written by the launch of the level below)
                 }
             }
 #pragma unroll
@@ -655,7 +663,16 @@ __global__ void k_moments(const double4 *__restrict__ s_pm, const unsigned char 
               if(c == -1)
                 continue;
               if(c <= -2)
-                add_particle_v(rec[q][0], aux[q]);
+                {
+                  if(NG > 1)
+                    {
+                      const unsigned sg = species(aux[q]);
+                      sp_slot |= sg << (2 * (k0 + q));
+                      if(cnt_acc < FLAG_SPECIES_SLOTS)
+                        sp_range |= sg << (2 * cnt_acc);
+                    }
+                  add_particle_v(rec[q][0], aux[q]);
+                }
               else
                 {
 #pragma unroll
@@ -671,6 +688,8 @@ __global__ void k_moments(const double4 *__restrict__ s_pm, const unsigned char 
                     }
                   const int cf = aux[q];
                   soft_merge(sa, (cf >> 2) & 7, (cf >> 5) & 1, wp.fsoft);
+                  if(NG > 1 && cnt_acc < FLAG_SPECIES_SLOTS)   // (only used if this node is range-coded: then the child is too)
+                    sp_range |= (((unsigned)cf >> FLAG_SPECIES_SHIFT) & 0xffffu) << (2 * cnt_acc);
                   cnt_acc += cnt_c[q];
                   if(geo_rw)
                     {
@@ -708,7 +727,11 @@ __global__ void k_moments(const double4 *__restrict__ s_pm, const unsigned char 
       if(n_npart)
         n_npart[(long long)node * NG + g] = np[g];
     }
-  n_flags[node] = (fl & (FLAG_BUCKET | FLAG_PSEUDO | FLAG_PARTIAL)) | (4 * sa.maxsofttype + 32 * sa.diff);
+  // the walk hands a bucket, or a whole node of at most 8 particles, over as the range first ... first + count - 1 (k_walk_group2)
+  const int cnt_node = (n_count_rw && !(fl & FLAG_BUCKET)) ? cnt_acc : n_count[node];
+  const bool range_coded = (fl & FLAG_BUCKET) || (cnt_node <= FLAG_SPECIES_SLOTS && !(fl & FLAG_PARTIAL));
+  const unsigned sp = NG > 1 ? ((range_coded ? sp_range : sp_slot) & 0xffffu) : 0u;
+  n_flags[node] = (fl & (FLAG_BUCKET | FLAG_PSEUDO | FLAG_PARTIAL)) | (4 * sa.maxsofttype + 32 * sa.diff) | (int)(sp << FLAG_SPECIES_SHIFT);
   if(n_count_rw && !(fl & FLAG_BUCKET))
     n_count_rw[node] = cnt_acc;
 }
@@ -756,7 +779,8 @@ __global__ void k_top_moments(const int *__restrict__ n_top, const int *__restri
   for(int ty = 0; ty < NGRAVS_NTYPES; ty++)
     if(s[1 + ty] > 0)
       soft_merge(sa, ty, 0, wp.fsoft);
-  n_flags[node] = (fl & (FLAG_BUCKET | FLAG_PSEUDO | FLAG_PARTIAL)) | (4 * sa.maxsofttype + 32 * sa.diff);
+  // (the species field of k_moments stays: the local particle children of a split top node are what they were)
+  n_flags[node] = (fl & (FLAG_BUCKET | FLAG_PSEUDO | FLAG_PARTIAL | FLAG_SPECIES_MASK)) | (4 * sa.maxsofttype + 32 * sa.diff);
 }
 
 static int tree_top_moments(ngravs_ctx *c)

@@ -610,6 +610,7 @@ __global__ __launch_bounds__(256) void k_walk_strict(TreeView tv, const double4 
 // per wave: [NULL entry (double4)] [128 x double4 position/mass] [4 x 128 floats] [128 type bytes] -- 16-byte multiple
 #define GW2_WAVE_LDS (sizeof(double4) + (sizeof(double4) + 4 * sizeof(float) + 1) * 128)
 #define GW_NLEAF 8          // an opened node with <= NLEAF particles hands over its particles directly
+static_assert(GW_NLEAF <= FLAG_SPECIES_SLOTS, "a node handed over as a leaf must be range-coded (k_moments)");
 
 // =============================================================================================
 //  group walk: traversal and force evaluation are separate phases per group (and, by default, separate kernels).
@@ -1668,7 +1669,9 @@ __global__ __launch_bounds__(MODE == 1 ? GW3_TBLOCK : (MODE == 2 ? GW2_MAXWAVES 
           // decision: 0 drop, 1 accept (monopoles), 2 open (children), 3 open as a leaf (all particles of the range)
           int dec = 0;
           int first = 0, count = 0;
-          unsigned massmask = 0;
+          // one register for what the record step needs of the node: accepted (dec 1): the species with mass, one bit each;
+          // opened (dec >= 2): bit 0 FLAG_PARTIAL, bits 1-16 the node's species field (FLAG_SPECIES_*)
+          unsigned info = 0;
           bool pseudo_hit = false;
           int4 ch_lo = {-1, -1, -1, -1}, ch_hi = {-1, -1, -1, -1};
           if(my >= 0)
@@ -1701,6 +1704,7 @@ __global__ __launch_bounds__(MODE == 1 ? GW3_TBLOCK : (MODE == 2 ? GW2_MAXWAVES 
                 {
                   first = tv.first[my];
                   count = tv.count[my];
+                  unsigned massmask = 0;
                   double r2min = BIG, r2far = 0, summass = 0;   // r2far: the largest of the species' distances, each to the nearest point of the box
 #pragma unroll
                   for(int g = 0; g < NG; g++)
@@ -1760,6 +1764,8 @@ __global__ __launch_bounds__(MODE == 1 ? GW3_TBLOCK : (MODE == 2 ? GW2_MAXWAVES 
                         dec = ((fl & FLAG_BUCKET) || (count <= wp.nleaf && !(fl & FLAG_PARTIAL))) ? 3 : 2;
                       else
                         dec = 1;
+                      static_assert(FLAG_PARTIAL << 1 == 1 << FLAG_SPECIES_SHIFT, "one shift takes both out of the flags word");
+                      info = open ? (NG > 1 ? ((unsigned)fl >> (FLAG_SPECIES_SHIFT - 1)) & 0x1ffffu : 0u) : massmask;
                     }
                 }
             }
@@ -1778,34 +1784,29 @@ __global__ __launch_bounds__(MODE == 1 ? GW3_TBLOCK : (MODE == 2 ? GW2_MAXWAVES 
 #pragma unroll
           for(int g = 0; g < NG; g++)
             {
-              const bool pg = dec == 1 && ((massmask >> g) & 1u);
+              const bool pg = dec == 1 && ((info >> g) & 1u);
               unsigned long long mask = __ballot(pg ? 1 : 0);
               if(pg)
                 lists[g][n_items[g] + lane_prefix(mask)] = -1 - (my * NG + g);
               n_items[g] += __popcll(mask);
             }
           const int chv[8] = {ch_lo.x, ch_lo.y, ch_lo.z, ch_lo.w, ch_hi.x, ch_hi.y, ch_hi.z, ch_hi.w};
-          // source species of the (up to 8) particles this lane is about to record, 2 bits each: eight independent
-          // byte loads in flight instead of one dependent load per ballot round
-          unsigned sp8 = 0;
+          // source species of the (up to 8) particles this lane is about to record, 2 bits each: the node's species field, which
+          // the build wrote in the order the items are recorded in -- by position in the range for a node handed over as a leaf
+          // (dec 3: always range-coded, wp.nleaf <= FLAG_SPECIES_SLOTS), by child slot for a node opened child by child
+          unsigned sp8 = NG > 1 ? info >> 1 : 0u;   // only the fields of real items are read later
           if(NG > 1)
             {
-              // unconditional loads (index 0 when there is nothing to look up): all eight are in flight before the first
-              // is used; a predicated load per slot made the compiler wait for each in turn
-              unsigned char ty8[8];
-#pragma unroll
-              for(int q = 0; q < 8; q++)
+              // a small node opened child by child (walk_nleaf below 8; never a bucket) is range-coded: particle p is field p - first
+              const bool remap = dec == 2 && count <= FLAG_SPECIES_SLOTS && !(info & 1u);
+              if(__any(remap))
                 {
-                  int pi = 0;
-                  if(dec == 2 && chv[q] <= -2)
-                    pi = -2 - chv[q];
-                  if(dec == 3 && q < count)
-                    pi = first + q;
-                  ty8[q] = s_type[pi];
-                }
+                  unsigned r = 0;
 #pragma unroll
-              for(int q = 0; q < 8; q++)
-                sp8 |= ((wp.t2g_packed >> (2 * ty8[q])) & 3u) << (2 * q);   // only the fields of real items are read later
+                  for(int q = 0; q < 8; q++)
+                    r |= ((sp8 >> (2 * ((-2 - chv[q] - first) & 7))) & 3u) << (2 * q);
+                  sp8 = remap ? r : sp8;
+                }
             }
           // ---- append: every lane holds up to 8 things to record -- child nodes for the LIFO (dec 2) and particles for the
           //      item lists (children of an opened node, or the first 8 particles of a small node's range, dec 3).  One packed
@@ -2485,6 +2486,24 @@ static EvalLds eval_lds(const WalkParams &wp, bool tables, int max_waves)
   return {waves, fixed + (size_t)waves * GW2_WAVE_LDS};
 }
 
+// hipFuncAttributeMaxDynamicSharedMemorySize of a walk kernel: set when the kernel is first launched with this size, not on every
+// step (the call takes the runtime's locks in front of the step's first walk launch)
+static int walk_dyn_lds(ngravs_ctx *c, const void *kern, size_t lds)
+{
+  for(auto &e : c->walk_lds_set)
+    if(e.first == kern)
+      {
+        if(e.second == lds)
+          return NGRAVS_OK;
+        HIP_TRY(c, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        e.second = lds;
+        return NGRAVS_OK;
+      }
+  HIP_TRY(c, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  c->walk_lds_set.emplace_back(kern, lds);
+  return NGRAVS_OK;
+}
+
 template <int NG, int PM, int YUK, int TAB_LDS, int LATT, int USR>
 static int launch_group2_t(Row<NG, PM, YUK, TAB_LDS, LATT, USR>, ngravs_ctx *c, const WalkParams &wp, int *glist, int nlist)
 {
@@ -2515,7 +2534,8 @@ static int launch_group2_t(Row<NG, PM, YUK, TAB_LDS, LATT, USR>, ngravs_ctx *c, 
   else
     HIP_TRY(c, hipMemsetAsync(c->walk_counters.p, 0, sizeof(int) * 32, c->stream));
   auto kern = k_walk_group2<NG, PM, YUK, TAB_LDS, LATT, 0, USR>;
-  HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  if(int rl = walk_dyn_lds(c, reinterpret_cast<const void *>(kern), lds))
+    return rl;
   hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(waves * 64), lds, c->stream, tree_view(c), c->s_pm.p,
                      c->s_type.p, c->s_oldacc.p, c->s_active.p, LATT ? c->lat.p : c->table.p, wp, (long long)c->shard_first,
                      walk_tcount(c), c->walk_counters.p, c->walk_stack.p, c->walk_counters.p + 1, c->r_acc.p,
@@ -2585,17 +2605,23 @@ static int launch_group3_t(Row<NG, PM, YUK, TAB_LDS, LATT, USR>, ngravs_ctx *c, 
   // least 8 GB and at most 64 GB, unless NGRAVS_WALK_BATCH fixes the group count
   long long batch = 1 << 20;   // units per launch pair
   size_t cap_bytes = (size_t)8 << 30;
-  {
-    size_t free_b = 0, total_b = 0;
-    if(hipMemGetInfo(&free_b, &total_b) == hipSuccess)
-      {
-        free_b += c->walk_stack.cap * sizeof(int);   // what this scratch already holds counts as available
-        if(free_b / 4 > cap_bytes)
-          cap_bytes = free_b / 4;
-        if(cap_bytes > ((size_t)64 << 30))
-          cap_bytes = (size_t)64 << 30;
-      }
-  }
+  if(c->walk_cap_n == c->n && c->walk_cap_stack == c->walk_stack.cap && c->walk_cap_bytes > 0)
+    cap_bytes = c->walk_cap_bytes;   // (hipMemGetInfo is a driver call in front of the step's first walk launch)
+  else
+    {
+      size_t free_b = 0, total_b = 0;
+      if(hipMemGetInfo(&free_b, &total_b) == hipSuccess)
+        {
+          free_b += c->walk_stack.cap * sizeof(int);   // what this scratch already holds counts as available
+          if(free_b / 4 > cap_bytes)
+            cap_bytes = free_b / 4;
+          if(cap_bytes > ((size_t)64 << 30))
+            cap_bytes = (size_t)64 << 30;
+          c->walk_cap_n = c->n;
+          c->walk_cap_stack = c->walk_stack.cap;
+          c->walk_cap_bytes = cap_bytes;
+        }
+    }
   if(c->tune.walk_batch > 0)
     {
       batch = c->tune.walk_batch;
@@ -2614,7 +2640,8 @@ static int launch_group3_t(Row<NG, PM, YUK, TAB_LDS, LATT, USR>, ngravs_ctx *c, 
   HIP_TRY(c, hipMemsetAsync(c->walk_counters.p, 0, sizeof(int) * 32, c->stream));
   auto kt = k_walk_group2<NG, PM, YUK, TAB_LDS, LATT, 1, USR>;
   auto ke = k_walk_group2<NG, PM, YUK, TAB_LDS, LATT, 2, USR>;
-  HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void *>(ke), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  if(int rl = walk_dyn_lds(c, reinterpret_cast<const void *>(ke), lds))
+    return rl;
   // TreePM lists with the tables in LDS go through the ring-pool evaluation kernel when at least 4 slots per wave fit
   int ringK = 0, ring_waves = waves;
   if constexpr(PM && TAB_LDS && !LATT && !USR)
@@ -2776,7 +2803,10 @@ static int walk_read_back(ngravs_ctx *c, int *flag, unsigned long long (&st64)[4
   return NGRAVS_OK;
 }
 
-int walk_run(ngravs_ctx *c)
+// The walk in two halves: walk_enqueue() puts every launch of the walk on c->stream and returns without waiting for them;
+// walk_complete() waits, redoes what the split walk left over, and reads the statistics.  Between the two the host may enqueue
+// other work on another stream (PM beside the walk, ngravs_compute_accelerations).
+int walk_enqueue(ngravs_ctx *c)
 {
   const long long n = c->n;
   if(c->r_acc.ensure(3 * n) || c->r_nint.ensure(n) || c->r_oldacc.ensure(n))
@@ -2848,6 +2878,17 @@ int walk_run(ngravs_ctx *c)
     return rc;
   HIP_TRY(c, hipEventRecord(c->evk1, c->stream));
   HIP_TRY(c, hipGetLastError());
+  c->walk_used_split = used_split;
+  return NGRAVS_OK;
+}
+
+int walk_complete(ngravs_ctx *c)
+{
+  const bool strict = c->cfg.walk_mode == NGRAVS_WALK_STRICT;
+  const bool used_split = c->walk_used_split;
+  int rc = NGRAVS_OK;
+  WalkParams wp;
+  make_walk_params(c, &wp);   // (what walk_enqueue launched with: nothing it depends on has changed)
   c->walk_unopened = 0;
   if(strict && c->top.on)
     {
@@ -2925,6 +2966,12 @@ int walk_run(ngravs_ctx *c)
         }
     }
   return NGRAVS_OK;
+}
+
+int walk_run(ngravs_ctx *c)
+{
+  const int rc = walk_enqueue(c);
+  return rc ? rc : walk_complete(c);
 }
 
 int walk_finish(ngravs_ctx *c)
