@@ -218,6 +218,13 @@ static int check_config(const ngravs_config_t *cfg, std::string &why)
       why = "n_gravs out of range";
       return NGRAVS_ERR_ARG;
     }
+  if(cfg->pmgrid < 0 || (cfg->pmgrid & 1))
+    {
+      // odd PMGRID: the reference pads to PMGRID2 = 2*(PMGRID/2+1) = N+1; a mesh of [N][N][N+2] would be transformed wrongly
+      why = "PMGRID must be 0 (no mesh) or positive and even: the in-place real-to-complex mesh is laid out [N][N][N+2], which is the "
+            "padding of the transform only for even N";
+      return NGRAVS_ERR_ARG;
+    }
   if(cfg->pmgrid && !cfg->periodic)
     {
       why = "non-periodic PM is disabled by ngravs itself (ngravs_core.c:235-242)";

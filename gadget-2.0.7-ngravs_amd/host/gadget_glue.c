@@ -55,6 +55,9 @@ static ngravs_rccl *Rccl = NULL;
 #ifndef UNEQUALSOFTENINGS
 #error "libngravs_hip applies per-type softening lengths: build the reference with -DUNEQUALSOFTENINGS"
 #endif
+#if defined(PMGRID) && ((PMGRID) < 0 || ((PMGRID) % 2) != 0)
+#error "libngravs_hip lays its in-place real-to-complex mesh out [PMGRID][PMGRID][PMGRID+2], which is right only for even PMGRID (the reference pads to PMGRID2 = 2*(PMGRID/2+1)): choose an even PMGRID"
+#endif
 #ifdef NGRAVS_GLUE_SPH
 #ifdef TWODIMS
 #error "NGRAVS_GLUE_SPH: TWODIMS is not provided (the SPH calls of libngravs_hip have the 3-D kernel only)"

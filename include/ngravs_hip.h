@@ -106,7 +106,9 @@ typedef struct {
   int32_t abi_version;        /* NGRAVS_ABI_VERSION                                            */
   int32_t n_gravs;            /* N_GRAVS, 1..NGRAVS_MAX_GRAVS                                   */
   int32_t periodic;           /* PERIODIC                                                       */
-  int32_t pmgrid;             /* PMGRID, 0 = tree-only                                          */
+  int32_t pmgrid;             /* PMGRID, 0 = tree-only; must be even and >= 0: the in-place real-to-complex mesh is laid
+                                 out [N][N][N+2], the transform's padding only for even N -- an odd or negative
+                                 value is refused with NGRAVS_ERR_ARG                                           */
   double box_size;            /* All.BoxSize                                                    */
   double G;                   /* All.G                                                          */
   double err_tol_theta;       /* All.ErrTolTheta (0 => relative criterion, gravtree.c:334-335)  */

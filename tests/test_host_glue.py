@@ -40,6 +40,19 @@ def test_glue_compiles_against_the_reference_interface(pkg, flags):
     assert out.returncode != 0 and "DOUBLEPRECISION" in out.stderr
 
 
+def test_glue_refuses_an_odd_pmgrid(pkg):
+    """The library's mesh is [N][N][N+2], the in-place transform's padding only for even N (the reference pads to
+    PMGRID2 = 2*(PMGRID/2+1)): an odd PMGRID is refused when the glue is compiled, an even one that is no power of two is not."""
+    root = os.path.join(os.path.dirname(pkg.__file__), "..")
+    glue = os.path.join(os.path.dirname(pkg.__file__), "host", "gadget_glue.c")
+    base = ["gcc", "-fsyntax-only", "-Wall", "-Wextra", "-Werror", "-DNGRAVS_BUILD_INSIDE_REFERENCE", "-DDOUBLEPRECISION",
+            "-DUNEQUALSOFTENINGS", "-I" + os.path.join(root, "tests", "glue_stub"), "-I" + os.path.join(root, "include")]
+    out = subprocess.run(base + ["-DPERIODIC", "-DPMGRID=33", glue], capture_output=True, text=True)
+    assert out.returncode != 0 and "even PMGRID" in out.stderr
+    out = subprocess.run(base + ["-DPERIODIC", "-DPMGRID=96", glue], capture_output=True, text=True)
+    assert out.returncode == 0, out.stderr
+
+
 OPTION_SETS = [[], ["-DPERIODIC", "-DPMGRID=64"], ["-DPERIODIC", "-DPMGRID=64", "-DFORCETEST=0.1"], ["-DFORCETEST=0.1", "-DN_GRAVS=3"],
                ["-DPERIODIC"], ["-DPERIODIC", "-DPMGRID=64", "-DNGRAVS_WITH_RCCL"]]
 
