@@ -42,7 +42,7 @@ EXPORTS = [
     "ngravs_dd_set_ids", "ngravs_dd_get_ids",
     "ngravs_pm_slab_begin", "ngravs_pm_slab_pack", "ngravs_pm_slab_unpack", "ngravs_pm_slab_bytes",
     "ngravs_sph_density", "ngravs_sph_kernel", "ngravs_sph_hydro", "ngravs_sph_accelerations",
-    "ngravs_sph_hsml_guess",
+    "ngravs_sph_hsml_guess", "ngravs_sph_density_sums", "ngravs_sph_hydro_sums", "ngravs_sph_density_update",
 ]
 # include/ngravs_host.h (plain-C multi-task drivers over a communicator vtable, linked into the same library)
 HOST_EXPORTS = ["ngravs_host_comm_selftest", "ngravs_host_kept_step", "ngravs_host_toptree_borrow", "ngravs_host_domain_decomposition", "ngravs_host_domain_owners", "ngravs_host_domain_halo",
@@ -134,6 +134,10 @@ def lib():
         L.ngravs_sph_hydro.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ngravs_sph_accelerations.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ngravs_sph_hsml_guess.argtypes = abi.SPH_HSML_GUESS_ARGTYPES
+        L.ngravs_sph_density_sums.argtypes = abi.SPH_DENSITY_SUMS_ARGTYPES
+        L.ngravs_sph_hydro_sums.argtypes = abi.SPH_HYDRO_SUMS_ARGTYPES
+        L.ngravs_sph_density_update.argtypes = abi.SPH_DENSITY_UPDATE_ARGTYPES
+        L.ngravs_sph_density_update.restype = C.c_int64
         _LIB = L
     return _LIB
 
@@ -229,6 +233,61 @@ def hydro_factors(time, omega0, omega_lambda, hubble, gamma=5.0 / 3):
 
 def _ptr(a):
     return a.ctypes.data if a is not None else None
+
+
+def _is_device(a):
+    return not isinstance(a, np.ndarray) and hasattr(a, "data_ptr")
+
+
+def _columns(cols, shapes, on_device, int_keys=()):
+    """the arrays of one call, all of one kind: numpy (converted to contiguous float64 / int32) or torch tensors on the device
+    (float64 / int32, contiguous, as they are).  Returns the dict and the function that gives an array's address."""
+    if on_device:
+        import torch
+        for k, a in cols.items():
+            assert a is None or (a.dtype == (torch.int32 if k in int_keys else torch.float64) and a.is_contiguous() and a.is_cuda), k
+        torch.cuda.synchronize()   # the library works on a stream of its own: the tensors must be complete
+        addr = lambda a: a.data_ptr()   # noqa: E731
+    else:
+        cols = {k: a if a is None else np.ascontiguousarray(a, dtype=np.int32 if k in int_keys else np.float64) for k, a in cols.items()}
+        addr = lambda a: a.ctypes.data   # noqa: E731
+    for k, a in cols.items():
+        assert a is None or tuple(a.shape) == shapes[k], (k, tuple(a.shape), shapes[k])
+    return cols, addr
+
+
+def _zeros(shape, like, on_device, dtype=np.float64):
+    if on_device:
+        import torch
+        return torch.zeros(shape, dtype=torch.int32 if dtype == np.int32 else torch.float64, device=like.device)
+    return np.zeros(shape, dtype=dtype)
+
+
+def sph_density_update(sums, hsml, left, right, rounds, des_num_ngb, max_num_ngb_deviation, min_gas_hsml=0.0):
+    """The owner's side of one round of density() (density.c:296-389) for targets whose added sums [n,7] came from
+    Engine.sph_density_sums: hsml, left, right (float64 [n]) and rounds (int32 [n]) are UPDATED IN PLACE (left = right = 0,
+    rounds = 0 before the first round).  numpy arrays (no GPU needed) or torch tensors on the device.  Returns a dict: accepted
+    (int32 [n]), hsml, density, num_ngb, div_vel, curl_vel, dhsml_factor (written for accepted targets, else 0), failed (the
+    number of targets past MAXITER)."""
+    on_device = _is_device(sums)
+    n = int(sums.shape[0])
+    io = dict(sums=sums, hsml=hsml, left=left, right=right, rounds=rounds)
+    chk, addr = _columns(io, dict(sums=(n, 7), hsml=(n,), left=(n,), right=(n,), rounds=(n,)), on_device, int_keys=("rounds",))
+    for k in ("hsml", "left", "right", "rounds"):   # written through: the caller's own arrays, never converted copies
+        assert chk[k] is io[k], k + " must be a contiguous float64 (rounds: int32) array"
+    res = {"accepted": _zeros(n, sums, on_device, np.int32)}
+    uo = abi.SphUpdateOut()
+    uo.accepted = addr(res["accepted"])
+    for k in abi.SPH_UPDATE_NAMES:
+        res[k] = _zeros(n, sums, on_device)
+        setattr(uo, k, addr(res[k]))
+    rc = lib().ngravs_sph_density_update(n, addr(chk["sums"]), addr(hsml), addr(left), addr(right), addr(rounds), float(des_num_ngb),
+                                         float(max_num_ngb_deviation), float(min_gas_hsml), C.byref(uo), int(on_device))
+    if rc < 0:
+        msg = lib().ngravs_last_error(None)
+        raise NgravsError("ngravs_sph_density_update failed: status %d (%s)" % (rc, msg.decode() if msg else ""))
+    res["failed"] = int(rc)
+    return res
 
 
 class Engine:
@@ -602,6 +661,60 @@ class Engine:
         res["max_rounds"], res["kernel_ms"] = int(rounds.value), [float(x) for x in ms]
         return res
 
+    def sph_density_sums(self, vel, tpos, tvel, th):
+        """density_evaluate(j, 1) of the reference (density.c:231-284): ONE round of the density sums over this engine's own gas
+        for targets that need not be its particles.  vel = SphP[].VelPred[N,3] of the own rows; tpos, tvel [nt,3] and th [nt] the
+        targets' positions, velocities and trial smoothing lengths, in any order.  numpy arrays, or torch tensors on the device.
+        Returns sums [nt,7] (abi.SPH_SUM_NAMES: rho, the weighted neighbour number, dhsmlrho, div, rot[3]), RAW: add the sums of
+        all engines, then sph_density_update()."""
+        on_device = _is_device(vel)
+        nt = int(tpos.shape[0])
+        cols, addr = _columns(dict(vel=vel, pos=tpos, tvel=tvel, hsml=th), dict(vel=(self.n, 3), pos=(nt, 3), tvel=(nt, 3), hsml=(nt,)),
+                              on_device)
+        tg = abi.SphTargets()
+        tg.pos, tg.pos_stride = addr(cols["pos"]), 24
+        tg.vel, tg.vel_stride = addr(cols["tvel"]), 24
+        tg.hsml, tg.hsml_stride = addr(cols["hsml"]), 8
+        sums = _zeros((nt, 7), vel, on_device)
+        ms = C.c_double(0)
+        self._check(lib().ngravs_sph_density_sums(self._h, addr(cols["vel"]), 24, C.byref(tg), nt, addr(sums), int(on_device), C.byref(ms)),
+                    "ngravs_sph_density_sums")
+        self.last_sums_ms = float(ms.value)
+        return sums
+
+    def sph_hydro_sums(self, vel, hsml, density, pressure, dhsml_factor, div_vel, curl_vel, targets, *, art_bulk_visc_const, timestep=None,
+                       timebase_interval=0.0, gamma=5.0 / 3, viscosity_limiter=True, comoving=None):
+        """hydro_evaluate(j, 1) of the reference (hydra.c:232-287): the hydro sums over this engine's own gas for targets that
+        need not be its particles.  vel ... curl_vel, timestep: the own rows' columns as for sph_hydro (every own type-0 row is a
+        source).  targets: a dict of the reference's hydrodata_in -- pos, vel [nt,3], hsml, mass, density, pressure, dhsml_factor,
+        f1 [nt] and optionally timestep (int32 [nt]); sph_split.hydro_targets() builds it.  numpy arrays, or torch tensors on the
+        device.  Returns sums [nt,5] (abi.HYDRO_SUM_NAMES): acc[3], dt_entropy BEFORE hydra.c:320, max_signal_vel."""
+        on_device = _is_device(vel)
+        n = self.n
+        own = dict(vel_pred=vel, hsml=hsml, density=density, pressure=pressure, dhsml_factor=dhsml_factor, div_vel=div_vel,
+                   curl_vel=curl_vel, timestep=timestep)
+        own, addr = _columns(own, {k: (n, 3) if k == "vel_pred" else (n,) for k in own}, on_device, int_keys=("timestep",))
+        nt = int(targets["pos"].shape[0])
+        tcols = {k: targets.get(k) for k in abi.HYDRO_TARGET_NAMES}
+        tcols, _ = _columns(tcols, {k: (nt, 3) if k in ("pos", "vel") else (nt,) for k in tcols}, on_device, int_keys=("timestep",))
+        hi, tg = abi.HydroIn(), abi.HydroTargets()
+        for st, cols in ((hi, own), (tg, tcols)):
+            for k, a in cols.items():
+                if a is not None:
+                    setattr(st, k, addr(a))
+                    setattr(st, k + "_stride", 24 if k in ("vel_pred", "pos", "vel") else 4 if k == "timestep" else 8)
+        hi.art_bulk_visc_const, hi.timebase_interval, hi.gamma = float(art_bulk_visc_const), float(timebase_interval), float(gamma)
+        hi.viscosity_limiter, hi.on_device = int(bool(viscosity_limiter)), int(on_device)
+        if comoving is not None:
+            hi.comoving = 1
+            hi.hubble_a2, hi.fac_mu, hi.fac_vsic_fix = (float(x) for x in comoving)
+        sums = _zeros((nt, 5), vel, on_device)
+        ms = C.c_double(0)
+        self._check(lib().ngravs_sph_hydro_sums(self._h, C.byref(hi), C.byref(tg), nt, addr(sums), int(on_device), C.byref(ms)),
+                    "ngravs_sph_hydro_sums")
+        self.last_sums_ms = float(ms.value)
+        return sums
+
     def stats(self):
         s = Stats()
         self._check(lib().ngravs_get_stats(self._h, C.byref(s)), "ngravs_get_stats")
@@ -650,3 +763,5 @@ class Engine:
         out = np.zeros((len(idx), 3))
         self._check(lib().ngravs_direct_sum(self._h, idx.ctypes.data, len(idx), out.ctypes.data), "ngravs_direct_sum")
         return out
+
+from . import sph_split  # noqa: E402,F401  (uses NgravsError and sph_density_update above)

@@ -175,6 +175,37 @@ class GasOut(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in GAS_OUT_NAMES] + [(k + "_stride", C.c_int64) for k in GAS_OUT_NAMES]
 
 
+SPH_TARGET_NAMES = ("pos", "vel", "hsml")
+HYDRO_TARGET_NAMES = ("pos", "vel", "hsml", "mass", "density", "pressure", "dhsml_factor", "f1", "timestep")
+SPH_SUM_NAMES = ("rho", "num_ngb", "dhsmlrho", "div", "rot_x", "rot_y", "rot_z")          # a row of ngravs_sph_density_sums
+HYDRO_SUM_NAMES = ("acc_x", "acc_y", "acc_z", "dt_entropy", "max_signal_vel")             # a row of ngravs_sph_hydro_sums
+SPH_UPDATE_NAMES = ("hsml",) + SPH_OUT_NAMES
+
+
+class SphTargets(C.Structure):
+    """ngravs_sph_targets_t"""
+    _fields_ = [f for k in SPH_TARGET_NAMES for f in ((k, C.c_void_p), (k + "_stride", C.c_int64))]
+
+
+class HydroTargets(C.Structure):
+    """ngravs_hydro_targets_t"""
+    _fields_ = [f for k in HYDRO_TARGET_NAMES for f in ((k, C.c_void_p), (k + "_stride", C.c_int64))]
+
+
+class SphUpdateOut(C.Structure):
+    """ngravs_sph_update_out_t"""
+    _fields_ = [("accepted", C.c_void_p)] + [(k, C.c_void_p) for k in SPH_UPDATE_NAMES]
+
+
+# int ngravs_sph_density_sums(ctx, own_vel_pred, own_vel_stride, targets, nt, sums, on_device, kernel_ms)
+SPH_DENSITY_SUMS_ARGTYPES = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]
+# int ngravs_sph_hydro_sums(ctx, own, targets, nt, sums, on_device, kernel_ms)
+SPH_HYDRO_SUMS_ARGTYPES = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]
+# int64 ngravs_sph_density_update(n, sums, hsml, left, right, rounds, des, dev, minh, out, on_device)
+SPH_DENSITY_UPDATE_ARGTYPES = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double,
+                               C.c_void_p, C.c_int32]
+
+
 def make_config(n_gravs=1, periodic=0, pmgrid=0, box_size=0.0, G=1.0, theta=0.5, err_tol_force_acc=0.005,
                 softening=None, type_to_grav=None, wiring="newton", yukawa_imass=60.0, walk_mode=WALK_STRICT,
                 tree_alloc_factor=0.0, device=0, rank=0, world_size=1, group_reach=0.0):

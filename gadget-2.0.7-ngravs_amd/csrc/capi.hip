@@ -427,6 +427,11 @@ extern "C" void ngravs_destroy(ngravs_ctx *c)
   c->sph_tpos.release();
   c->sph_gmass.release();
   c->sph_gcount.release();
+  c->sph_tg_in.release();
+  c->sph_tg_ts.release();
+  c->sph_tg_key.release();
+  c->sph_tg_ord.release();
+  c->sph_tg_res.release();
   (void)hipEventDestroy(c->ev0);
   (void)hipEventDestroy(c->ev1);
   (void)hipEventDestroy(c->evk0);
@@ -2335,6 +2340,214 @@ extern "C" int ngravs_sph_accelerations(ngravs_ctx *c, const ngravs_gas_in_t *in
     return rc;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return NGRAVS_OK;
+}
+
+// ---- SPH sums for targets that are not own rows: density_evaluate(j, 1) / hydro_evaluate(j, 1) (kernels_sph.hip) ---------------------
+static_assert(sizeof(ngravs_sph_targets_t) == 48 && sizeof(ngravs_hydro_targets_t) == 144 && sizeof(ngravs_sph_update_out_t) == 56,
+              "the Python mirror (abi.SphTargets / HydroTargets / SphUpdateOut) assumes this layout");
+// sph_tg_res [nt][ncomp] (caller order; NULL: zeros) -> the caller's contiguous array
+static int sph_write_sums(ngravs_ctx *c, const double *res, int ncomp, int64_t nt, double *out, int on_device)
+{
+  const size_t bytes = sizeof(double) * ncomp * (size_t)nt;
+  if(!res)
+    {
+      if(on_device)
+        {
+          HIP_TRY(c, hipMemsetAsync(out, 0, bytes, c->stream));
+          HIP_TRY(c, hipStreamSynchronize(c->stream));
+        }
+      else
+        memset(out, 0, bytes);
+      return NGRAVS_OK;
+    }
+  HIP_TRY(c, hipMemcpyAsync(out, res, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return NGRAVS_OK;
+}
+
+extern "C" int ngravs_sph_density_sums(ngravs_ctx *c, const double *own_vel_pred, int64_t own_vel_stride, const ngravs_sph_targets_t *tg, int64_t nt,
+                                       double *sums, int32_t on_device, double *kernel_ms)
+{
+  if(!c)
+    return NGRAVS_ERR_ARG;
+  auto refuse = [&](int code, const char *why) {
+    ngravs_report(c, code, std::string("ngravs_sph_density_sums: ") + why);
+    return code;
+  };
+  if(nt < 0 || nt > 0x7fffffff)
+    return refuse(NGRAVS_ERR_ARG, "nt must be >= 0 (and below 2^31)");
+  if(!own_vel_pred || !tg || (nt > 0 && (!tg->pos || !tg->vel || !tg->hsml || !sums)))
+    return refuse(NGRAVS_ERR_ARG, "own_vel_pred, targets, its pos, vel, hsml and sums must not be NULL");
+  int rc;
+  if((rc = sph_ready(c, refuse)))
+    return rc;
+  if(kernel_ms)
+    *kernel_ms = 0;
+  if(nt == 0)
+    return NGRAVS_OK;
+  const int64_t n = c->n_local;
+  if(n == 0 || c->nnodes <= 0)
+    return sph_write_sums(c, nullptr, SPH_NSUMS, nt, sums, on_device);
+  if(c->sph_vel_in.ensure(3 * n) || c->sph_vel.ensure(3 * n) || c->sph_tg_in.ensure((size_t)(SPH_TG_H + 1 + 3) * nt))
+    return refuse(NGRAVS_ERR_NOMEM, "device allocation failed");
+  if((rc = upload_column_f64(c, own_vel_pred, own_vel_stride, 3, n, on_device, c->sph_vel_in.p)))
+    return rc;
+  if((rc = upload_column_f64(c, tg->pos, tg->pos_stride, 3, nt, on_device, c->sph_tg_in.p)) ||
+     (rc = upload_column_f64(c, tg->vel, tg->vel_stride, 3, nt, on_device, c->sph_tg_in.p + 3 * nt)) ||
+     (rc = upload_column_f64(c, tg->hsml, tg->hsml_stride, 1, nt, on_device, c->sph_tg_in.p + SPH_TG_H * nt)))
+    return rc;
+  HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
+  hipLaunchKernelGGL(k_permute_f64, GRID1(n), 0, c->stream, c->s_idx.p, (long long)n, 3, c->sph_vel_in.p, c->sph_vel.p);
+  SphSumsStats st;
+  if((rc = sph_density_sums_run(c, nt, &st)))
+    return rc;
+  HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
+  if(kernel_ms)
+    *kernel_ms = ev_ms(c);
+  if(st.bad_hsml)
+    return refuse(NGRAVS_ERR_ARG, "a target's hsml is <= 0 or not finite");
+  if(st.bad_pos)
+    return refuse(NGRAVS_ERR_ARG, "a target's position is not finite, or outside [0, BoxSize] in a periodic run");
+  if(c->tune.sph_verbose)
+    printf("ngravs_sph_density_sums: %lld targets, %lld candidates tested, %lld neighbours\n", (long long)nt, st.candidates, st.pairs);
+  if(st.stack_ovf)
+    return refuse(NGRAVS_ERR_TREE, "the tree is deeper than the walk's stack");
+  return sph_write_sums(c, c->sph_tg_res.p, SPH_NSUMS, nt, sums, on_device);
+}
+
+extern "C" int ngravs_sph_hydro_sums(ngravs_ctx *c, const ngravs_hydro_in_t *in, const ngravs_hydro_targets_t *tg, int64_t nt, double *sums,
+                                     int32_t on_device, double *kernel_ms)
+{
+  if(!c)
+    return NGRAVS_ERR_ARG;
+  auto refuse = [&](int code, const char *why) {
+    ngravs_report(c, code, std::string("ngravs_sph_hydro_sums: ") + why);
+    return code;
+  };
+  if(nt < 0 || nt > 0x7fffffff)
+    return refuse(NGRAVS_ERR_ARG, "nt must be >= 0 (and below 2^31)");
+  if(!in || !in->vel_pred || !in->hsml || !in->density || !in->pressure || !in->dhsml_factor || !in->div_vel || !in->curl_vel)
+    return refuse(NGRAVS_ERR_ARG, "own and its vel_pred, hsml, density, pressure, dhsml_factor, div_vel, curl_vel must not be NULL");
+  if(!tg || (nt > 0 && (!tg->pos || !tg->vel || !tg->hsml || !tg->mass || !tg->density || !tg->pressure || !tg->dhsml_factor || !tg->f1 || !sums)))
+    return refuse(NGRAVS_ERR_ARG, "targets, its pos, vel, hsml, mass, density, pressure, dhsml_factor, f1 and sums must not be NULL");
+  if(!(in->gamma >= 1) || !(in->art_bulk_visc_const >= 0) || !(in->timebase_interval >= 0))
+    return refuse(NGRAVS_ERR_ARG, "gamma must be >= 1, art_bulk_visc_const and timebase_interval >= 0");
+  if(in->comoving && (!(in->hubble_a2 > 0) || !(in->fac_mu > 0) || !(in->fac_vsic_fix > 0)))
+    return refuse(NGRAVS_ERR_ARG, "comoving: hubble_a2, fac_mu and fac_vsic_fix must be > 0");
+  int rc;
+  if((rc = sph_ready(c, refuse)))
+    return rc;
+  if(kernel_ms)
+    *kernel_ms = 0;
+  if(nt == 0)
+    return NGRAVS_OK;
+  const int64_t n = c->n_local;
+  if(n == 0 || c->nnodes <= 0)
+    return sph_write_sums(c, nullptr, SPH_HY_NRES, nt, sums, on_device);
+  if(c->sph_vel_in.ensure(3 * n) || c->sph_h_in.ensure(n) || c->sph_col_in.ensure(5 * n) || c->sph_ts_in.ensure(n) ||
+     c->sph_tg_in.ensure((size_t)(SPH_TG_NCOL + 3) * nt) || c->sph_tg_ts.ensure((size_t)nt))
+    return refuse(NGRAVS_ERR_NOMEM, "device allocation failed");
+  if((rc = upload_column_f64(c, in->vel_pred, in->vel_pred_stride, 3, n, in->on_device, c->sph_vel_in.p)))
+    return rc;
+  if((rc = upload_column_f64(c, in->hsml, in->hsml_stride, 1, n, in->on_device, c->sph_h_in.p)))
+    return rc;
+  const double *col[5] = {in->density, in->pressure, in->dhsml_factor, in->div_vel, in->curl_vel};
+  const int64_t cstride[5] = {in->density_stride, in->pressure_stride, in->dhsml_factor_stride, in->div_vel_stride, in->curl_vel_stride};
+  for(int k = 0; k < 5; k++)
+    if((rc = upload_column_f64(c, col[k], cstride[k], 1, n, in->on_device, c->sph_col_in.p + k * n)))
+      return rc;
+  if(in->timestep && (rc = upload_column_i32(c, in->timestep, in->timestep_stride, n, in->on_device, c->sph_ts_in.p)))
+    return rc;
+  if((rc = upload_column_f64(c, tg->pos, tg->pos_stride, 3, nt, on_device, c->sph_tg_in.p)) ||
+     (rc = upload_column_f64(c, tg->vel, tg->vel_stride, 3, nt, on_device, c->sph_tg_in.p + 3 * nt)))
+    return rc;
+  const double *tcol[6] = {tg->hsml, tg->mass, tg->density, tg->pressure, tg->dhsml_factor, tg->f1};
+  const int64_t tstride[6] = {tg->hsml_stride, tg->mass_stride, tg->density_stride, tg->pressure_stride, tg->dhsml_factor_stride, tg->f1_stride};
+  for(int k = 0; k < 6; k++)
+    if((rc = upload_column_f64(c, tcol[k], tstride[k], 1, nt, on_device, c->sph_tg_in.p + (SPH_TG_H + k) * nt)))
+      return rc;
+  if(tg->timestep && (rc = upload_column_i32(c, tg->timestep, tg->timestep_stride, nt, on_device, c->sph_tg_ts.p)))
+    return rc;
+  SphHydroParams hp;
+  hp.periodic = c->cfg.periodic;
+  hp.box = c->cfg.box_size;
+  hp.boxhalf = 0.5 * c->cfg.box_size;
+  hp.comoving = in->comoving != 0;
+  hp.limiter = in->viscosity_limiter != 0;
+  hp.have_ts = in->timestep != nullptr;
+  hp.hubble_a2 = hp.comoving ? in->hubble_a2 : 1.0;   // hydra.c:96-97
+  hp.fac_mu = hp.comoving ? in->fac_mu : 1.0;
+  hp.fac_vsic_fix = hp.comoving ? in->fac_vsic_fix : 1.0;
+  hp.visc = in->art_bulk_visc_const;
+  hp.tbi = in->timebase_interval;
+  hp.gamma = in->gamma;
+  HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
+  SphSumsStats st;
+  SphHydroStats own;
+  if((rc = sph_hydro_sums_run(c, hp, nt, tg->timestep != nullptr, &st, &own)))
+    return rc;
+  HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
+  if(kernel_ms)
+    *kernel_ms = ev_ms(c);
+  if(own.bad_hsml)
+    return refuse(NGRAVS_ERR_ARG, "a type-0 row's hsml is <= 0 or not finite");
+  if(own.bad_density)
+    return refuse(NGRAVS_ERR_ARG, "a type-0 row's density is <= 0 or not finite");
+  if(own.bad_pressure)
+    return refuse(NGRAVS_ERR_ARG, "a type-0 row's pressure is < 0 or not finite");
+  if(st.bad_hsml)
+    return refuse(NGRAVS_ERR_ARG, "a target's hsml is <= 0 or not finite");
+  if(st.bad_density)
+    return refuse(NGRAVS_ERR_ARG, "a target's density is <= 0 or not finite");
+  if(st.bad_pressure)
+    return refuse(NGRAVS_ERR_ARG, "a target's pressure is < 0 or not finite");
+  if(st.bad_pos)
+    return refuse(NGRAVS_ERR_ARG, "a target's position is not finite, or outside [0, BoxSize] in a periodic run");
+  if(c->tune.sph_verbose)
+    printf("ngravs_sph_hydro_sums: %lld targets, %lld candidates tested, %lld pairs evaluated\n", (long long)nt, st.candidates, st.pairs);
+  if(st.stack_ovf)
+    return refuse(NGRAVS_ERR_TREE, "the tree is deeper than the walk's stack");
+  return sph_write_sums(c, c->sph_tg_res.p, SPH_HY_NRES, nt, sums, on_device);
+}
+
+extern "C" int64_t ngravs_sph_density_update(int64_t n, const double *sums, double *hsml, double *left, double *right, int32_t *rounds,
+                                             double des_num_ngb, double max_num_ngb_deviation, double min_gas_hsml,
+                                             const ngravs_sph_update_out_t *out, int32_t on_device)
+{
+  if(n < 0 || !out || (n > 0 && (!sums || !hsml || !left || !right || !rounds || !out->accepted)) || !(des_num_ngb > 0) ||
+     !(max_num_ngb_deviation >= 0) || !(min_gas_hsml >= 0))
+    {
+      ngravs_report(nullptr, NGRAVS_ERR_ARG,
+                    "ngravs_sph_density_update: n >= 0; sums, hsml, left, right, rounds, out and out->accepted must not be NULL; des_num_ngb > 0, "
+                    "max_num_ngb_deviation and min_gas_hsml >= 0");
+      return NGRAVS_ERR_ARG;
+    }
+  if(n == 0)
+    return 0;
+  double *const col[SPH_NRES] = {out->hsml, out->density, out->num_ngb, out->div_vel, out->curl_vel, out->dhsml_factor};
+  long long failed = 0;
+  if(on_device)
+    {
+      int rc = sph_density_update_device(n, sums, hsml, left, right, rounds, des_num_ngb, max_num_ngb_deviation, min_gas_hsml, out->accepted, col,
+                                         &failed);
+      return rc ? rc : failed;
+    }
+  for(int64_t t = 0; t < n; t++)   // GPU-free, as ngravs_sph_kernel is
+    {
+      double o[SPH_NRES];
+      const int r = sph_density_update_one(sums + SPH_NSUMS * t, des_num_ngb, max_num_ngb_deviation, min_gas_hsml, &hsml[t], &left[t], &right[t],
+                                           &rounds[t], o);
+      out->accepted[t] = r == 0;
+      if(r == 0)
+        {
+          for(int k = 0; k < SPH_NRES; k++)
+            if(col[k])
+              col[k][t] = o[k];
+        }
+      else if(r == 2)
+        failed++;
+    }
+  return failed;
 }
 
 extern "C" int ngravs_sph_kernel(double h, const double *r, int64_t n, double *wk, double *dwk)

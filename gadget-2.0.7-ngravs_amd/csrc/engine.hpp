@@ -387,6 +387,12 @@ struct ngravs_ctx
   // the first smoothing-length guess (ngravs_sph_hsml_guess); empty until it is used
   DevBuf<double> sph_gmass;              // [n + 1], Peano order: gas mass of the rows before a row (inclusive scan shifted by one)
   DevBuf<int> sph_gcount;                // [n + 1]: gas rows before a row
+  // sums for targets that are not own rows (ngravs_sph_density_sums / ngravs_sph_hydro_sums); empty until they are used
+  DevBuf<double> sph_tg_in;              // the caller's target columns, caller order: pos[nt][3], vel[nt][3], then one column each
+  DevBuf<int> sph_tg_ts;                 // the targets' timestep column
+  DevBuf<unsigned long long> sph_tg_key; // [2][nt]: the targets' Peano keys (coordinates clamped to the domain cube), unsorted and sorted
+  DevBuf<unsigned int> sph_tg_ord;       // [2][nt]: 0 .. nt-1, and the caller's indices in Peano order
+  DevBuf<double> sph_tg_res;             // [nt][7] or [nt][5], caller order: copied out only when the whole call succeeded
 };
 
 // Routes the context's launches to stream `s`, whose CU mask leaves them `cus` CUs, until the end of the scope (the kernels
@@ -555,6 +561,76 @@ struct SphScatterCols
 int sph_scatter_cols(ngravs_ctx *c, long long nt, const SphScatterCols &cols);
 // list order -> rows of a strided device column
 int sph_scatter(ngravs_ctx *c, const double *src, long long nt, double *dst, long long stride);
+// ---- sums for targets that are not own rows: the reference's density_evaluate(j, 1) / hydro_evaluate(j, 1) -------------------------
+enum { SPH_SUM_RHO = 0, SPH_SUM_NGB, SPH_SUM_DHR, SPH_SUM_DIV, SPH_SUM_ROTX, SPH_SUM_ROTY, SPH_SUM_ROTZ, SPH_NSUMS };   // density.c:531-575
+// columns of sph_tg_in behind pos[nt][3] and vel[nt][3]: density targets hold SPH_TG_H only
+enum { SPH_TG_H = 6, SPH_TG_MASS, SPH_TG_RHO, SPH_TG_P, SPH_TG_DHSML, SPH_TG_F1, SPH_TG_NCOL };
+struct SphSumsStats
+{
+  long long bad_hsml, bad_density, bad_pressure, bad_pos, stack_ovf, candidates, pairs;
+};
+// reads sph_tg_in (pos, vel, SPH_TG_H) and sph_vel (Peano order); orders the targets along the Peano curve, walks ONE round and
+// writes the raw sums to sph_tg_res [nt][SPH_NSUMS] in caller order (nothing is walked when a target was bad)
+int sph_density_sums_run(ngravs_ctx *c, long long nt, SphSumsStats *st);
+// reads sph_tg_in (all columns), sph_tg_ts and the own-row columns sph_vel_in, sph_h_in, sph_col_in, sph_ts_in; fills sph_hsrc and
+// sph_hmax as sph_hydro_run does (have_tts: sph_tg_ts holds the targets' timesteps, else all 0), orders the targets, walks once and writes sph_tg_res [nt][SPH_HY_NRES] in caller order: acc[3],
+// dt_entropy before hydra.c:320, max_signal_vel.  own: the counts of bad own rows
+int sph_hydro_sums_run(ngravs_ctx *c, const SphHydroParams &hp, long long nt, int have_tts, SphSumsStats *st, SphHydroStats *own);
+// The owner's side of one round for one target (density.c:296-389 as k_sph_density applies it per lane): the final operations on
+// the added sums s[SPH_NSUMS], the acceptance and bracketing rules, the next trial length, the clamp.  Returns 0: accepted, out6 =
+// Hsml, Density, NumNgb, DivVel, CurlVel, DhsmlDensityFactor; 1: to be repeated with the new *h; 2: the same, and *rounds is past
+// MAXITER (density.c:416).  No contraction: host and device give the same bits but for pow() in the bisection.
+__host__ __device__ inline int sph_density_update_one(const double *s, double des, double dev, double minh, double *h_io, double *left_io,
+                                                      double *right_io, int *rounds_io, double *out6)
+{
+#pragma clang fp contract(off)
+  double h = *h_io, left = *left_io, right = *right_io;
+  const int nr = ++*rounds_io;
+  // final operations (density.c:296-303)
+  const double numngb = s[SPH_SUM_NGB], rho = s[SPH_SUM_RHO];
+  const double dhf = 1 / (1 + h * s[SPH_SUM_DHR] / (3 * rho));
+  // enough neighbours? (density.c:314-389, rule for rule)
+  bool redo = numngb < (des - dev) || (numngb > (des + dev) && h > 1.01 * minh);
+  if(redo && left > 0 && right > 0 && (right - left) < 1.0e-3 * left)
+    redo = false;
+  if(!redo)
+    {
+      out6[SPH_HSML] = h;
+      out6[SPH_DENSITY] = rho;
+      out6[SPH_NUMNGB] = numngb;
+      out6[SPH_DIVVEL] = s[SPH_SUM_DIV] / rho;
+      out6[SPH_CURLVEL] = sqrt(s[SPH_SUM_ROTX] * s[SPH_SUM_ROTX] + s[SPH_SUM_ROTY] * s[SPH_SUM_ROTY] + s[SPH_SUM_ROTZ] * s[SPH_SUM_ROTZ]) / rho;
+      out6[SPH_DHSML] = dhf;
+      return 0;
+    }
+  if(numngb < (des - dev))
+    left = fmax(h, left);
+  else if(right != 0)
+    {
+      if(h < right)
+        right = h;
+    }
+  else
+    right = h;
+  if(right > 0 && left > 0)
+    h = pow(0.5 * (pow(left, 3) + pow(right, 3)), 1.0 / 3);
+  else
+    {
+      const bool newton = fabs(numngb - des) < 0.5 * des;
+      const double fac = 1 - (numngb - des) / (3 * numngb) * dhf;
+      if(right == 0 && left > 0)
+        h *= newton ? fac : 1.26;
+      if(right > 0 && left == 0)
+        h = newton ? h * fac : h / 1.26;
+    }
+  if(h < minh)
+    h = minh;
+  *h_io = h, *left_io = left, *right_io = right;
+  return nr > SPH_MAXITER ? 2 : 1;
+}
+// one thread per target over device arrays; *failed counts the targets past MAXITER
+int sph_density_update_device(long long n, const double *sums, double *h, double *left, double *right, int *rounds, double des, double dev,
+                              double minh, int *accepted, double *const out[SPH_NRES], long long *failed);
 // ---- kernels_pm.hip
 int pm_run(ngravs_ctx *c);
 int pm_deposit(ngravs_ctx *c);

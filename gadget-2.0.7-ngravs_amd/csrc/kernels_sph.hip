@@ -33,6 +33,11 @@
 // The gas side in one call (ngravs_sph_accelerations): k_sph_density, then k_sph_gas_prep in the place of k_sph_hydro_prep (the
 //      pressure line of density.c:305-308 and the hydro sources, a target's from the density results where they lie), k_sph_hmax,
 //      k_sph_hydro, and one k_sph_scatter_cols for all columns.  The two walks are the kernels above, unchanged.
+//
+// Sums for targets that are NOT own rows (ngravs_sph_density_sums, ngravs_sph_hydro_sums; density_evaluate(j, 1) and
+// hydro_evaluate(j, 1) of the reference, density.c:231-284, hydra.c:232-287): k_sph_density_sums and k_sph_hydro_sums at the end
+//      of this file, one round over the engine's own gas for records handed in, raw sums out; k_sph_density_update is the owner's
+//      side of a round.
 #include "engine.hpp"
 #include "walk_device.hpp"
 #include <hipcub/hipcub.hpp>
@@ -1137,5 +1142,355 @@ int sph_scatter(ngravs_ctx *c, const double *src, long long nt, double *dst, lon
   hipLaunchKernelGGL(k_sph_scatter, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, c->stream, c->sph_row.p, nt, src,
                      reinterpret_cast<unsigned char *>(dst), stride);
   HIP_TRY(c, hipGetLastError());
+  return NGRAVS_OK;
+}
+
+// ---- sums for targets that are not own rows (density_evaluate(j, 1), density.c:231-284; hydro_evaluate(j, 1), hydra.c:232-287) ---
+// What the reference does for a particle it imported: partial sums over the LOCAL gas, unfinalised, for the owner to add up.  A
+// target is a record in sph_tg_in, not a row of the tree; the same calls serve probe points (tracers, grids).
+// k_sph_tg_prep : one thread per target: refuses a bad record, and clamps the position to the domain cube for the Peano key only (a
+//      foreign target may lie outside the cube of the engine's own particles).  The targets are then sorted by that key, so that
+//      the 64 lanes of a wave are neighbours in space whatever the caller's order was.
+// k_sph_density_sums : sph_hull_walk for the hull of the lanes' search boxes, ONE round at the given h, sph_block per staged block;
+//      the seven raw sums of density.c:531-575 go to the caller's index of the target, without density.c:296-303.
+// k_sph_hydro_sums : the walk of k_sph_hydro for lanes that hold the reference's hydrodata_in (hydra.c:145-162); acc[3], dt_entropy
+//      BEFORE hydra.c:320 and max_signal_vel.
+// k_sph_density_update : the owner's side of one round, sph_density_update_one per target.
+// No workgroup barrier, no atomics on results; a push that would not fit the LIFO ends the call, and sph_tg_res is not copied out.
+#define SPH_T_BADPOS 4   // counter: targets whose position is not finite, or outside [0, BoxSize] in a periodic run
+
+__global__ void k_sph_tg_prep(const double *__restrict__ tg, long long nt, int hydro, int periodic, double box, double cx, double cy, double cz,
+                              double len, double *__restrict__ clamped, unsigned int *__restrict__ iota,
+                              unsigned long long *__restrict__ counters)
+{
+  const long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+  if(t >= nt)
+    return;
+  const double BIG = 1e300;
+  const double h = tg[SPH_TG_H * nt + t];
+  if(!(h > 0) || !(h < BIG))
+    atomicAdd(&counters[SPH_H_BADH], 1ull);
+  if(hydro)
+    {
+      const double rho = tg[SPH_TG_RHO * nt + t], pressure = tg[SPH_TG_P * nt + t];
+      if(!(rho > 0) || !(rho < BIG))
+        atomicAdd(&counters[SPH_H_BADRHO], 1ull);
+      if(!(pressure >= 0) || !(pressure < BIG))
+        atomicAdd(&counters[SPH_H_BADP], 1ull);
+    }
+  const double corner[3] = {cx, cy, cz};
+  bool bad = false;
+  for(int k = 0; k < 3; k++)
+    {
+      const double x = tg[3 * t + k];
+      if(!(fabs(x) < BIG) || (periodic && !(x >= 0 && x <= box)))
+        bad = true;
+      // inside the cube with a cell to spare: (x - corner) * DomainFac stays below 2^TREE_BITS
+      clamped[3 * t + k] = fmin(fmax(x, corner[k]), corner[k] + len * (1 - 1e-6));
+    }
+  if(bad)
+    atomicAdd(&counters[SPH_T_BADPOS], 1ull);
+  iota[t] = (unsigned int)t;
+}
+
+__global__ __launch_bounds__(64 * SPH_WAVES) void k_sph_density_sums(TreeView tv, const double4 *__restrict__ pm, const unsigned char *__restrict__ type,
+                                                                     const double *__restrict__ svel, long long n, const double *__restrict__ tg,
+                                                                     const unsigned int *__restrict__ ord, long long nt, SphParams sp,
+                                                                     double *__restrict__ res, unsigned long long *__restrict__ counters)
+{
+  __shared__ double s_src[SPH_WAVES][7][SPH_STAGE];
+  __shared__ int s_stack[SPH_WAVES][SPH_STACK];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const long long t = ((long long)blockIdx.x * SPH_WAVES + w) * 64 + lane;
+  if(t - lane >= nt)   // the whole wave (no workgroup barrier anywhere below)
+    return;
+  double (*src)[SPH_STAGE] = s_src[w];
+  int *stack = s_stack[w];
+  const double BIG = 1e300;
+
+  const bool live = t < nt;
+  SphLane L = {};
+  double h = 0;
+  long long me = 0;
+  if(live)
+    {
+      me = ord[t];
+      L.x = tg[3 * me], L.y = tg[3 * me + 1], L.z = tg[3 * me + 2];
+      L.vx = tg[3 * nt + 3 * me], L.vy = tg[3 * nt + 3 * me + 1], L.vz = tg[3 * nt + 3 * me + 2];
+      h = tg[SPH_TG_H * nt + me];
+      L.h2 = h * h;
+      L.hinv = 1.0 / h;
+      L.hinv3 = L.hinv * L.hinv * L.hinv;
+      L.hinv4 = L.hinv3 * L.hinv;
+    }
+  // the hull of the lanes' search boxes (ngb.c:206-210), as in k_sph_density
+  const double lx = wave_min(live ? L.x - h : BIG), ly = wave_min(live ? L.y - h : BIG), lz = wave_min(live ? L.z - h : BIG);
+  const double ux = wave_max(live ? L.x + h : -BIG), uy = wave_max(live ? L.y + h : -BIG), uz = wave_max(live ? L.z + h : -BIG);
+  const double hcx = wave_uniform(0.5 * (lx + ux)), hcy = wave_uniform(0.5 * (ly + uy)), hcz = wave_uniform(0.5 * (lz + uz));
+  const double hhx = wave_uniform(0.5 * (ux - lx) * (1 + 1e-12)), hhy = wave_uniform(0.5 * (uy - ly) * (1 + 1e-12)),
+               hhz = wave_uniform(0.5 * (uz - lz) * (1 + 1e-12));
+  const bool ok = sph_hull_walk<SPH_STAGE>(
+    tv, pm, type, n, sp.periodic, sp.box, sp.boxhalf, hcx, hcy, hcz, hhx, hhy, hhz, stack, lane, [](int) { return 0.0; },
+    [&](int q, long long p) {
+      const double4 pp = pm[p];
+      src[0][q] = pp.x, src[1][q] = pp.y, src[2][q] = pp.z, src[3][q] = pp.w;
+      src[4][q] = svel[3 * p], src[5][q] = svel[3 * p + 1], src[6][q] = svel[3 * p + 2];
+    },
+    [&](int cnt) { sph_block(src, cnt, live, sp, L); });
+  if(live && ok)
+    {
+      double *r = res + SPH_NSUMS * me;   // the caller's order; NOT passed through density.c:296-303
+      r[SPH_SUM_RHO] = L.rho;
+      r[SPH_SUM_NGB] = L.wnn;
+      r[SPH_SUM_DHR] = L.dhr;
+      r[SPH_SUM_DIV] = L.divv;
+      r[SPH_SUM_ROTX] = L.rx;
+      r[SPH_SUM_ROTY] = L.ry;
+      r[SPH_SUM_ROTZ] = L.rz;
+    }
+  unsigned long long cand = L.ncand, ngb = L.nngb;
+  for(int off = 32; off > 0; off >>= 1)
+    {
+      cand += __shfl_xor(cand, off);
+      ngb += __shfl_xor(ngb, off);
+    }
+  if(lane == 0)
+    {
+      atomicAdd(&counters[SPH_C_CAND], cand);
+      atomicAdd(&counters[SPH_C_NGB], ngb);
+      if(!ok)
+        atomicAdd(&counters[SPH_C_OVF], 1ull);
+    }
+}
+
+__global__ __launch_bounds__(64 * SPH_HWAVES) void k_sph_hydro_sums(TreeView tv, const double4 *__restrict__ pm, const unsigned char *__restrict__ type,
+                                                                    const double *__restrict__ hs, const double *__restrict__ hmax, long long n,
+                                                                    const double *__restrict__ tg, const int *__restrict__ tts,
+                                                                    const unsigned int *__restrict__ ord, long long nt, SphHydroParams hp,
+                                                                    double *__restrict__ res, unsigned long long *__restrict__ counters)
+{
+  __shared__ double s_src[SPH_HWAVES][SPH_HFIELDS][SPH_STAGE];
+  __shared__ int s_stack[SPH_HWAVES][SPH_STACK];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const long long t = ((long long)blockIdx.x * SPH_HWAVES + w) * 64 + lane;
+  if(t - lane >= nt)   // the whole wave (no workgroup barrier anywhere below)
+    return;
+  double (*src)[SPH_STAGE] = s_src[w];
+  int *stack = s_stack[w];
+  const double BIG = 1e300;
+  const double *sh = hs + SPH_HS_H * n;
+
+  const bool live = t < nt;
+  SphHydroLane L = {};
+  double h = 0;
+  long long me = 0;
+  if(live)
+    {
+      // hydrodata_in (hydra.c:145-162), and what hydro_evaluate derives from it (hydra.c:379, :403)
+      me = ord[t];
+      L.x = tg[3 * me], L.y = tg[3 * me + 1], L.z = tg[3 * me + 2];
+      L.vx = tg[3 * nt + 3 * me], L.vy = tg[3 * nt + 3 * me + 1], L.vz = tg[3 * nt + 3 * me + 2];
+      h = tg[SPH_TG_H * nt + me];
+      L.mass = tg[SPH_TG_MASS * nt + me];
+      L.h2 = h * h;
+      L.hinv = 1.0 / h;
+      L.hinv4 = L.hinv * L.hinv * L.hinv * L.hinv;
+      L.rho = tg[SPH_TG_RHO * nt + me];
+      const double pressure = tg[SPH_TG_P * nt + me];
+      const double por2 = pressure / (L.rho * L.rho);
+      L.por2 = por2 * tg[SPH_TG_DHSML * nt + me];
+      L.cs = sqrt(hp.gamma * pressure / L.rho);
+      L.f1 = tg[SPH_TG_F1 * nt + me];
+      L.ts = tts ? (double)tts[me] : 0.0;
+    }
+  // the hull of the lanes' positions; a child is tested against it widened by max(largest h_i, hmax of the child) (ngb.c:146-177)
+  const double lx = wave_min(live ? L.x : BIG), ly = wave_min(live ? L.y : BIG), lz = wave_min(live ? L.z : BIG);
+  const double ux = wave_max(live ? L.x : -BIG), uy = wave_max(live ? L.y : -BIG), uz = wave_max(live ? L.z : -BIG);
+  const double hw = wave_uniform(wave_max(live ? h : 0.0));
+  const double hcx = wave_uniform(0.5 * (lx + ux)), hcy = wave_uniform(0.5 * (ly + uy)), hcz = wave_uniform(0.5 * (lz + uz));
+  const double hhx = wave_uniform(0.5 * (ux - lx) * (1 + 1e-12)), hhy = wave_uniform(0.5 * (uy - ly) * (1 + 1e-12)),
+               hhz = wave_uniform(0.5 * (uz - lz) * (1 + 1e-12));
+  const bool ok = sph_hull_walk<SPH_STAGE>(
+    tv, pm, type, n, hp.periodic, hp.box, hp.boxhalf, hcx, hcy, hcz, hhx, hhy, hhz, stack, lane,
+    [&](int ch) { return fmax(hw, ch >= 0 ? hmax[ch] : sh[-2 - ch]) * (1 + 1e-12); },
+    [&](int q, long long p) {
+      const double4 pp = pm[p];
+      src[0][q] = pp.x, src[1][q] = pp.y, src[2][q] = pp.z, src[3][q] = pp.w;
+      src[4][q] = hs[SPH_HS_VX * n + p], src[5][q] = hs[SPH_HS_VY * n + p], src[6][q] = hs[SPH_HS_VZ * n + p];
+      src[7][q] = hs[SPH_HS_H * n + p], src[8][q] = hs[SPH_HS_RHO * n + p], src[9][q] = hs[SPH_HS_POR2 * n + p];
+      src[10][q] = hs[SPH_HS_CSJ * n + p], src[11][q] = hs[SPH_HS_F2 * n + p], src[12][q] = hs[SPH_HS_TS * n + p];
+    },
+    [&](int cnt) { sph_hydro_block(src, cnt, live, hp, L); });
+  if(live && ok)
+    {
+      double *r = res + SPH_HY_NRES * me;   // the caller's order; dt_entropy WITHOUT the final operation of hydra.c:320
+      r[SPH_HY_ACCX] = L.ax;
+      r[SPH_HY_ACCY] = L.ay;
+      r[SPH_HY_ACCZ] = L.az;
+      r[SPH_HY_DTENTR] = L.dte;
+      r[SPH_HY_MAXSIG] = L.maxsig;
+    }
+  unsigned long long cand = L.ncand, pairs = L.npair;
+  for(int off = 32; off > 0; off >>= 1)
+    {
+      cand += __shfl_xor(cand, off);
+      pairs += __shfl_xor(pairs, off);
+    }
+  if(lane == 0)
+    {
+      atomicAdd(&counters[SPH_C_CAND], cand);
+      atomicAdd(&counters[SPH_C_NGB], pairs);
+      if(!ok)
+        atomicAdd(&counters[SPH_C_OVF], 1ull);
+    }
+}
+
+// refuses bad targets (st says which), else leaves the caller's indices in Peano order in sph_tg_ord + nt
+static int sph_targets_order(ngravs_ctx *c, long long nt, int hydro, SphSumsStats *st, bool *good)
+{
+  *good = false;
+  double *clamped = c->sph_tg_in.p + (hydro ? SPH_TG_NCOL : SPH_TG_H + 1) * nt;
+  HIP_TRY(c, hipMemsetAsync(c->sph_counters.p, 0, (SPH_C_COUNT + 1) * sizeof(unsigned long long), c->stream));
+  hipLaunchKernelGGL(k_sph_tg_prep, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, c->stream, c->sph_tg_in.p, nt, hydro, c->cfg.periodic,
+                     c->cfg.box_size, c->dom[0], c->dom[1], c->dom[2], c->dom[6], clamped, c->sph_tg_ord.p, c->sph_counters.p);
+  HIP_TRY(c, hipGetLastError());
+  unsigned long long h[SPH_C_COUNT];
+  HIP_TRY(c, hipMemcpyAsync(h, c->sph_counters.p, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  st->bad_hsml = (long long)h[SPH_H_BADH];
+  st->bad_density = (long long)h[SPH_H_BADRHO];
+  st->bad_pressure = (long long)h[SPH_H_BADP];
+  st->bad_pos = (long long)h[SPH_T_BADPOS];
+  if(st->bad_hsml || st->bad_density || st->bad_pressure || st->bad_pos)
+    return NGRAVS_OK;   // the caller refuses; nothing is walked for such a target
+  const double fac21 = c->dom[7] * (double)(1 << (TREE_BITS - NGRAVS_BITS_PER_DIMENSION));
+  if(int rc = dom_keys_only(c, clamped, nt, c->dom, fac21, TREE_BITS, reinterpret_cast<long long *>(c->sph_tg_key.p)))
+    return rc;
+  size_t bytes = 0;
+  HIP_TRY(c, hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, c->sph_tg_key.p, c->sph_tg_key.p + nt, c->sph_tg_ord.p, c->sph_tg_ord.p + nt,
+                                                (int)nt, 0, 3 * TREE_BITS, c->stream));
+  if(c->sph_tmp.ensure(bytes))
+    return NGRAVS_ERR_NOMEM;
+  HIP_TRY(c, hipcub::DeviceRadixSort::SortPairs(c->sph_tmp.p, bytes, c->sph_tg_key.p, c->sph_tg_key.p + nt, c->sph_tg_ord.p,
+                                                c->sph_tg_ord.p + nt, (int)nt, 0, 3 * TREE_BITS, c->stream));
+  *good = true;
+  return NGRAVS_OK;
+}
+
+static int sph_sums_counters(ngravs_ctx *c, SphSumsStats *st)
+{
+  unsigned long long h[SPH_C_COUNT];
+  HIP_TRY(c, hipMemcpyAsync(h, c->sph_counters.p, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  st->stack_ovf = (long long)h[SPH_C_OVF];
+  st->candidates = (long long)h[SPH_C_CAND];
+  st->pairs = (long long)h[SPH_C_NGB];
+  return NGRAVS_OK;
+}
+
+int sph_density_sums_run(ngravs_ctx *c, long long nt, SphSumsStats *st)
+{
+  memset(st, 0, sizeof(*st));
+  if(c->sph_counters.ensure(SPH_C_COUNT + 1) || c->sph_tg_key.ensure(2 * (size_t)nt) || c->sph_tg_ord.ensure(2 * (size_t)nt) ||
+     c->sph_tg_res.ensure((size_t)SPH_NSUMS * nt))
+    return NGRAVS_ERR_NOMEM;
+  bool good;
+  if(int rc = sph_targets_order(c, nt, 0, st, &good))
+    return rc;
+  if(!good)
+    return NGRAVS_OK;
+  SphParams sp = {};
+  sp.periodic = c->cfg.periodic;
+  sp.box = c->cfg.box_size;
+  sp.boxhalf = 0.5 * c->cfg.box_size;
+  const long long nwaves = (nt + 63) / 64;
+  const unsigned nb = (unsigned)((nwaves + SPH_WAVES - 1) / SPH_WAVES);
+  hipLaunchKernelGGL(k_sph_density_sums, dim3(nb), dim3(64 * SPH_WAVES), 0, c->stream, sph_tree_view(c), c->s_pm.p, c->s_type.p, c->sph_vel.p,
+                     (long long)c->n, c->sph_tg_in.p, c->sph_tg_ord.p + nt, nt, sp, c->sph_tg_res.p, c->sph_counters.p);
+  HIP_TRY(c, hipGetLastError());
+  return sph_sums_counters(c, st);
+}
+
+int sph_hydro_sums_run(ngravs_ctx *c, const SphHydroParams &hp, long long nt, int have_tts, SphSumsStats *st, SphHydroStats *own)
+{
+  memset(st, 0, sizeof(*st));
+  memset(own, 0, sizeof(*own));
+  const long long n = c->n;
+  if(c->sph_counters.ensure(SPH_C_COUNT + 1) || c->sph_tg_key.ensure(2 * (size_t)nt) || c->sph_tg_ord.ensure(2 * (size_t)nt) ||
+     c->sph_tg_res.ensure((size_t)SPH_HY_NRES * nt) || c->sph_hsrc.ensure((size_t)SPH_HS_NCOL * n) || c->sph_hmax.ensure((size_t)c->nnodes))
+    return NGRAVS_ERR_NOMEM;
+  // the engine's own gas: sph_hsrc and the nodes' hmax, as sph_hydro_run prepares them
+  HIP_TRY(c, hipMemsetAsync(c->sph_counters.p, 0, (SPH_C_COUNT + 1) * sizeof(unsigned long long), c->stream));
+  hipLaunchKernelGGL(k_sph_hydro_prep, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->s_type.p, c->s_idx.p, n, c->sph_vel_in.p,
+                     c->sph_h_in.p, c->sph_col_in.p, c->sph_ts_in.p, hp, c->sph_hsrc.p, c->sph_counters.p);
+  HIP_TRY(c, hipGetLastError());
+  unsigned long long h[SPH_C_COUNT];
+  HIP_TRY(c, hipMemcpyAsync(h, c->sph_counters.p, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  own->bad_hsml = (long long)h[SPH_H_BADH];
+  own->bad_density = (long long)h[SPH_H_BADRHO];
+  own->bad_pressure = (long long)h[SPH_H_BADP];
+  if(own->bad_hsml || own->bad_density || own->bad_pressure)
+    return NGRAVS_OK;   // the caller refuses; nothing is walked with such a column
+  bool good;
+  if(int rc = sph_targets_order(c, nt, 1, st, &good))   // (clears the counters)
+    return rc;
+  if(!good)
+    return NGRAVS_OK;
+  if(int rc = sph_hmax_levels(c))
+    return rc;
+  const long long nwaves = (nt + 63) / 64;
+  const unsigned nb = (unsigned)((nwaves + SPH_HWAVES - 1) / SPH_HWAVES);
+  hipLaunchKernelGGL(k_sph_hydro_sums, dim3(nb), dim3(64 * SPH_HWAVES), 0, c->stream, sph_tree_view(c), c->s_pm.p, c->s_type.p, c->sph_hsrc.p,
+                     c->sph_hmax.p, n, c->sph_tg_in.p, have_tts ? c->sph_tg_ts.p : nullptr, c->sph_tg_ord.p + nt, nt, hp, c->sph_tg_res.p, c->sph_counters.p);
+  HIP_TRY(c, hipGetLastError());
+  return sph_sums_counters(c, st);
+}
+
+__global__ void k_sph_density_update(long long n, const double *__restrict__ sums, double *__restrict__ h, double *__restrict__ left,
+                                     double *__restrict__ right, int *__restrict__ rounds, double des, double dev, double minh,
+                                     int *__restrict__ accepted, SphScatterCols out, unsigned long long *__restrict__ failed)
+{
+  const long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+  if(t >= n)
+    return;
+  double o[SPH_NRES];
+  const int r = sph_density_update_one(sums + SPH_NSUMS * t, des, dev, minh, &h[t], &left[t], &right[t], &rounds[t], o);
+  accepted[t] = r == 0;
+  if(r == 0)
+    {
+#pragma unroll
+      for(int k = 0; k < SPH_NRES; k++)
+        if(out.dst[k])
+          reinterpret_cast<double *>(out.dst[k])[t] = o[k];
+    }
+  else if(r == 2)
+    atomicAdd(failed, 1ull);
+}
+
+int sph_density_update_device(long long n, const double *sums, double *h, double *left, double *right, int *rounds, double des, double dev,
+                              double minh, int *accepted, double *const out[SPH_NRES], long long *failed)
+{
+  *failed = 0;
+  unsigned long long *d_failed = nullptr;
+  if(hipMalloc(&d_failed, sizeof(unsigned long long)) != hipSuccess)
+    return NGRAVS_ERR_NOMEM;
+  SphScatterCols cols = {};
+  for(int k = 0; k < SPH_NRES; k++)
+    cols.dst[k] = reinterpret_cast<unsigned char *>(out[k]);
+  unsigned long long f = 0;
+  hipError_t e = hipMemsetAsync(d_failed, 0, sizeof(unsigned long long), 0);
+  if(e == hipSuccess)
+    {
+      hipLaunchKernelGGL(k_sph_density_update, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, n, sums, h, left, right, rounds, des, dev, minh,
+                         accepted, cols, d_failed);
+      e = hipGetLastError();
+    }
+  if(e == hipSuccess)
+    e = hipMemcpy(&f, d_failed, sizeof(f), hipMemcpyDeviceToHost);   // (waits for the kernel)
+  (void)hipFree(d_failed);
+  if(e != hipSuccess)
+    return NGRAVS_ERR_NO_DEVICE;
+  *failed = (long long)f;
   return NGRAVS_OK;
 }

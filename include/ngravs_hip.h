@@ -617,6 +617,68 @@ typedef struct {   /* any pointer may be NULL; strides in bytes; rows = own rows
 int ngravs_sph_accelerations(ngravs_ctx *ctx, const ngravs_gas_in_t *in, const ngravs_gas_out_t *out, int32_t *max_rounds,
                              double *kernel_ms /* [3] */);
 
+/* ---- SPH sums for targets that are NOT the engine's own rows: the per-task half of density() / hydro_force() across tasks ---------
+ * What the reference does for a particle it imported, density_evaluate(j, 1) (density.c:231-284) and hydro_evaluate(j, 1)
+ * (hydra.c:232-287): partial sums over the LOCAL gas for a target handed in as a record, returned UNFINALISED so that the owner
+ * adds the sums of all tasks and finishes them.  The same calls give density, velocity divergence and curl of the gas at
+ * arbitrary probe points (tracers, grids).  No communicator is involved: who sends which target where is the caller's business
+ * (sph_split.py plays the reference's export loop between engines of one process).
+ * Sources are the engine's own type-0 rows (ngb.c:221), nearest image in periodic runs.  A target may lie anywhere in an open
+ * run (also outside the cube of the engine's particles); in a periodic run inside [0, BoxSize].  The caller's target order is
+ * arbitrary: the targets are walked in the order of the engine's Peano curve (coordinates clamped to the domain cube for the key
+ * only) and the sums come back in the caller's order.  An engine without gas: success, all sums 0.  nt == 0: success.
+ * Both need a built tree of the current particle set (NGRAVS_ERR_STATE otherwise; after ngravs_update_particles the tree is
+ * refit first); NGRAVS_ERR_STATE, "single task only": world_size > 1 or a multi-task working set.  The tree, the walk's state and
+ * the stored accelerations are not modified.  NGRAVS_ERR_ARG with a message, and nothing written: a NULL argument, nt < 0, a
+ * target whose hsml (hydro: or density) is <= 0 or not finite, whose pressure is < 0 or not finite, whose position is not finite
+ * or, in a periodic run, outside [0, BoxSize]; for the hydro sums also what ngravs_sph_hydro refuses about the own rows.
+ * on_device: every array of the call (own columns of ngravs_sph_density_sums, targets, sums) is a device array; the own columns
+ * of ngravs_sph_hydro_sums follow own->on_device.  sums is contiguous.  kernel_ms may be NULL.
+ * Not provided: TWODIMS, LONG_X/Y/Z, SPH_BND_PARTICLES; the exchange itself (ngravs_host_* drivers, the glue). */
+typedef struct {   /* strides in bytes; nt rows */
+  const double *pos;  int64_t pos_stride;    /* the target's Pos[3]                                  */
+  const double *vel;  int64_t vel_stride;    /* its VelPred[3]                                       */
+  const double *hsml; int64_t hsml_stride;   /* the trial smoothing length of this round, > 0        */
+} ngravs_sph_targets_t;
+/* ONE round at the given hsml.  sums [nt][7]: the raw sums of density.c:531-575 -- rho, the weighted neighbour number, dhsmlrho,
+ * div, rot[3] -- NOT passed through the final operations density.c:296-303.  A target that coincides with a source gets the
+ * r = 0 term and no velocity terms (density.c:560), so an own particle handed in as a target gets its self term.
+ * own_vel_pred: SphP[].VelPred[3] per own row (rows of other types are not read). */
+int ngravs_sph_density_sums(ngravs_ctx *ctx, const double *own_vel_pred, int64_t own_vel_stride, const ngravs_sph_targets_t *targets,
+                            int64_t nt, double *sums, int32_t on_device, double *kernel_ms);
+typedef struct {   /* the reference's hydrodata_in (hydra.c:145-162); strides in bytes; nt rows */
+  const double *pos;          int64_t pos_stride;            /* Pos[3]                                                      */
+  const double *vel;          int64_t vel_stride;            /* VelPred[3]                                                  */
+  const double *hsml;         int64_t hsml_stride;           /* Hsml                                                        */
+  const double *mass;         int64_t mass_stride;           /* Mass                                                        */
+  const double *density;      int64_t density_stride;        /* Density                                                     */
+  const double *pressure;     int64_t pressure_stride;       /* Pressure                                                    */
+  const double *dhsml_factor; int64_t dhsml_factor_stride;   /* DhsmlDensityFactor                                          */
+  const double *f1;           int64_t f1_stride;             /* F1 = |div| / (|div| + curl + 0.0001 c_s / Hsml / fac_mu), computed by the sender (hydra.c:160) */
+  const int32_t *timestep;    int64_t timestep_stride;       /* Ti_endstep - Ti_begstep, or NULL (all 0)                    */
+} ngravs_hydro_targets_t;
+/* own: the engine's own source columns and the constants, as for ngravs_sph_hydro (every own type-0 row is a source).  Per pair
+ * exactly hydra.c:416-534.  sums [nt][5]: acc[3], dt_entropy BEFORE the final operation of hydra.c:320, max_signal_vel starting
+ * from 0 (the owner adds acc and dt_entropy, takes the maximum of max_signal_vel, then applies hydra.c:320). */
+int ngravs_sph_hydro_sums(ngravs_ctx *ctx, const ngravs_hydro_in_t *own, const ngravs_hydro_targets_t *targets, int64_t nt, double *sums,
+                          int32_t on_device, double *kernel_ms);
+/* The owner's side of one round of density() for n targets whose sums [n][7] have been added up: the final operations
+ * density.c:296-303 and the acceptance and bracketing rules density.c:314-389 as ngravs_sph_density applies them (the band, above
+ * the band with hsml <= 1.01 MinGasHsml, a bracket narrower than 1e-3; bisection in h^3, the Newton-like step, the factor 1.26;
+ * the clamp to MinGasHsml).  hsml, left, right, rounds [n] are IN/OUT: left = right = 0 and rounds = 0 before the first round;
+ * rounds is incremented; for a target that is to be repeated hsml holds the next trial length.  accepted [n]: 1 / 0; for accepted
+ * targets the six result columns (any may be NULL) are written.  All arrays contiguous, host or device (on_device); the host
+ * path needs no GPU.  Host and device give the same bits except for pow() in the bisection step.
+ * Returns the number of targets that are to be repeated with rounds > MAXITER = 150 (the reference's endrun(1155)), or a
+ * negative NGRAVS_ERR_*. */
+typedef struct {
+  int32_t *accepted;
+  double *hsml, *density, *num_ngb, *div_vel, *curl_vel, *dhsml_factor;
+} ngravs_sph_update_out_t;
+int64_t ngravs_sph_density_update(int64_t n, const double *sums, double *hsml, double *left, double *right, int32_t *rounds,
+                                  double des_num_ngb, double max_num_ngb_deviation, double min_gas_hsml,
+                                  const ngravs_sph_update_out_t *out, int32_t on_device);
+
 #ifdef __cplusplus
 }
 #endif
