@@ -239,9 +239,11 @@ def _is_device(a):
     return not isinstance(a, np.ndarray) and hasattr(a, "data_ptr")
 
 
-def _columns(cols, shapes, on_device, int_keys=()):
+def _columns(cols, shapes, on_device, int_keys=(), own=()):
     """the arrays of one call, all of one kind: numpy (converted to contiguous float64 / int32) or torch tensors on the device
-    (float64 / int32, contiguous, as they are).  Returns the dict and the function that gives an array's address."""
+    (float64 / int32, contiguous, as they are).  own: the keys of arrays that the library writes through, which must be right as
+    they are: the caller's own arrays, never converted copies.  Returns the dict and the function that gives an array's address."""
+    given = cols
     if on_device:
         import torch
         for k, a in cols.items():
@@ -251,6 +253,8 @@ def _columns(cols, shapes, on_device, int_keys=()):
     else:
         cols = {k: a if a is None else np.ascontiguousarray(a, dtype=np.int32 if k in int_keys else np.float64) for k, a in cols.items()}
         addr = lambda a: a.ctypes.data   # noqa: E731
+    for k in own:
+        assert cols[k] is given[k], k + " must be a C-contiguous float64 (int32) numpy array: it is written through"
     for k, a in cols.items():
         assert a is None or tuple(a.shape) == shapes[k], (k, tuple(a.shape), shapes[k])
     return cols, addr
@@ -263,6 +267,28 @@ def _zeros(shape, like, on_device, dtype=np.float64):
     return np.zeros(shape, dtype=dtype)
 
 
+def _results(names, shape, out, like, on_device):
+    """the arrays a call writes: what `out` holds under a name (written through), else zeros"""
+    return {k: out[k] if out and k in out else _zeros(shape(k), like, on_device) for k in names}
+
+
+def _set_columns(st, cols, addr):
+    """address and row stride of every given array into the fields <key> and <key>_stride of an ABI struct"""
+    for k, a in cols.items():
+        if a is not None:
+            setattr(st, k, addr(a))
+            setattr(st, k + "_stride", (4 if str(a.dtype).endswith("int32") else 8) * (3 if len(a.shape) == 2 else 1))
+
+
+def _hydro_switches(st, art_bulk_visc_const, timebase_interval, gamma, viscosity_limiter, comoving, on_device):
+    """the switch fields that abi.HydroIn and abi.GasIn share"""
+    st.art_bulk_visc_const, st.timebase_interval, st.gamma = float(art_bulk_visc_const), float(timebase_interval), float(gamma)
+    st.viscosity_limiter, st.on_device = int(bool(viscosity_limiter)), int(on_device)
+    if comoving is not None:
+        st.comoving = 1
+        st.hubble_a2, st.fac_mu, st.fac_vsic_fix = (float(x) for x in comoving)
+
+
 def sph_density_update(sums, hsml, left, right, rounds, des_num_ngb, max_num_ngb_deviation, min_gas_hsml=0.0):
     """The owner's side of one round of density() (density.c:296-389) for targets whose added sums [n,7] came from
     Engine.sph_density_sums: hsml, left, right (float64 [n]) and rounds (int32 [n]) are UPDATED IN PLACE (left = right = 0,
@@ -272,9 +298,8 @@ def sph_density_update(sums, hsml, left, right, rounds, des_num_ngb, max_num_ngb
     on_device = _is_device(sums)
     n = int(sums.shape[0])
     io = dict(sums=sums, hsml=hsml, left=left, right=right, rounds=rounds)
-    chk, addr = _columns(io, dict(sums=(n, 7), hsml=(n,), left=(n,), right=(n,), rounds=(n,)), on_device, int_keys=("rounds",))
-    for k in ("hsml", "left", "right", "rounds"):   # written through: the caller's own arrays, never converted copies
-        assert chk[k] is io[k], k + " must be a contiguous float64 (rounds: int32) array"
+    chk, addr = _columns(io, dict(sums=(n, 7), hsml=(n,), left=(n,), right=(n,), rounds=(n,)), on_device, int_keys=("rounds",),
+                         own=("hsml", "left", "right", "rounds"))
     res = {"accepted": _zeros(n, sums, on_device, np.int32)}
     uo = abi.SphUpdateOut()
     uo.accepted = addr(res["accepted"])
@@ -493,39 +518,26 @@ class Engine:
         self._check(lib().ngravs_get_accel(self._h, None, 0, pm.ctypes.data, 24, None, 0, None, 0, 0, 0), "ngravs_get_accel")
         return pm
 
+    def _rows(self, k):
+        """shape of the SPH column k over the rows of the last hand-over"""
+        return (self.n, 3) if k in ("vel_pred", "hydro_accel") else (self.n,)
+
     def sph_density(self, vel, hsml, des_num_ngb, max_num_ngb_deviation, min_gas_hsml=0.0, out=None):
         """density() of the reference for one task (density.c:56-441): vel = SphP[].VelPred[N,3], hsml = starting guesses [N], one
         row per particle of the last hand-over (only rows of active type-0 particles are read as targets and written).  numpy
         arrays, or torch tensors on the device (float64, contiguous: no copy through the host).  Returns a dict: hsml, density,
         num_ngb, div_vel, curl_vel, dhsml_factor (rows that are no targets: the given hsml, else 0 -- or what `out`, a dict of
         arrays of the same kind, held), max_rounds, kernel_ms."""
-        on_device = not isinstance(vel, np.ndarray) and hasattr(vel, "data_ptr")
-        res = {}
-        if on_device:
-            import torch
-            assert vel.dtype == torch.float64 and hsml.dtype == torch.float64 and vel.is_contiguous() and hsml.is_contiguous()
-            res["hsml"] = hsml.clone()
-            for k in abi.SPH_OUT_NAMES:
-                res[k] = out[k] if out and k in out else torch.zeros_like(hsml)
-                assert res[k].dtype == torch.float64 and res[k].is_contiguous()
-            addr = lambda a: a.data_ptr()   # noqa: E731
-            torch.cuda.synchronize()   # the library works on a stream of its own: the tensors above must be complete
-        else:
-            vel = np.ascontiguousarray(vel, dtype=np.float64)
-            res["hsml"] = np.array(hsml, dtype=np.float64)
-            for k in abi.SPH_OUT_NAMES:
-                res[k] = out[k] if out and k in out else np.zeros(self.n)
-                assert res[k].dtype == np.float64 and res[k].flags.c_contiguous
-            addr = lambda a: a.ctypes.data   # noqa: E731
-        assert tuple(vel.shape) == (self.n, 3) and all(tuple(a.shape) == (self.n,) for a in res.values())
+        on_device = _is_device(vel)
+        res = {"hsml": hsml.clone() if on_device else np.array(hsml, dtype=np.float64)}
+        res.update(_results(abi.SPH_OUT_NAMES, self._rows, out, vel, on_device))
+        cols, addr = _columns(dict(res, vel_pred=vel), {k: self._rows(k) for k in ["vel_pred"] + list(res)}, on_device, own=tuple(res))
         si, so = abi.SphIn(), abi.SphOut()
-        si.vel_pred, si.vel_stride = addr(vel), 24
+        si.vel_pred, si.vel_stride = addr(cols["vel_pred"]), 24
         si.hsml, si.hsml_stride = addr(res["hsml"]), 8
         si.des_num_ngb, si.max_num_ngb_deviation, si.min_gas_hsml = des_num_ngb, max_num_ngb_deviation, min_gas_hsml
         si.on_device = int(on_device)
-        for k in abi.SPH_OUT_NAMES:
-            setattr(so, k, addr(res[k]))
-            setattr(so, k + "_stride", 8)
+        _set_columns(so, {k: res[k] for k in abi.SPH_OUT_NAMES}, addr)
         rounds, ms = C.c_int32(0), C.c_double(0)
         self._check(lib().ngravs_sph_density(self._h, C.byref(si), C.byref(so), C.byref(rounds), C.byref(ms)), "ngravs_sph_density")
         res["max_rounds"], res["kernel_ms"] = int(rounds.value), float(ms.value)
@@ -562,46 +574,16 @@ class Engine:
         torch tensors on the device (float64 / int32, contiguous: no copy through the host).  Returns a dict: hydro_accel [N,3],
         dt_entropy, max_signal_vel (rows that are no targets: 0 -- or what `out`, a dict of arrays of the same kind, held),
         kernel_ms."""
-        cols = dict(vel_pred=vel, hsml=hsml, density=density, pressure=pressure, dhsml_factor=dhsml_factor, div_vel=div_vel,
-                    curl_vel=curl_vel)
-        on_device = not isinstance(vel, np.ndarray) and hasattr(vel, "data_ptr")
-        res = {}
-        if on_device:
-            import torch
-            assert all(a.dtype == torch.float64 and a.is_contiguous() for a in cols.values())
-            if timestep is not None:
-                assert timestep.dtype == torch.int32 and timestep.is_contiguous()
-            for k in abi.HYDRO_OUT_NAMES:
-                res[k] = out[k] if out and k in out else torch.zeros((self.n, 3) if k == "hydro_accel" else (self.n,),
-                                                                     dtype=torch.float64, device=vel.device)
-                assert res[k].dtype == torch.float64 and res[k].is_contiguous()
-            addr = lambda a: a.data_ptr()   # noqa: E731
-            torch.cuda.synchronize()   # the library works on a stream of its own: the tensors above must be complete
-        else:
-            cols = {k: np.ascontiguousarray(a, dtype=np.float64) for k, a in cols.items()}
-            if timestep is not None:
-                timestep = np.ascontiguousarray(timestep, dtype=np.int32)
-            for k in abi.HYDRO_OUT_NAMES:
-                res[k] = out[k] if out and k in out else np.zeros((self.n, 3) if k == "hydro_accel" else self.n)
-                assert res[k].dtype == np.float64 and res[k].flags.c_contiguous
-            addr = lambda a: a.ctypes.data   # noqa: E731
-        assert all(tuple(a.shape) == ((self.n, 3) if k == "vel_pred" else (self.n,)) for k, a in cols.items())
-        assert tuple(res["hydro_accel"].shape) == (self.n, 3) and tuple(res["dt_entropy"].shape) == (self.n,)
-        assert tuple(res["max_signal_vel"].shape) == (self.n,) and (timestep is None or tuple(timestep.shape) == (self.n,))
+        on_device = _is_device(vel)
+        ins = dict(vel_pred=vel, hsml=hsml, density=density, pressure=pressure, dhsml_factor=dhsml_factor, div_vel=div_vel,
+                   curl_vel=curl_vel, timestep=timestep)
+        res = _results(abi.HYDRO_OUT_NAMES, self._rows, out, vel, on_device)
+        cols, addr = _columns(dict(ins, **res), {k: self._rows(k) for k in list(ins) + list(res)}, on_device, int_keys=("timestep",),
+                              own=tuple(res))
         hi, ho = abi.HydroIn(), abi.HydroOut()
-        for k, a in cols.items():
-            setattr(hi, k, addr(a))
-            setattr(hi, k + "_stride", 24 if k == "vel_pred" else 8)
-        if timestep is not None:
-            hi.timestep, hi.timestep_stride = addr(timestep), 4
-        hi.art_bulk_visc_const, hi.timebase_interval, hi.gamma = float(art_bulk_visc_const), float(timebase_interval), float(gamma)
-        hi.viscosity_limiter, hi.on_device = int(bool(viscosity_limiter)), int(on_device)
-        if comoving is not None:
-            hi.comoving = 1
-            hi.hubble_a2, hi.fac_mu, hi.fac_vsic_fix = (float(x) for x in comoving)
-        for k in abi.HYDRO_OUT_NAMES:
-            setattr(ho, k, addr(res[k]))
-            setattr(ho, k + "_stride", 24 if k == "hydro_accel" else 8)
+        _set_columns(hi, {k: cols[k] for k in ins}, addr)
+        _hydro_switches(hi, art_bulk_visc_const, timebase_interval, gamma, viscosity_limiter, comoving, on_device)
+        _set_columns(ho, res, addr)
         ms = C.c_double(0)
         self._check(lib().ngravs_sph_hydro(self._h, C.byref(hi), C.byref(ho), C.byref(ms)), "ngravs_sph_hydro")
         res["kernel_ms"] = float(ms.value)
@@ -619,43 +601,19 @@ class Engine:
         (float64 / int32, contiguous: no copy through the host).  comoving: None, or hydro_factors(...).  Returns a dict: num_ngb,
         hydro_accel [N,3], dt_entropy_out, max_signal_vel (rows that are no targets: 0 -- or what `out`, a dict of arrays of the
         same kind, held), max_rounds, kernel_ms (density walk, pressure line + hydro sources + hmax, hydro walk)."""
+        on_device = _is_device(vel)
         ins = dict(vel_pred=vel, entropy=entropy, dt_entropy=dt_entropy, ti_begstep=ti_begstep, ti_endstep=ti_endstep)
         inout = dict(hsml=hsml, density=density, pressure=pressure, dhsml_factor=dhsml_factor, div_vel=div_vel, curl_vel=curl_vel)
-        on_device = not isinstance(vel, np.ndarray) and hasattr(vel, "data_ptr")
-        shape = lambda k: (self.n, 3) if k in ("vel_pred", "hydro_accel") else (self.n,)   # noqa: E731
-        res = {}
-        if on_device:
-            import torch
-            f64, i32 = torch.float64, torch.int32
-            ok = lambda a, t: a.dtype == t and a.is_contiguous() and a.is_cuda   # noqa: E731
-            for k in abi.GAS_OUT_NAMES:
-                res[k] = out[k] if out and k in out else torch.zeros(shape(k), dtype=f64, device=vel.device)
-            addr = lambda a: a.data_ptr()   # noqa: E731
-            torch.cuda.synchronize()   # the library works on a stream of its own: the tensors above must be complete
-        else:
-            f64, i32 = np.float64, np.int32
-            ok = lambda a, t: isinstance(a, np.ndarray) and a.dtype == t and a.flags.c_contiguous   # noqa: E731
-            ins = {k: a if a is None else np.ascontiguousarray(a, dtype=i32 if k.startswith("ti_") else f64) for k, a in ins.items()}
-            for k in abi.GAS_OUT_NAMES:
-                res[k] = out[k] if out and k in out else np.zeros(shape(k))
-            addr = lambda a: a.ctypes.data   # noqa: E731
-        for k, a in list(ins.items()) + list(inout.items()) + list(res.items()):
-            # (the in/out columns are written through: they must be the caller's own arrays, never converted copies)
-            assert a is None or (ok(a, i32 if k.startswith("ti_") else f64) and tuple(a.shape) == shape(k)), k
+        res = _results(abi.GAS_OUT_NAMES, self._rows, out, vel, on_device)
+        # (the in/out columns are written through, as the results are: the caller's own arrays, never converted copies)
+        cols, addr = _columns(dict(ins, **inout, **res), {k: self._rows(k) for k in list(ins) + list(inout) + list(res)}, on_device,
+                              int_keys=("ti_begstep", "ti_endstep"), own=tuple(inout) + tuple(res))
         gi, go = abi.GasIn(), abi.GasOut()
-        for k, a in list(ins.items()) + list(inout.items()):
-            if a is not None:
-                setattr(gi, k, addr(a))
-                setattr(gi, k + "_stride", 24 if k == "vel_pred" else 4 if k.startswith("ti_") else 8)
+        _set_columns(gi, {k: cols[k] for k in list(ins) + list(inout)}, addr)
         gi.des_num_ngb, gi.max_num_ngb_deviation, gi.min_gas_hsml = float(des_num_ngb), float(max_num_ngb_deviation), float(min_gas_hsml)
-        gi.art_bulk_visc_const, gi.timebase_interval, gi.gamma = float(art_bulk_visc_const), float(timebase_interval), float(gamma)
-        gi.ti_current, gi.viscosity_limiter, gi.on_device = int(ti_current), int(bool(viscosity_limiter)), int(on_device)
-        if comoving is not None:
-            gi.comoving = 1
-            gi.hubble_a2, gi.fac_mu, gi.fac_vsic_fix = (float(x) for x in comoving)
-        for k in abi.GAS_OUT_NAMES:
-            setattr(go, k, addr(res[k]))
-            setattr(go, k + "_stride", 24 if k == "hydro_accel" else 8)
+        gi.ti_current = int(ti_current)
+        _hydro_switches(gi, art_bulk_visc_const, timebase_interval, gamma, viscosity_limiter, comoving, on_device)
+        _set_columns(go, res, addr)
         rounds, ms = C.c_int32(0), (C.c_double * 3)()
         self._check(lib().ngravs_sph_accelerations(self._h, C.byref(gi), C.byref(go), C.byref(rounds), ms), "ngravs_sph_accelerations")
         res["max_rounds"], res["kernel_ms"] = int(rounds.value), [float(x) for x in ms]
@@ -672,9 +630,7 @@ class Engine:
         cols, addr = _columns(dict(vel=vel, pos=tpos, tvel=tvel, hsml=th), dict(vel=(self.n, 3), pos=(nt, 3), tvel=(nt, 3), hsml=(nt,)),
                               on_device)
         tg = abi.SphTargets()
-        tg.pos, tg.pos_stride = addr(cols["pos"]), 24
-        tg.vel, tg.vel_stride = addr(cols["tvel"]), 24
-        tg.hsml, tg.hsml_stride = addr(cols["hsml"]), 8
+        _set_columns(tg, dict(pos=cols["pos"], vel=cols["tvel"], hsml=cols["hsml"]), addr)
         sums = _zeros((nt, 7), vel, on_device)
         ms = C.c_double(0)
         self._check(lib().ngravs_sph_density_sums(self._h, addr(cols["vel"]), 24, C.byref(tg), nt, addr(sums), int(on_device), C.byref(ms)),
@@ -698,16 +654,9 @@ class Engine:
         tcols = {k: targets.get(k) for k in abi.HYDRO_TARGET_NAMES}
         tcols, _ = _columns(tcols, {k: (nt, 3) if k in ("pos", "vel") else (nt,) for k in tcols}, on_device, int_keys=("timestep",))
         hi, tg = abi.HydroIn(), abi.HydroTargets()
-        for st, cols in ((hi, own), (tg, tcols)):
-            for k, a in cols.items():
-                if a is not None:
-                    setattr(st, k, addr(a))
-                    setattr(st, k + "_stride", 24 if k in ("vel_pred", "pos", "vel") else 4 if k == "timestep" else 8)
-        hi.art_bulk_visc_const, hi.timebase_interval, hi.gamma = float(art_bulk_visc_const), float(timebase_interval), float(gamma)
-        hi.viscosity_limiter, hi.on_device = int(bool(viscosity_limiter)), int(on_device)
-        if comoving is not None:
-            hi.comoving = 1
-            hi.hubble_a2, hi.fac_mu, hi.fac_vsic_fix = (float(x) for x in comoving)
+        _set_columns(hi, own, addr)
+        _set_columns(tg, tcols, addr)
+        _hydro_switches(hi, art_bulk_visc_const, timebase_interval, gamma, viscosity_limiter, comoving, on_device)
         sums = _zeros((nt, 5), vel, on_device)
         ms = C.c_double(0)
         self._check(lib().ngravs_sph_hydro_sums(self._h, C.byref(hi), C.byref(tg), nt, addr(sums), int(on_device), C.byref(ms)),

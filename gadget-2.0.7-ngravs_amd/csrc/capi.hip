@@ -1968,8 +1968,22 @@ static int upload_column_i32(ngravs_ctx *c, const void *src, int64_t stride, int
   return NGRAVS_OK;
 }
 
-// one task, a built tree of the current particle set (refit first when the particles drifted, as ngravs_gravity_tree does)
-template <class Refuse> static int sph_ready(ngravs_ctx *c, Refuse refuse)
+// a refusal of the entry point who: reported as "<who>: <why>", nothing is written
+struct SphRefuse
+{
+  ngravs_ctx *c;
+  const char *who;
+  int operator()(int code, const char *why) const
+  {
+    ngravs_report(c, code, std::string(who) + ": " + why);
+    return code;
+  }
+};
+
+// What every SPH call does once its arguments are checked: one task, a built tree of the current particle set (refit first when
+// the particles drifted, as ngravs_gravity_tree does); then max_rounds (may be NULL) and the nms values of kernel_ms (may be NULL)
+// read 0 for a call that ends early.
+static int sph_begin(ngravs_ctx *c, const SphRefuse &refuse, int32_t *max_rounds, double *kernel_ms, int nms)
 {
   if(c->cfg.world_size > 1 || c->top.on || c->n_local != c->n)
     return refuse(NGRAVS_ERR_STATE, "single task only (the neighbour search does not cross task boundaries yet)");
@@ -1977,7 +1991,93 @@ template <class Refuse> static int sph_ready(ngravs_ctx *c, Refuse refuse)
     return refuse(NGRAVS_ERR_STATE, "needs a built tree of the current particle set");
   (void)hipSetDevice(c->cfg.device);
   if(c->tree_stale)
-    return ngravs_force_update_tree(c);
+    if(int rc = ngravs_force_update_tree(c))
+      return rc;
+  if(max_rounds)
+    *max_rounds = 0;
+  for(int k = 0; kernel_ms && k < nms; k++)
+    kernel_ms[k] = 0;
+  return NGRAVS_OK;
+}
+
+// an engine without particles (or without a tree node) has nothing to walk
+static bool sph_empty(const ngravs_ctx *c) { return c->n_local == 0 || c->nnodes <= 0; }
+
+// what a density walk's statistics mean for the call: the log line, then the three ways it can have gone wrong
+static int sph_density_outcome(ngravs_ctx *c, const SphStats &st, const SphRefuse &refuse)
+{
+  if(c->tune.sph_verbose && st.targets > 0)   // the reference logs every round of its iteration (density.c:409-414); here one line per call
+    printf("ngravs_sph_density: %lld targets, rounds mean %.3f max %lld, %lld candidates tested, %lld neighbours\n", st.targets,
+           (double)st.sum_rounds / (double)st.targets, st.max_rounds, st.candidates, st.neighbours);
+  if(st.bad_hsml)
+    return refuse(NGRAVS_ERR_ARG, "a target's starting hsml is <= 0 or not finite");
+  if(st.stack_ovf)
+    return refuse(NGRAVS_ERR_TREE, "the tree is deeper than the walk's stack");
+  if(st.failed)
+    {
+      ngravs_report(c, 1155, "failed to converge in neighbour iteration in density()");   // density.c:416-421
+      return NGRAVS_ERR_STATE;
+    }
+  return NGRAVS_OK;
+}
+
+// the own rows' columns that k_sph_hydro_prep / k_sph_gas_prep counted as bad
+static int sph_hydro_rows_outcome(const SphHydroStats &st, const SphRefuse &refuse)
+{
+  if(st.bad_hsml)
+    return refuse(NGRAVS_ERR_ARG, "a type-0 row's hsml is <= 0 or not finite");
+  if(st.bad_density)
+    return refuse(NGRAVS_ERR_ARG, "a type-0 row's density is <= 0 or not finite");
+  if(st.bad_pressure)
+    return refuse(NGRAVS_ERR_ARG, "a type-0 row's pressure is < 0 or not finite");
+  return NGRAVS_OK;
+}
+
+// The hydro side of ngravs_hydro_in_t and ngravs_gas_in_t, whose switch and column fields carry the same names.  Three steps, because
+// each entry point has checks of its own between them and the order of the refusals is part of its behaviour:
+// whether the seven columns of the own rows are given (the caller words the refusal: its list of names differs),
+template <class In> static bool sph_hydro_cols_given(const In *in)
+{
+  return in && in->vel_pred && in->hsml && in->density && in->pressure && in->dhsml_factor && in->div_vel && in->curl_vel;
+}
+// the switches,
+template <class In> static int sph_hydro_switches(const In *in, const SphRefuse &refuse)
+{
+  if(!(in->gamma >= 1) || !(in->art_bulk_visc_const >= 0) || !(in->timebase_interval >= 0))
+    return refuse(NGRAVS_ERR_ARG, "gamma must be >= 1, art_bulk_visc_const and timebase_interval >= 0");
+  if(in->comoving && (!(in->hubble_a2 > 0) || !(in->fac_mu > 0) || !(in->fac_vsic_fix > 0)))
+    return refuse(NGRAVS_ERR_ARG, "comoving: hubble_a2, fac_mu and fac_vsic_fix must be > 0");
+  return NGRAVS_OK;
+}
+// and, after sph_begin, the upload of the seven columns to sph_vel_in, sph_h_in and sph_col_in with SphHydroParams from the switches
+// (have_ts and the timestep columns stay with the caller)
+template <class In> static int sph_hydro_own(ngravs_ctx *c, const In *in, const SphRefuse &refuse, SphHydroParams *hp)
+{
+  const int64_t n = c->n_local;
+  int rc;
+  if(c->sph_vel_in.ensure(3 * n) || c->sph_h_in.ensure(n) || c->sph_col_in.ensure(5 * n))
+    return refuse(NGRAVS_ERR_NOMEM, "device allocation failed");
+  if((rc = upload_column_f64(c, in->vel_pred, in->vel_pred_stride, 3, n, in->on_device, c->sph_vel_in.p)))
+    return rc;
+  if((rc = upload_column_f64(c, in->hsml, in->hsml_stride, 1, n, in->on_device, c->sph_h_in.p)))
+    return rc;
+  const double *col[5] = {in->density, in->pressure, in->dhsml_factor, in->div_vel, in->curl_vel};
+  const int64_t cstride[5] = {in->density_stride, in->pressure_stride, in->dhsml_factor_stride, in->div_vel_stride, in->curl_vel_stride};
+  for(int k = 0; k < 5; k++)
+    if((rc = upload_column_f64(c, col[k], cstride[k], 1, n, in->on_device, c->sph_col_in.p + k * n)))
+      return rc;
+  hp->periodic = c->cfg.periodic;
+  hp->box = c->cfg.box_size;
+  hp->boxhalf = 0.5 * c->cfg.box_size;
+  hp->comoving = in->comoving != 0;
+  hp->limiter = in->viscosity_limiter != 0;
+  hp->have_ts = 0;
+  hp->hubble_a2 = hp->comoving ? in->hubble_a2 : 1.0;   // hydra.c:96-97
+  hp->fac_mu = hp->comoving ? in->fac_mu : 1.0;
+  hp->fac_vsic_fix = hp->comoving ? in->fac_vsic_fix : 1.0;
+  hp->visc = in->art_bulk_visc_const;
+  hp->tbi = in->timebase_interval;
+  hp->gamma = in->gamma;
   return NGRAVS_OK;
 }
 
@@ -2011,24 +2111,15 @@ extern "C" int ngravs_sph_density(ngravs_ctx *c, const ngravs_sph_in_t *in, cons
 {
   if(!c)
     return NGRAVS_ERR_ARG;
-  auto refuse = [&](int code, const char *why) {
-    ngravs_report(c, code, std::string("ngravs_sph_density: ") + why);
-    return code;
-  };
+  const SphRefuse refuse = {c, "ngravs_sph_density"};
   if(!in || !in->hsml || !in->vel_pred)
     return refuse(NGRAVS_ERR_ARG, "in, in->hsml and in->vel_pred must not be NULL");
   if(!(in->des_num_ngb > 0) || !(in->max_num_ngb_deviation >= 0) || !(in->min_gas_hsml >= 0))
     return refuse(NGRAVS_ERR_ARG, "des_num_ngb must be > 0, max_num_ngb_deviation and min_gas_hsml >= 0");
   int rc;
-  if((rc = sph_ready(c, refuse)))
+  if((rc = sph_begin(c, refuse, max_rounds, kernel_ms, 1)) || sph_empty(c))
     return rc;
-  if(max_rounds)
-    *max_rounds = 0;
-  if(kernel_ms)
-    *kernel_ms = 0;
   const int64_t n = c->n_local;
-  if(n == 0 || c->nnodes <= 0)
-    return NGRAVS_OK;
   if(c->sph_vel_in.ensure(3 * n) || c->sph_h_in.ensure(n) || c->sph_vel.ensure(3 * n))
     return refuse(NGRAVS_ERR_NOMEM, "device allocation failed");
   if((rc = upload_column_f64(c, in->vel_pred, in->vel_stride, 3, n, in->on_device, c->sph_vel_in.p)))
@@ -2043,18 +2134,8 @@ extern "C" int ngravs_sph_density(ngravs_ctx *c, const ngravs_sph_in_t *in, cons
   HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
   if(kernel_ms)
     *kernel_ms = ev_ms(c);
-  if(c->tune.sph_verbose && st.targets > 0)   // the reference logs every round of its iteration (density.c:409-414); here one line per call
-    printf("ngravs_sph_density: %lld targets, rounds mean %.3f max %lld, %lld candidates tested, %lld neighbours\n", st.targets,
-           (double)st.sum_rounds / (double)st.targets, st.max_rounds, st.candidates, st.neighbours);
-  if(st.bad_hsml)
-    return refuse(NGRAVS_ERR_ARG, "a target's starting hsml is <= 0 or not finite");
-  if(st.stack_ovf)
-    return refuse(NGRAVS_ERR_TREE, "the tree is deeper than the walk's stack");
-  if(st.failed)
-    {
-      ngravs_report(c, 1155, "failed to converge in neighbour iteration in density()");   // density.c:416-421
-      return NGRAVS_ERR_STATE;
-    }
+  if((rc = sph_density_outcome(c, st, refuse)))
+    return rc;
   if(max_rounds)
     *max_rounds = (int32_t)st.max_rounds;
   const long long nt = st.targets;
@@ -2080,20 +2161,13 @@ extern "C" int ngravs_sph_hsml_guess(ngravs_ctx *c, double des_num_ngb, double *
 {
   if(!c)
     return NGRAVS_ERR_ARG;
-  auto refuse = [&](int code, const char *why) {
-    ngravs_report(c, code, std::string("ngravs_sph_hsml_guess: ") + why);
-    return code;
-  };
+  const SphRefuse refuse = {c, "ngravs_sph_hsml_guess"};
   if(!hsml || !(des_num_ngb > 0))
     return refuse(NGRAVS_ERR_ARG, "hsml must not be NULL and des_num_ngb must be > 0");
   int rc;
-  if((rc = sph_ready(c, refuse)))
+  if((rc = sph_begin(c, refuse, nullptr, kernel_ms, 1)) || sph_empty(c))
     return rc;
-  if(kernel_ms)
-    *kernel_ms = 0;
   const int64_t n = c->n_local;
-  if(n == 0 || c->nnodes <= 0)
-    return NGRAVS_OK;
   if(only_unset)
     {
       if(c->sph_h_in.ensure(n))
@@ -2123,50 +2197,23 @@ extern "C" int ngravs_sph_hydro(ngravs_ctx *c, const ngravs_hydro_in_t *in, cons
 {
   if(!c)
     return NGRAVS_ERR_ARG;
-  auto refuse = [&](int code, const char *why) {
-    ngravs_report(c, code, std::string("ngravs_sph_hydro: ") + why);
-    return code;
-  };
-  if(!in || !in->vel_pred || !in->hsml || !in->density || !in->pressure || !in->dhsml_factor || !in->div_vel || !in->curl_vel)
+  const SphRefuse refuse = {c, "ngravs_sph_hydro"};
+  if(!sph_hydro_cols_given(in))
     return refuse(NGRAVS_ERR_ARG, "in and its vel_pred, hsml, density, pressure, dhsml_factor, div_vel, curl_vel must not be NULL");
-  if(!(in->gamma >= 1) || !(in->art_bulk_visc_const >= 0) || !(in->timebase_interval >= 0))
-    return refuse(NGRAVS_ERR_ARG, "gamma must be >= 1, art_bulk_visc_const and timebase_interval >= 0");
-  if(in->comoving && (!(in->hubble_a2 > 0) || !(in->fac_mu > 0) || !(in->fac_vsic_fix > 0)))
-    return refuse(NGRAVS_ERR_ARG, "comoving: hubble_a2, fac_mu and fac_vsic_fix must be > 0");
   int rc;
-  if((rc = sph_ready(c, refuse)))
+  if((rc = sph_hydro_switches(in, refuse)))
     return rc;
-  if(kernel_ms)
-    *kernel_ms = 0;
+  if((rc = sph_begin(c, refuse, nullptr, kernel_ms, 1)) || sph_empty(c))
+    return rc;
   const int64_t n = c->n_local;
-  if(n == 0 || c->nnodes <= 0)
-    return NGRAVS_OK;
-  if(c->sph_vel_in.ensure(3 * n) || c->sph_h_in.ensure(n) || c->sph_col_in.ensure(5 * n) || c->sph_ts_in.ensure(n))
+  SphHydroParams hp;
+  if((rc = sph_hydro_own(c, in, refuse, &hp)))
+    return rc;
+  if(c->sph_ts_in.ensure(n))
     return refuse(NGRAVS_ERR_NOMEM, "device allocation failed");
-  if((rc = upload_column_f64(c, in->vel_pred, in->vel_pred_stride, 3, n, in->on_device, c->sph_vel_in.p)))
-    return rc;
-  if((rc = upload_column_f64(c, in->hsml, in->hsml_stride, 1, n, in->on_device, c->sph_h_in.p)))
-    return rc;
-  const double *col[5] = {in->density, in->pressure, in->dhsml_factor, in->div_vel, in->curl_vel};
-  const int64_t cstride[5] = {in->density_stride, in->pressure_stride, in->dhsml_factor_stride, in->div_vel_stride, in->curl_vel_stride};
-  for(int k = 0; k < 5; k++)
-    if((rc = upload_column_f64(c, col[k], cstride[k], 1, n, in->on_device, c->sph_col_in.p + k * n)))
-      return rc;
   if(in->timestep && (rc = upload_column_i32(c, in->timestep, in->timestep_stride, n, in->on_device, c->sph_ts_in.p)))
     return rc;
-  SphHydroParams hp;
-  hp.periodic = c->cfg.periodic;
-  hp.box = c->cfg.box_size;
-  hp.boxhalf = 0.5 * c->cfg.box_size;
-  hp.comoving = in->comoving != 0;
-  hp.limiter = in->viscosity_limiter != 0;
   hp.have_ts = in->timestep != nullptr;
-  hp.hubble_a2 = hp.comoving ? in->hubble_a2 : 1.0;   // hydra.c:96-97
-  hp.fac_mu = hp.comoving ? in->fac_mu : 1.0;
-  hp.fac_vsic_fix = hp.comoving ? in->fac_vsic_fix : 1.0;
-  hp.visc = in->art_bulk_visc_const;
-  hp.tbi = in->timebase_interval;
-  hp.gamma = in->gamma;
   HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
   SphHydroStats st;
   if((rc = sph_hydro_run(c, hp, &st)))
@@ -2174,12 +2221,8 @@ extern "C" int ngravs_sph_hydro(ngravs_ctx *c, const ngravs_hydro_in_t *in, cons
   HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
   if(kernel_ms)
     *kernel_ms = ev_ms(c);
-  if(st.bad_hsml)
-    return refuse(NGRAVS_ERR_ARG, "a type-0 row's hsml is <= 0 or not finite");
-  if(st.bad_density)
-    return refuse(NGRAVS_ERR_ARG, "a type-0 row's density is <= 0 or not finite");
-  if(st.bad_pressure)
-    return refuse(NGRAVS_ERR_ARG, "a type-0 row's pressure is < 0 or not finite");
+  if((rc = sph_hydro_rows_outcome(st, refuse)))
+    return rc;
   if(c->tune.sph_verbose && st.targets > 0)
     printf("ngravs_sph_hydro: %lld targets, %lld candidates tested, %lld pairs evaluated\n", st.targets, st.candidates, st.pairs);
   if(st.stack_ovf)
@@ -2202,42 +2245,24 @@ extern "C" int ngravs_sph_accelerations(ngravs_ctx *c, const ngravs_gas_in_t *in
 {
   if(!c)
     return NGRAVS_ERR_ARG;
-  auto refuse = [&](int code, const char *why) {
-    ngravs_report(c, code, std::string("ngravs_sph_accelerations: ") + why);
-    return code;
-  };
-  if(!in || !in->vel_pred || !in->entropy || !in->hsml || !in->density || !in->pressure || !in->dhsml_factor || !in->div_vel || !in->curl_vel)
+  const SphRefuse refuse = {c, "ngravs_sph_accelerations"};
+  if(!sph_hydro_cols_given(in) || !in->entropy)
     return refuse(NGRAVS_ERR_ARG, "in and its vel_pred, entropy, hsml, density, pressure, dhsml_factor, div_vel, curl_vel must not be NULL");
   if(!in->ti_begstep != !in->ti_endstep)
     return refuse(NGRAVS_ERR_ARG, "ti_begstep and ti_endstep must both be given or both be NULL");
   if(!(in->des_num_ngb > 0) || !(in->max_num_ngb_deviation >= 0) || !(in->min_gas_hsml >= 0))
     return refuse(NGRAVS_ERR_ARG, "des_num_ngb must be > 0, max_num_ngb_deviation and min_gas_hsml >= 0");
-  if(!(in->gamma >= 1) || !(in->art_bulk_visc_const >= 0) || !(in->timebase_interval >= 0))
-    return refuse(NGRAVS_ERR_ARG, "gamma must be >= 1, art_bulk_visc_const and timebase_interval >= 0");
-  if(in->comoving && (!(in->hubble_a2 > 0) || !(in->fac_mu > 0) || !(in->fac_vsic_fix > 0)))
-    return refuse(NGRAVS_ERR_ARG, "comoving: hubble_a2, fac_mu and fac_vsic_fix must be > 0");
   int rc;
-  if((rc = sph_ready(c, refuse)))
+  if((rc = sph_hydro_switches(in, refuse)))
     return rc;
-  if(max_rounds)
-    *max_rounds = 0;
-  if(kernel_ms)
-    kernel_ms[0] = kernel_ms[1] = kernel_ms[2] = 0;
+  if((rc = sph_begin(c, refuse, max_rounds, kernel_ms, 3)) || sph_empty(c))
+    return rc;
   const int64_t n = c->n_local;
-  if(n == 0 || c->nnodes <= 0)
-    return NGRAVS_OK;
-  if(c->sph_vel_in.ensure(3 * n) || c->sph_h_in.ensure(n) || c->sph_vel.ensure(3 * n) || c->sph_col_in.ensure(5 * n) ||
-     c->sph_gas_in.ensure(2 * n) || c->sph_ti_in.ensure(2 * n))
+  SphHydroParams hp;
+  if((rc = sph_hydro_own(c, in, refuse, &hp)))
+    return rc;
+  if(c->sph_vel.ensure(3 * n) || c->sph_gas_in.ensure(2 * n) || c->sph_ti_in.ensure(2 * n))
     return refuse(NGRAVS_ERR_NOMEM, "device allocation failed");
-  if((rc = upload_column_f64(c, in->vel_pred, in->vel_pred_stride, 3, n, in->on_device, c->sph_vel_in.p)))
-    return rc;
-  if((rc = upload_column_f64(c, in->hsml, in->hsml_stride, 1, n, in->on_device, c->sph_h_in.p)))
-    return rc;
-  const double *col[5] = {in->density, in->pressure, in->dhsml_factor, in->div_vel, in->curl_vel};
-  const int64_t cstride[5] = {in->density_stride, in->pressure_stride, in->dhsml_factor_stride, in->div_vel_stride, in->curl_vel_stride};
-  for(int k = 0; k < 5; k++)
-    if((rc = upload_column_f64(c, col[k], cstride[k], 1, n, in->on_device, c->sph_col_in.p + k * n)))
-      return rc;
   if((rc = upload_column_f64(c, in->entropy, in->entropy_stride, 1, n, in->on_device, c->sph_gas_in.p)))
     return rc;
   if(in->dt_entropy && (rc = upload_column_f64(c, in->dt_entropy, in->dt_entropy_stride, 1, n, in->on_device, c->sph_gas_in.p + n)))
@@ -2251,19 +2276,7 @@ extern "C" int ngravs_sph_accelerations(ngravs_ctx *c, const ngravs_gas_in_t *in
   gp.minh = in->min_gas_hsml;
   gp.ti_current = in->ti_current;
   gp.have_dte = in->dt_entropy != nullptr;
-  SphHydroParams hp;
-  hp.periodic = c->cfg.periodic;
-  hp.box = c->cfg.box_size;
-  hp.boxhalf = 0.5 * c->cfg.box_size;
-  hp.comoving = in->comoving != 0;
-  hp.limiter = in->viscosity_limiter != 0;
   hp.have_ts = in->ti_begstep != nullptr;
-  hp.hubble_a2 = hp.comoving ? in->hubble_a2 : 1.0;   // hydra.c:96-97
-  hp.fac_mu = hp.comoving ? in->fac_mu : 1.0;
-  hp.fac_vsic_fix = hp.comoving ? in->fac_vsic_fix : 1.0;
-  hp.visc = in->art_bulk_visc_const;
-  hp.tbi = in->timebase_interval;
-  hp.gamma = in->gamma;
   HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
   HIP_TRY(c, hipEventRecord(c->ev1, c->stream));    // (recorded again where the stages end: a call that ends early reads 0)
   HIP_TRY(c, hipEventRecord(c->evk0, c->stream));
@@ -2287,24 +2300,8 @@ extern "C" int ngravs_sph_accelerations(ngravs_ctx *c, const ngravs_gas_in_t *in
       for(int k = 0; k < 3; k++)
         kernel_ms[k] = ms[k];
     }
-  if(c->tune.sph_verbose && ds.targets > 0)
-    printf("ngravs_sph_density: %lld targets, rounds mean %.3f max %lld, %lld candidates tested, %lld neighbours\n", ds.targets,
-           (double)ds.sum_rounds / (double)ds.targets, ds.max_rounds, ds.candidates, ds.neighbours);
-  if(ds.bad_hsml)
-    return refuse(NGRAVS_ERR_ARG, "a target's starting hsml is <= 0 or not finite");
-  if(ds.stack_ovf)
-    return refuse(NGRAVS_ERR_TREE, "the tree is deeper than the walk's stack");
-  if(ds.failed)
-    {
-      ngravs_report(c, 1155, "failed to converge in neighbour iteration in density()");   // density.c:416-421
-      return NGRAVS_ERR_STATE;
-    }
-  if(hs.bad_hsml)
-    return refuse(NGRAVS_ERR_ARG, "a type-0 row's hsml is <= 0 or not finite");
-  if(hs.bad_density)
-    return refuse(NGRAVS_ERR_ARG, "a type-0 row's density is <= 0 or not finite");
-  if(hs.bad_pressure)
-    return refuse(NGRAVS_ERR_ARG, "a type-0 row's pressure is < 0 or not finite");
+  if((rc = sph_density_outcome(c, ds, refuse)) || (rc = sph_hydro_rows_outcome(hs, refuse)))
+    return rc;
   if(c->tune.sph_verbose && hs.targets > 0)
     printf("ngravs_sph_hydro: %lld targets, %lld candidates tested, %lld pairs evaluated\n", hs.targets, hs.candidates, hs.pairs);
   if(hs.stack_ovf)
@@ -2370,23 +2367,16 @@ extern "C" int ngravs_sph_density_sums(ngravs_ctx *c, const double *own_vel_pred
 {
   if(!c)
     return NGRAVS_ERR_ARG;
-  auto refuse = [&](int code, const char *why) {
-    ngravs_report(c, code, std::string("ngravs_sph_density_sums: ") + why);
-    return code;
-  };
+  const SphRefuse refuse = {c, "ngravs_sph_density_sums"};
   if(nt < 0 || nt > 0x7fffffff)
     return refuse(NGRAVS_ERR_ARG, "nt must be >= 0 (and below 2^31)");
   if(!own_vel_pred || !tg || (nt > 0 && (!tg->pos || !tg->vel || !tg->hsml || !sums)))
     return refuse(NGRAVS_ERR_ARG, "own_vel_pred, targets, its pos, vel, hsml and sums must not be NULL");
   int rc;
-  if((rc = sph_ready(c, refuse)))
+  if((rc = sph_begin(c, refuse, nullptr, kernel_ms, 1)) || nt == 0)
     return rc;
-  if(kernel_ms)
-    *kernel_ms = 0;
-  if(nt == 0)
-    return NGRAVS_OK;
   const int64_t n = c->n_local;
-  if(n == 0 || c->nnodes <= 0)
+  if(sph_empty(c))
     return sph_write_sums(c, nullptr, SPH_NSUMS, nt, sums, on_device);
   if(c->sph_vel_in.ensure(3 * n) || c->sph_vel.ensure(3 * n) || c->sph_tg_in.ensure((size_t)(SPH_TG_H + 1 + 3) * nt))
     return refuse(NGRAVS_ERR_NOMEM, "device allocation failed");
@@ -2420,42 +2410,26 @@ extern "C" int ngravs_sph_hydro_sums(ngravs_ctx *c, const ngravs_hydro_in_t *in,
 {
   if(!c)
     return NGRAVS_ERR_ARG;
-  auto refuse = [&](int code, const char *why) {
-    ngravs_report(c, code, std::string("ngravs_sph_hydro_sums: ") + why);
-    return code;
-  };
+  const SphRefuse refuse = {c, "ngravs_sph_hydro_sums"};
   if(nt < 0 || nt > 0x7fffffff)
     return refuse(NGRAVS_ERR_ARG, "nt must be >= 0 (and below 2^31)");
-  if(!in || !in->vel_pred || !in->hsml || !in->density || !in->pressure || !in->dhsml_factor || !in->div_vel || !in->curl_vel)
+  if(!sph_hydro_cols_given(in))
     return refuse(NGRAVS_ERR_ARG, "own and its vel_pred, hsml, density, pressure, dhsml_factor, div_vel, curl_vel must not be NULL");
   if(!tg || (nt > 0 && (!tg->pos || !tg->vel || !tg->hsml || !tg->mass || !tg->density || !tg->pressure || !tg->dhsml_factor || !tg->f1 || !sums)))
     return refuse(NGRAVS_ERR_ARG, "targets, its pos, vel, hsml, mass, density, pressure, dhsml_factor, f1 and sums must not be NULL");
-  if(!(in->gamma >= 1) || !(in->art_bulk_visc_const >= 0) || !(in->timebase_interval >= 0))
-    return refuse(NGRAVS_ERR_ARG, "gamma must be >= 1, art_bulk_visc_const and timebase_interval >= 0");
-  if(in->comoving && (!(in->hubble_a2 > 0) || !(in->fac_mu > 0) || !(in->fac_vsic_fix > 0)))
-    return refuse(NGRAVS_ERR_ARG, "comoving: hubble_a2, fac_mu and fac_vsic_fix must be > 0");
   int rc;
-  if((rc = sph_ready(c, refuse)))
+  if((rc = sph_hydro_switches(in, refuse)))
     return rc;
-  if(kernel_ms)
-    *kernel_ms = 0;
-  if(nt == 0)
-    return NGRAVS_OK;
+  if((rc = sph_begin(c, refuse, nullptr, kernel_ms, 1)) || nt == 0)
+    return rc;
   const int64_t n = c->n_local;
-  if(n == 0 || c->nnodes <= 0)
+  if(sph_empty(c))
     return sph_write_sums(c, nullptr, SPH_HY_NRES, nt, sums, on_device);
-  if(c->sph_vel_in.ensure(3 * n) || c->sph_h_in.ensure(n) || c->sph_col_in.ensure(5 * n) || c->sph_ts_in.ensure(n) ||
-     c->sph_tg_in.ensure((size_t)(SPH_TG_NCOL + 3) * nt) || c->sph_tg_ts.ensure((size_t)nt))
+  SphHydroParams hp;
+  if((rc = sph_hydro_own(c, in, refuse, &hp)))
+    return rc;
+  if(c->sph_ts_in.ensure(n) || c->sph_tg_in.ensure((size_t)(SPH_TG_NCOL + 3) * nt) || c->sph_tg_ts.ensure((size_t)nt))
     return refuse(NGRAVS_ERR_NOMEM, "device allocation failed");
-  if((rc = upload_column_f64(c, in->vel_pred, in->vel_pred_stride, 3, n, in->on_device, c->sph_vel_in.p)))
-    return rc;
-  if((rc = upload_column_f64(c, in->hsml, in->hsml_stride, 1, n, in->on_device, c->sph_h_in.p)))
-    return rc;
-  const double *col[5] = {in->density, in->pressure, in->dhsml_factor, in->div_vel, in->curl_vel};
-  const int64_t cstride[5] = {in->density_stride, in->pressure_stride, in->dhsml_factor_stride, in->div_vel_stride, in->curl_vel_stride};
-  for(int k = 0; k < 5; k++)
-    if((rc = upload_column_f64(c, col[k], cstride[k], 1, n, in->on_device, c->sph_col_in.p + k * n)))
-      return rc;
   if(in->timestep && (rc = upload_column_i32(c, in->timestep, in->timestep_stride, n, in->on_device, c->sph_ts_in.p)))
     return rc;
   if((rc = upload_column_f64(c, tg->pos, tg->pos_stride, 3, nt, on_device, c->sph_tg_in.p)) ||
@@ -2468,19 +2442,7 @@ extern "C" int ngravs_sph_hydro_sums(ngravs_ctx *c, const ngravs_hydro_in_t *in,
       return rc;
   if(tg->timestep && (rc = upload_column_i32(c, tg->timestep, tg->timestep_stride, nt, on_device, c->sph_tg_ts.p)))
     return rc;
-  SphHydroParams hp;
-  hp.periodic = c->cfg.periodic;
-  hp.box = c->cfg.box_size;
-  hp.boxhalf = 0.5 * c->cfg.box_size;
-  hp.comoving = in->comoving != 0;
-  hp.limiter = in->viscosity_limiter != 0;
   hp.have_ts = in->timestep != nullptr;
-  hp.hubble_a2 = hp.comoving ? in->hubble_a2 : 1.0;   // hydra.c:96-97
-  hp.fac_mu = hp.comoving ? in->fac_mu : 1.0;
-  hp.fac_vsic_fix = hp.comoving ? in->fac_vsic_fix : 1.0;
-  hp.visc = in->art_bulk_visc_const;
-  hp.tbi = in->timebase_interval;
-  hp.gamma = in->gamma;
   HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
   SphSumsStats st;
   SphHydroStats own;
@@ -2489,12 +2451,8 @@ extern "C" int ngravs_sph_hydro_sums(ngravs_ctx *c, const ngravs_hydro_in_t *in,
   HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
   if(kernel_ms)
     *kernel_ms = ev_ms(c);
-  if(own.bad_hsml)
-    return refuse(NGRAVS_ERR_ARG, "a type-0 row's hsml is <= 0 or not finite");
-  if(own.bad_density)
-    return refuse(NGRAVS_ERR_ARG, "a type-0 row's density is <= 0 or not finite");
-  if(own.bad_pressure)
-    return refuse(NGRAVS_ERR_ARG, "a type-0 row's pressure is < 0 or not finite");
+  if((rc = sph_hydro_rows_outcome(own, refuse)))
+    return rc;
   if(st.bad_hsml)
     return refuse(NGRAVS_ERR_ARG, "a target's hsml is <= 0 or not finite");
   if(st.bad_density)

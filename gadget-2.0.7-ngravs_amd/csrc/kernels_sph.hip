@@ -25,6 +25,16 @@
 //      cube lies within max(largest h_i of the wave, hmax of the child) of the hull of the lanes' positions, the staged entry holds
 //      13 doubles, and every lane applies hydra.c:416-534 to every staged source.
 //
+// How the four walk kernels share their text.  sph_wave_hull (the hull of a wave's lanes), sph_stage_density (the seven staged
+// doubles of a density source) and sph_wave_counters (the statistics, one set of atomics per wave) serve all of them.
+// sph_hull_walk is the depth-first walk as a template; k_sph_density_sums, k_sph_hydro and k_sph_hydro_sums go through it.
+// sph_hydro_wave is the whole body of a hydro wave; k_sph_hydro and k_sph_hydro_sums are wrappers that hand it two functors: where
+// a lane's target comes from (a row of sph_hsrc, or a record of sph_tg_in) and where its five results go (with or without
+// hydra.c:320).  k_sph_density stands apart in ONE respect: it keeps an inline copy of the walk, because called through the
+// template it takes 180 VGPRs instead of 164 and loses its third wave per SIMD (see sph_hull_walk); the three small helpers leave
+// its registers, LDS and occupancy as they were, so it uses them.  Its per-lane acceptance rules are not merged with
+// sph_density_update_one (engine.hpp) either: that function is compiled with contraction off, the kernel is not.
+//
 // The first guess of the smoothing lengths (ngravs_sph_hsml_guess; setup_smoothinglengths, init.c:229-247):
 // k_sph_gas_cols : one thread per sorted particle: gas mass and gas flag, the inputs of two prefix scans over the Peano-ordered rows
 // k_sph_hsml_guess : one lane per gas row: from the root down the cells that hold the particle, a node's gas mass and count as
@@ -113,6 +123,65 @@ __device__ __forceinline__ void sph_block(const double (*__restrict__ s)[SPH_STA
     }
 }
 
+// The hull of a wave: the box around the live lanes' x -/+ pad (pad: h for the search boxes of the density walks, ngb.c:206-210;
+// 0 for the bare positions of the hydro walks), as centre and half sides, the latter a hair wider than the boxes' own rounding.
+struct SphHull
+{
+  double cx, cy, cz, hx, hy, hz;
+};
+__device__ __forceinline__ SphHull sph_wave_hull(double x, double y, double z, double pad, bool live)
+{
+  const double BIG = 1e300;
+  const double lx = wave_min(live ? x - pad : BIG), ly = wave_min(live ? y - pad : BIG), lz = wave_min(live ? z - pad : BIG);
+  const double ux = wave_max(live ? x + pad : -BIG), uy = wave_max(live ? y + pad : -BIG), uz = wave_max(live ? z + pad : -BIG);
+  SphHull H;
+  H.cx = wave_uniform(0.5 * (lx + ux)), H.cy = wave_uniform(0.5 * (ly + uy)), H.cz = wave_uniform(0.5 * (lz + uz));
+  H.hx = wave_uniform(0.5 * (ux - lx) * (1 + 1e-12)), H.hy = wave_uniform(0.5 * (uy - ly) * (1 + 1e-12));
+  H.hz = wave_uniform(0.5 * (uz - lz) * (1 + 1e-12));
+  return H;
+}
+
+// particle p into slot q of a density walk's staging block: position, mass, VelPred
+__device__ __forceinline__ void sph_stage_density(double (*__restrict__ src)[SPH_STAGE], int q, long long p, const double4 *__restrict__ pm,
+                                                  const double *__restrict__ svel)
+{
+  const double4 pp = pm[p];
+  src[0][q] = pp.x, src[1][q] = pp.y, src[2][q] = pp.z, src[3][q] = pp.w;
+  src[4][q] = svel[3 * p], src[5][q] = svel[3 * p + 1], src[6][q] = svel[3 * p + 2];
+}
+
+// statistics of a walk kernel: one set of atomics per wave.  ROUNDS: also the lanes' round counts nr (k_sph_density)
+template <bool ROUNDS>
+__device__ __forceinline__ void sph_wave_counters(int lane, unsigned ncand, unsigned nngb, int nr, bool ovf,
+                                                  unsigned long long *__restrict__ counters)
+{
+  unsigned long long cand = ncand, ngb = nngb, sumr = (unsigned long long)nr;
+  int maxr = nr;
+  for(int off = 32; off > 0; off >>= 1)
+    {
+      cand += __shfl_xor(cand, off);
+      ngb += __shfl_xor(ngb, off);
+      if(ROUNDS)
+        {
+          sumr += __shfl_xor(sumr, off);
+          const int o = __shfl_xor(maxr, off);
+          maxr = o > maxr ? o : maxr;
+        }
+    }
+  if(lane == 0)
+    {
+      atomicAdd(&counters[SPH_C_CAND], cand);
+      atomicAdd(&counters[SPH_C_NGB], ngb);
+      if(ROUNDS)
+        {
+          atomicAdd(&counters[SPH_C_SUMR], sumr);
+          atomicMax(&counters[SPH_C_MAXR], (unsigned long long)maxr);
+        }
+      if(ovf)
+        atomicAdd(&counters[SPH_C_OVF], 1ull);
+    }
+}
+
 // The wave's depth-first walk of k_sph_density for a hull (centre hc, half sides hh) as a function of its own, for k_sph_hydro.
 // k_sph_density keeps its inline copy: called through this template (same arithmetic, same results) the compiler gives it 180
 // instead of 164 VGPRs, which costs the third wave per SIMD, and holding it to three waves spills.  A node is popped from the LDS
@@ -123,8 +192,8 @@ __device__ __forceinline__ void sph_block(const double (*__restrict__ s)[SPH_STA
 // lane over it.  Returns false when the LIFO would overflow (nothing is written past it).
 template <int STAGE, class Widen, class Put, class Block>
 __device__ __forceinline__ bool sph_hull_walk(const TreeView &tv, const double4 *__restrict__ pm, const unsigned char *__restrict__ type,
-                                              long long n, int periodic, double box, double boxhalf, double hcx, double hcy, double hcz,
-                                              double hhx, double hhy, double hhz, int *stack, int lane, Widen widen, Put put, Block block)
+                                              long long n, int periodic, double box, double boxhalf, const SphHull &H, int *stack, int lane,
+                                              Widen widen, Put put, Block block)
 {
   static_assert(STAGE >= 128, "a chunk of 64 must fit behind 64 staged entries");
   int top = 0, fill = 0;
@@ -155,7 +224,7 @@ __device__ __forceinline__ bool sph_hull_walk(const TreeView &tv, const double4 
             }
           if(ch != -1)
             {
-              double dx = cx - hcx, dy = cy - hcy, dz = cz - hcz;
+              double dx = cx - H.cx, dy = cy - H.cy, dz = cz - H.cz;
               if(periodic)
                 {
                   dx = nearest(dx, box, boxhalf);
@@ -164,7 +233,7 @@ __device__ __forceinline__ bool sph_hull_walk(const TreeView &tv, const double4 
                 }
               const double wd = widen(ch);
               // (ngb.c:146-177 for the hull instead of one particle's box)
-              if(fabs(dx) - half <= hhx + wd && fabs(dy) - half <= hhy + wd && fabs(dz) - half <= hhz + wd)
+              if(fabs(dx) - half <= H.hx + wd && fabs(dy) - half <= H.hy + wd && fabs(dz) - half <= H.hz + wd)
                 {
                   if(ch >= 0)
                     {
@@ -260,12 +329,7 @@ __global__ __launch_bounds__(64 * SPH_WAVES) void k_sph_density(TreeView tv, con
   bool ovf = false;
   while(wave_any(live))
     {
-      // the hull of the unconverged lanes' search boxes (ngb.c:206-210), a hair wider than the boxes' own rounding
-      const double lx = wave_min(live ? L.x - h : BIG), ly = wave_min(live ? L.y - h : BIG), lz = wave_min(live ? L.z - h : BIG);
-      const double ux = wave_max(live ? L.x + h : -BIG), uy = wave_max(live ? L.y + h : -BIG), uz = wave_max(live ? L.z + h : -BIG);
-      const double hcx = wave_uniform(0.5 * (lx + ux)), hcy = wave_uniform(0.5 * (ly + uy)), hcz = wave_uniform(0.5 * (lz + uz));
-      const double hhx = wave_uniform(0.5 * (ux - lx) * (1 + 1e-12)), hhy = wave_uniform(0.5 * (uy - ly) * (1 + 1e-12)),
-                   hhz = wave_uniform(0.5 * (uz - lz) * (1 + 1e-12));
+      const SphHull H = sph_wave_hull(L.x, L.y, L.z, h, live);   // of the unconverged lanes' search boxes
       L.h2 = h * h;
       L.hinv = 1.0 / h;
       L.hinv3 = L.hinv * L.hinv * L.hinv;
@@ -300,7 +364,7 @@ __global__ __launch_bounds__(64 * SPH_WAVES) void k_sph_density(TreeView tv, con
                 }
               if(ch != -1)
                 {
-                  double dx = cx - hcx, dy = cy - hcy, dz = cz - hcz;
+                  double dx = cx - H.cx, dy = cy - H.cy, dz = cz - H.cz;
                   if(sp.periodic)
                     {
                       dx = nearest(dx, sp.box, sp.boxhalf);
@@ -308,7 +372,7 @@ __global__ __launch_bounds__(64 * SPH_WAVES) void k_sph_density(TreeView tv, con
                       dz = nearest(dz, sp.box, sp.boxhalf);
                     }
                   // (ngb.c:272-297 for the hull instead of one particle's box)
-                  if(fabs(dx) - half <= hhx && fabs(dy) - half <= hhy && fabs(dz) - half <= hhz)
+                  if(fabs(dx) - half <= H.hx && fabs(dy) - half <= H.hy && fabs(dz) - half <= H.hz)
                     {
                       if(ch >= 0)
                         {
@@ -347,12 +411,7 @@ __global__ __launch_bounds__(64 * SPH_WAVES) void k_sph_density(TreeView tv, con
                   const bool ok = o + lane < cn && p < n && type[p] == 0;   // P[p].Type > 0: not a neighbour (ngb.c:221)
                   const unsigned long long m = __ballot(ok ? 1 : 0);
                   if(ok)
-                    {
-                      const int q = fill + lane_prefix(m);
-                      const double4 pp = pm[p];
-                      src[0][q] = pp.x, src[1][q] = pp.y, src[2][q] = pp.z, src[3][q] = pp.w;
-                      src[4][q] = svel[3 * p], src[5][q] = svel[3 * p + 1], src[6][q] = svel[3 * p + 2];
-                    }
+                    sph_stage_density(src, fill + lane_prefix(m), p, pm, svel);
                   fill += __popcll(m);
                   if(fill > 64)
                     {
@@ -428,26 +487,7 @@ __global__ __launch_bounds__(64 * SPH_WAVES) void k_sph_density(TreeView tv, con
             }
         }
     }
-  // statistics: one set of atomics per wave
-  unsigned long long cand = L.ncand, ngb = L.nngb, sumr = (unsigned long long)nr;
-  int maxr = nr;
-  for(int off = 32; off > 0; off >>= 1)
-    {
-      cand += __shfl_xor(cand, off);
-      ngb += __shfl_xor(ngb, off);
-      sumr += __shfl_xor(sumr, off);
-      const int o = __shfl_xor(maxr, off);
-      maxr = o > maxr ? o : maxr;
-    }
-  if(lane == 0)
-    {
-      atomicAdd(&counters[SPH_C_CAND], cand);
-      atomicAdd(&counters[SPH_C_NGB], ngb);
-      atomicAdd(&counters[SPH_C_SUMR], sumr);
-      atomicMax(&counters[SPH_C_MAXR], (unsigned long long)maxr);
-      if(ovf)
-        atomicAdd(&counters[SPH_C_OVF], 1ull);
-    }
+  sph_wave_counters<true>(lane, L.ncand, L.nngb, nr, ovf, counters);
 }
 
 struct SphIsTarget
@@ -467,6 +507,29 @@ static TreeView sph_tree_view(ngravs_ctx *c)
   tv.mom = c->n_mom.p;
   tv.nnodes = (int)c->nnodes;
   return tv;
+}
+
+// sph_counters on the host (waits for the stream)
+static int sph_read_counters(ngravs_ctx *c, unsigned long long h[SPH_C_COUNT])
+{
+  HIP_TRY(c, hipMemcpyAsync(h, c->sph_counters.p, SPH_C_COUNT * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return NGRAVS_OK;
+}
+
+// workgroups of a kernel that gives one wave to 64 targets, waves waves per workgroup
+static unsigned sph_wave_grid(long long nt, int waves)
+{
+  const long long nwaves = (nt + 63) / 64;
+  return (unsigned)((nwaves + waves - 1) / waves);
+}
+
+// periodic, box, boxhalf of SphParams or SphHydroParams
+template <class P> static void sph_set_box(const ngravs_ctx *c, P *p)
+{
+  p->periodic = c->cfg.periodic;
+  p->box = c->cfg.box_size;
+  p->boxhalf = 0.5 * c->cfg.box_size;
 }
 
 // the targets: active type-0 rows in Peano order (density.c:95, :123; hydra.c:101-105), compacted into sph_tlist as the group
@@ -494,21 +557,17 @@ static int sph_targets(ngravs_ctx *c, int *count)
 static int sph_density_walk(ngravs_ctx *c, double des_num_ngb, double max_dev, double min_hsml, long long nt, SphStats *st)
 {
   SphParams sp;
-  sp.periodic = c->cfg.periodic;
-  sp.box = c->cfg.box_size;
-  sp.boxhalf = 0.5 * c->cfg.box_size;
+  sph_set_box(c, &sp);
   sp.des = des_num_ngb;
   sp.dev = max_dev;
   sp.minh = min_hsml;
-  const long long nwaves = (nt + 63) / 64;
-  const unsigned nb = (unsigned)((nwaves + SPH_WAVES - 1) / SPH_WAVES);
-  hipLaunchKernelGGL(k_sph_density, dim3(nb), dim3(64 * SPH_WAVES), 0, c->stream, sph_tree_view(c), c->s_pm.p, c->s_type.p, c->sph_vel.p,
-                     c->s_idx.p, c->sph_tlist.p, nt, (long long)c->n, c->sph_h_in.p, sp, c->sph_res.p, c->sph_row.p, c->sph_rounds.p,
-                     c->sph_counters.p);
+  hipLaunchKernelGGL(k_sph_density, dim3(sph_wave_grid(nt, SPH_WAVES)), dim3(64 * SPH_WAVES), 0, c->stream, sph_tree_view(c), c->s_pm.p,
+                     c->s_type.p, c->sph_vel.p, c->s_idx.p, c->sph_tlist.p, nt, (long long)c->n, c->sph_h_in.p, sp, c->sph_res.p, c->sph_row.p,
+                     c->sph_rounds.p, c->sph_counters.p);
   HIP_TRY(c, hipGetLastError());
   unsigned long long h[SPH_C_COUNT];
-  HIP_TRY(c, hipMemcpyAsync(h, c->sph_counters.p, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if(int rc = sph_read_counters(c, h))
+    return rc;
   st->bad_hsml = (long long)h[SPH_C_BAD];
   st->failed = (long long)h[SPH_C_FAILED];
   st->stack_ovf = (long long)h[SPH_C_OVF];
@@ -910,11 +969,14 @@ __device__ __forceinline__ void sph_hydro_block(const double (*__restrict__ s)[S
     }
 }
 
-__global__ __launch_bounds__(64 * SPH_HWAVES) void k_sph_hydro(TreeView tv, const double4 *__restrict__ pm, const unsigned char *__restrict__ type,
-                                                               const double *__restrict__ hs, const double *__restrict__ hmax,
-                                                               const unsigned int *__restrict__ idx, const int *__restrict__ tlist,
-                                                               long long nt, long long n, SphHydroParams hp, double *__restrict__ res,
-                                                               int *__restrict__ row, unsigned long long *__restrict__ counters)
+// One wave of the hydro walk, the body of k_sph_hydro and k_sph_hydro_sums: the hull of the lanes' positions, ONE sph_hull_walk in
+// which a child is tested against the hull widened by max(largest h_i of the wave, hmax of the child) (ngb.c:146-177), the 13
+// staged doubles of a source, sph_hydro_block, the counters.  The two kernels differ in where a lane's target comes from and where
+// its results go: load(t, L) fills L for target t and returns its h, store(t, L) writes the five results.
+template <class Load, class Store>
+__device__ __forceinline__ void sph_hydro_wave(const TreeView &tv, const double4 *__restrict__ pm, const unsigned char *__restrict__ type,
+                                               const double *__restrict__ hs, const double *__restrict__ hmax, long long nt, long long n,
+                                               const SphHydroParams &hp, unsigned long long *__restrict__ counters, Load load, Store store)
 {
   __shared__ double s_src[SPH_HWAVES][SPH_HFIELDS][SPH_STAGE];
   __shared__ int s_stack[SPH_HWAVES][SPH_STACK];
@@ -924,39 +986,17 @@ __global__ __launch_bounds__(64 * SPH_HWAVES) void k_sph_hydro(TreeView tv, cons
     return;
   double (*src)[SPH_STAGE] = s_src[w];
   int *stack = s_stack[w];
-  const double BIG = 1e300;
   const double *sh = hs + SPH_HS_H * n;
 
   const bool live = t < nt;
   SphHydroLane L = {};
   double h = 0;
-  int myrow = 0;
   if(live)
-    {
-      const int i = tlist[t];
-      const double4 p = pm[i];
-      L.x = p.x, L.y = p.y, L.z = p.z, L.mass = p.w;
-      L.vx = hs[SPH_HS_VX * n + i], L.vy = hs[SPH_HS_VY * n + i], L.vz = hs[SPH_HS_VZ * n + i];
-      h = sh[i];
-      L.h2 = h * h;
-      L.hinv = 1.0 / h;
-      L.hinv4 = L.hinv * L.hinv * L.hinv * L.hinv;
-      L.rho = hs[SPH_HS_RHO * n + i];
-      L.por2 = hs[SPH_HS_POR2 * n + i];
-      L.cs = hs[SPH_HS_CSI * n + i];
-      L.f1 = hs[SPH_HS_F1 * n + i];
-      L.ts = hs[SPH_HS_TS * n + i];
-      myrow = (int)idx[i];
-    }
-  // the hull of the lanes' positions; a child is tested against it widened by max(largest h_i, hmax of the child) (ngb.c:146-177)
-  const double lx = wave_min(live ? L.x : BIG), ly = wave_min(live ? L.y : BIG), lz = wave_min(live ? L.z : BIG);
-  const double ux = wave_max(live ? L.x : -BIG), uy = wave_max(live ? L.y : -BIG), uz = wave_max(live ? L.z : -BIG);
+    h = load(t, L);
+  const SphHull H = sph_wave_hull(L.x, L.y, L.z, 0.0, live);
   const double hw = wave_uniform(wave_max(live ? h : 0.0));
-  const double hcx = wave_uniform(0.5 * (lx + ux)), hcy = wave_uniform(0.5 * (ly + uy)), hcz = wave_uniform(0.5 * (lz + uz));
-  const double hhx = wave_uniform(0.5 * (ux - lx) * (1 + 1e-12)), hhy = wave_uniform(0.5 * (uy - ly) * (1 + 1e-12)),
-               hhz = wave_uniform(0.5 * (uz - lz) * (1 + 1e-12));
   const bool ok = sph_hull_walk<SPH_STAGE>(
-    tv, pm, type, n, hp.periodic, hp.box, hp.boxhalf, hcx, hcy, hcz, hhx, hhy, hhz, stack, lane,
+    tv, pm, type, n, hp.periodic, hp.box, hp.boxhalf, H, stack, lane,
     [&](int ch) { return fmax(hw, ch >= 0 ? hmax[ch] : sh[-2 - ch]) * (1 + 1e-12); },
     [&](int q, long long p) {
       const double4 pp = pm[p];
@@ -967,7 +1007,36 @@ __global__ __launch_bounds__(64 * SPH_HWAVES) void k_sph_hydro(TreeView tv, cons
     },
     [&](int cnt) { sph_hydro_block(src, cnt, live, hp, L); });
   if(live && ok)
-    {
+    store(t, L);
+  sph_wave_counters<false>(lane, L.ncand, L.npair, 0, !ok, counters);
+}
+
+// targets: rows of sph_hsrc by sph_tlist; results [column][nt] by list position, dt_entropy through hydra.c:320
+__global__ __launch_bounds__(64 * SPH_HWAVES) void k_sph_hydro(TreeView tv, const double4 *__restrict__ pm, const unsigned char *__restrict__ type,
+                                                               const double *__restrict__ hs, const double *__restrict__ hmax,
+                                                               const unsigned int *__restrict__ idx, const int *__restrict__ tlist,
+                                                               long long nt, long long n, SphHydroParams hp, double *__restrict__ res,
+                                                               int *__restrict__ row, unsigned long long *__restrict__ counters)
+{
+  sph_hydro_wave(
+    tv, pm, type, hs, hmax, nt, n, hp, counters,
+    [&](long long t, SphHydroLane &L) {
+      const int i = tlist[t];
+      const double4 p = pm[i];
+      L.x = p.x, L.y = p.y, L.z = p.z, L.mass = p.w;
+      L.vx = hs[SPH_HS_VX * n + i], L.vy = hs[SPH_HS_VY * n + i], L.vz = hs[SPH_HS_VZ * n + i];
+      const double h = hs[SPH_HS_H * n + i];
+      L.h2 = h * h;
+      L.hinv = 1.0 / h;
+      L.hinv4 = L.hinv * L.hinv * L.hinv * L.hinv;
+      L.rho = hs[SPH_HS_RHO * n + i];
+      L.por2 = hs[SPH_HS_POR2 * n + i];
+      L.cs = hs[SPH_HS_CSI * n + i];
+      L.f1 = hs[SPH_HS_F1 * n + i];
+      L.ts = hs[SPH_HS_TS * n + i];
+      return h;
+    },
+    [&](long long t, const SphHydroLane &L) {
       // final operations (hydra.c:320)
       const double gm1 = hp.gamma - 1;
       res[SPH_HY_ACCX * nt + t] = L.ax;
@@ -975,21 +1044,8 @@ __global__ __launch_bounds__(64 * SPH_HWAVES) void k_sph_hydro(TreeView tv, cons
       res[SPH_HY_ACCZ * nt + t] = L.az;
       res[SPH_HY_DTENTR * nt + t] = L.dte * (gm1 / (hp.hubble_a2 * pow(L.rho, gm1)));
       res[SPH_HY_MAXSIG * nt + t] = L.maxsig;
-      row[t] = myrow;
-    }
-  unsigned long long cand = L.ncand, pairs = L.npair;
-  for(int off = 32; off > 0; off >>= 1)
-    {
-      cand += __shfl_xor(cand, off);
-      pairs += __shfl_xor(pairs, off);
-    }
-  if(lane == 0)
-    {
-      atomicAdd(&counters[SPH_C_CAND], cand);
-      atomicAdd(&counters[SPH_C_NGB], pairs);
-      if(!ok)
-        atomicAdd(&counters[SPH_C_OVF], 1ull);
-    }
+      row[t] = (int)idx[tlist[t]];
+    });
 }
 
 // force_update_hmax from the Hsml column of sph_hsrc
@@ -1011,21 +1067,48 @@ static int sph_hmax_levels(ngravs_ctx *c)
 // k_sph_hydro over the nt targets of sph_tlist: res [SPH_HY_NRES][nt] and sph_row in list order
 static int sph_hydro_walk(ngravs_ctx *c, const SphHydroParams &hp, long long nt, double *res)
 {
-  const long long n = c->n;
-  const long long nwaves = (nt + 63) / 64;
-  const unsigned nb = (unsigned)((nwaves + SPH_HWAVES - 1) / SPH_HWAVES);
-  hipLaunchKernelGGL(k_sph_hydro, dim3(nb), dim3(64 * SPH_HWAVES), 0, c->stream, sph_tree_view(c), c->s_pm.p, c->s_type.p, c->sph_hsrc.p,
-                     c->sph_hmax.p, c->s_idx.p, c->sph_tlist.p, nt, n, hp, res, c->sph_row.p, c->sph_counters.p);
+  hipLaunchKernelGGL(k_sph_hydro, dim3(sph_wave_grid(nt, SPH_HWAVES)), dim3(64 * SPH_HWAVES), 0, c->stream, sph_tree_view(c), c->s_pm.p,
+                     c->s_type.p, c->sph_hsrc.p, c->sph_hmax.p, c->s_idx.p, c->sph_tlist.p, nt, (long long)c->n, hp, res, c->sph_row.p,
+                     c->sph_counters.p);
   HIP_TRY(c, hipGetLastError());
+  return NGRAVS_OK;
+}
+
+// the stack / candidates / pairs counters of a hydro walk or a sums walk, read back (waits for the stream)
+template <class Stats> static int sph_walk_counters(ngravs_ctx *c, Stats *st)
+{
+  unsigned long long h[SPH_C_COUNT];
+  if(int rc = sph_read_counters(c, h))
+    return rc;
+  st->stack_ovf = (long long)h[SPH_C_OVF];
+  st->candidates = (long long)h[SPH_C_CAND];
+  st->pairs = (long long)h[SPH_C_NGB];
+  return NGRAVS_OK;
+}
+
+// The engine's own gas as hydro sources: sph_hsrc from the caller's columns (sph_vel_in, sph_h_in, sph_col_in, sph_ts_in) by
+// k_sph_hydro_prep, and the counts of its bad rows in st.  The counters are clear when this is called; sph_hmax is allocated here
+// and filled by sph_hmax_levels once the caller knows the rows are good.
+static int sph_hydro_sources(ngravs_ctx *c, const SphHydroParams &hp, SphHydroStats *st)
+{
+  const long long n = c->n;
+  if(c->sph_hsrc.ensure((size_t)SPH_HS_NCOL * n) || c->sph_hmax.ensure((size_t)c->nnodes))
+    return NGRAVS_ERR_NOMEM;
+  hipLaunchKernelGGL(k_sph_hydro_prep, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->s_type.p, c->s_idx.p, n, c->sph_vel_in.p,
+                     c->sph_h_in.p, c->sph_col_in.p, c->sph_ts_in.p, hp, c->sph_hsrc.p, c->sph_counters.p);
+  HIP_TRY(c, hipGetLastError());
+  unsigned long long h[SPH_C_COUNT];
+  if(int rc = sph_read_counters(c, h))
+    return rc;
+  st->bad_hsml = (long long)h[SPH_H_BADH];
+  st->bad_density = (long long)h[SPH_H_BADRHO];
+  st->bad_pressure = (long long)h[SPH_H_BADP];
   return NGRAVS_OK;
 }
 
 int sph_hydro_run(ngravs_ctx *c, const SphHydroParams &hp, SphHydroStats *st)
 {
   memset(st, 0, sizeof(*st));
-  const long long n = c->n;
-  if(c->sph_hsrc.ensure((size_t)SPH_HS_NCOL * n) || c->sph_hmax.ensure((size_t)c->nnodes))
-    return NGRAVS_ERR_NOMEM;
   int cnt = 0;
   if(int rc = sph_targets(c, &cnt))   // (clears the counters)
     return rc;
@@ -1035,27 +1118,15 @@ int sph_hydro_run(ngravs_ctx *c, const SphHydroParams &hp, SphHydroStats *st)
   const long long nt = cnt;
   if(c->sph_res.ensure((size_t)SPH_HY_NRES * nt) || c->sph_row.ensure((size_t)nt))
     return NGRAVS_ERR_NOMEM;
-  hipLaunchKernelGGL(k_sph_hydro_prep, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->s_type.p, c->s_idx.p, n, c->sph_vel_in.p,
-                     c->sph_h_in.p, c->sph_col_in.p, c->sph_ts_in.p, hp, c->sph_hsrc.p, c->sph_counters.p);
-  HIP_TRY(c, hipGetLastError());
-  unsigned long long h[SPH_C_COUNT];
-  HIP_TRY(c, hipMemcpyAsync(h, c->sph_counters.p, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  st->bad_hsml = (long long)h[SPH_H_BADH];
-  st->bad_density = (long long)h[SPH_H_BADRHO];
-  st->bad_pressure = (long long)h[SPH_H_BADP];
+  if(int rc = sph_hydro_sources(c, hp, st))
+    return rc;
   if(st->bad_hsml || st->bad_density || st->bad_pressure)
     return NGRAVS_OK;   // the caller refuses; nothing is walked with such a column
   if(int rc = sph_hmax_levels(c))
     return rc;
   if(int rc = sph_hydro_walk(c, hp, nt, c->sph_res.p))
     return rc;
-  HIP_TRY(c, hipMemcpyAsync(h, c->sph_counters.p, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  st->stack_ovf = (long long)h[SPH_C_OVF];
-  st->candidates = (long long)h[SPH_C_CAND];
-  st->pairs = (long long)h[SPH_C_NGB];
-  return NGRAVS_OK;
+  return sph_walk_counters(c, st);
 }
 
 // ---- the gas side in one call (ngravs_sph_accelerations): density(), its pressure line, force_update_hmax(), hydro_force() ----
@@ -1098,8 +1169,8 @@ int sph_gas_run(ngravs_ctx *c, const SphGasParams &gp, const SphHydroParams &hp,
   if(int rc = sph_hydro_walk(c, hp, nt, c->sph_res.p + SPH_GAS_HYDRO * nt))
     return rc;
   unsigned long long h[SPH_C_COUNT];
-  HIP_TRY(c, hipMemcpyAsync(h, c->sph_counters.p, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if(int rc = sph_read_counters(c, h))
+    return rc;
   hs->bad_hsml = (long long)h[SPH_H_BADH];
   hs->bad_density = (long long)h[SPH_H_BADRHO];
   hs->bad_pressure = (long long)h[SPH_H_BADP];
@@ -1206,7 +1277,6 @@ __global__ __launch_bounds__(64 * SPH_WAVES) void k_sph_density_sums(TreeView tv
     return;
   double (*src)[SPH_STAGE] = s_src[w];
   int *stack = s_stack[w];
-  const double BIG = 1e300;
 
   const bool live = t < nt;
   SphLane L = {};
@@ -1223,20 +1293,10 @@ __global__ __launch_bounds__(64 * SPH_WAVES) void k_sph_density_sums(TreeView tv
       L.hinv3 = L.hinv * L.hinv * L.hinv;
       L.hinv4 = L.hinv3 * L.hinv;
     }
-  // the hull of the lanes' search boxes (ngb.c:206-210), as in k_sph_density
-  const double lx = wave_min(live ? L.x - h : BIG), ly = wave_min(live ? L.y - h : BIG), lz = wave_min(live ? L.z - h : BIG);
-  const double ux = wave_max(live ? L.x + h : -BIG), uy = wave_max(live ? L.y + h : -BIG), uz = wave_max(live ? L.z + h : -BIG);
-  const double hcx = wave_uniform(0.5 * (lx + ux)), hcy = wave_uniform(0.5 * (ly + uy)), hcz = wave_uniform(0.5 * (lz + uz));
-  const double hhx = wave_uniform(0.5 * (ux - lx) * (1 + 1e-12)), hhy = wave_uniform(0.5 * (uy - ly) * (1 + 1e-12)),
-               hhz = wave_uniform(0.5 * (uz - lz) * (1 + 1e-12));
+  const SphHull H = sph_wave_hull(L.x, L.y, L.z, h, live);   // of the lanes' search boxes, as in k_sph_density
   const bool ok = sph_hull_walk<SPH_STAGE>(
-    tv, pm, type, n, sp.periodic, sp.box, sp.boxhalf, hcx, hcy, hcz, hhx, hhy, hhz, stack, lane, [](int) { return 0.0; },
-    [&](int q, long long p) {
-      const double4 pp = pm[p];
-      src[0][q] = pp.x, src[1][q] = pp.y, src[2][q] = pp.z, src[3][q] = pp.w;
-      src[4][q] = svel[3 * p], src[5][q] = svel[3 * p + 1], src[6][q] = svel[3 * p + 2];
-    },
-    [&](int cnt) { sph_block(src, cnt, live, sp, L); });
+    tv, pm, type, n, sp.periodic, sp.box, sp.boxhalf, H, stack, lane, [](int) { return 0.0; },
+    [&](int q, long long p) { sph_stage_density(src, q, p, pm, svel); }, [&](int cnt) { sph_block(src, cnt, live, sp, L); });
   if(live && ok)
     {
       double *r = res + SPH_NSUMS * me;   // the caller's order; NOT passed through density.c:296-303
@@ -1248,49 +1308,24 @@ __global__ __launch_bounds__(64 * SPH_WAVES) void k_sph_density_sums(TreeView tv
       r[SPH_SUM_ROTY] = L.ry;
       r[SPH_SUM_ROTZ] = L.rz;
     }
-  unsigned long long cand = L.ncand, ngb = L.nngb;
-  for(int off = 32; off > 0; off >>= 1)
-    {
-      cand += __shfl_xor(cand, off);
-      ngb += __shfl_xor(ngb, off);
-    }
-  if(lane == 0)
-    {
-      atomicAdd(&counters[SPH_C_CAND], cand);
-      atomicAdd(&counters[SPH_C_NGB], ngb);
-      if(!ok)
-        atomicAdd(&counters[SPH_C_OVF], 1ull);
-    }
+  sph_wave_counters<false>(lane, L.ncand, L.nngb, 0, !ok, counters);
 }
 
+// targets: records of sph_tg_in in the order ord; results [nt][5] by the caller's index, dt_entropy WITHOUT hydra.c:320
 __global__ __launch_bounds__(64 * SPH_HWAVES) void k_sph_hydro_sums(TreeView tv, const double4 *__restrict__ pm, const unsigned char *__restrict__ type,
                                                                     const double *__restrict__ hs, const double *__restrict__ hmax, long long n,
                                                                     const double *__restrict__ tg, const int *__restrict__ tts,
                                                                     const unsigned int *__restrict__ ord, long long nt, SphHydroParams hp,
                                                                     double *__restrict__ res, unsigned long long *__restrict__ counters)
 {
-  __shared__ double s_src[SPH_HWAVES][SPH_HFIELDS][SPH_STAGE];
-  __shared__ int s_stack[SPH_HWAVES][SPH_STACK];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const long long t = ((long long)blockIdx.x * SPH_HWAVES + w) * 64 + lane;
-  if(t - lane >= nt)   // the whole wave (no workgroup barrier anywhere below)
-    return;
-  double (*src)[SPH_STAGE] = s_src[w];
-  int *stack = s_stack[w];
-  const double BIG = 1e300;
-  const double *sh = hs + SPH_HS_H * n;
-
-  const bool live = t < nt;
-  SphHydroLane L = {};
-  double h = 0;
-  long long me = 0;
-  if(live)
-    {
+  sph_hydro_wave(
+    tv, pm, type, hs, hmax, nt, n, hp, counters,
+    [&](long long t, SphHydroLane &L) {
       // hydrodata_in (hydra.c:145-162), and what hydro_evaluate derives from it (hydra.c:379, :403)
-      me = ord[t];
+      const long long me = ord[t];
       L.x = tg[3 * me], L.y = tg[3 * me + 1], L.z = tg[3 * me + 2];
       L.vx = tg[3 * nt + 3 * me], L.vy = tg[3 * nt + 3 * me + 1], L.vz = tg[3 * nt + 3 * me + 2];
-      h = tg[SPH_TG_H * nt + me];
+      const double h = tg[SPH_TG_H * nt + me];
       L.mass = tg[SPH_TG_MASS * nt + me];
       L.h2 = h * h;
       L.hinv = 1.0 / h;
@@ -1302,47 +1337,16 @@ __global__ __launch_bounds__(64 * SPH_HWAVES) void k_sph_hydro_sums(TreeView tv,
       L.cs = sqrt(hp.gamma * pressure / L.rho);
       L.f1 = tg[SPH_TG_F1 * nt + me];
       L.ts = tts ? (double)tts[me] : 0.0;
-    }
-  // the hull of the lanes' positions; a child is tested against it widened by max(largest h_i, hmax of the child) (ngb.c:146-177)
-  const double lx = wave_min(live ? L.x : BIG), ly = wave_min(live ? L.y : BIG), lz = wave_min(live ? L.z : BIG);
-  const double ux = wave_max(live ? L.x : -BIG), uy = wave_max(live ? L.y : -BIG), uz = wave_max(live ? L.z : -BIG);
-  const double hw = wave_uniform(wave_max(live ? h : 0.0));
-  const double hcx = wave_uniform(0.5 * (lx + ux)), hcy = wave_uniform(0.5 * (ly + uy)), hcz = wave_uniform(0.5 * (lz + uz));
-  const double hhx = wave_uniform(0.5 * (ux - lx) * (1 + 1e-12)), hhy = wave_uniform(0.5 * (uy - ly) * (1 + 1e-12)),
-               hhz = wave_uniform(0.5 * (uz - lz) * (1 + 1e-12));
-  const bool ok = sph_hull_walk<SPH_STAGE>(
-    tv, pm, type, n, hp.periodic, hp.box, hp.boxhalf, hcx, hcy, hcz, hhx, hhy, hhz, stack, lane,
-    [&](int ch) { return fmax(hw, ch >= 0 ? hmax[ch] : sh[-2 - ch]) * (1 + 1e-12); },
-    [&](int q, long long p) {
-      const double4 pp = pm[p];
-      src[0][q] = pp.x, src[1][q] = pp.y, src[2][q] = pp.z, src[3][q] = pp.w;
-      src[4][q] = hs[SPH_HS_VX * n + p], src[5][q] = hs[SPH_HS_VY * n + p], src[6][q] = hs[SPH_HS_VZ * n + p];
-      src[7][q] = hs[SPH_HS_H * n + p], src[8][q] = hs[SPH_HS_RHO * n + p], src[9][q] = hs[SPH_HS_POR2 * n + p];
-      src[10][q] = hs[SPH_HS_CSJ * n + p], src[11][q] = hs[SPH_HS_F2 * n + p], src[12][q] = hs[SPH_HS_TS * n + p];
+      return h;
     },
-    [&](int cnt) { sph_hydro_block(src, cnt, live, hp, L); });
-  if(live && ok)
-    {
-      double *r = res + SPH_HY_NRES * me;   // the caller's order; dt_entropy WITHOUT the final operation of hydra.c:320
+    [&](long long t, const SphHydroLane &L) {
+      double *r = res + SPH_HY_NRES * (long long)ord[t];
       r[SPH_HY_ACCX] = L.ax;
       r[SPH_HY_ACCY] = L.ay;
       r[SPH_HY_ACCZ] = L.az;
       r[SPH_HY_DTENTR] = L.dte;
       r[SPH_HY_MAXSIG] = L.maxsig;
-    }
-  unsigned long long cand = L.ncand, pairs = L.npair;
-  for(int off = 32; off > 0; off >>= 1)
-    {
-      cand += __shfl_xor(cand, off);
-      pairs += __shfl_xor(pairs, off);
-    }
-  if(lane == 0)
-    {
-      atomicAdd(&counters[SPH_C_CAND], cand);
-      atomicAdd(&counters[SPH_C_NGB], pairs);
-      if(!ok)
-        atomicAdd(&counters[SPH_C_OVF], 1ull);
-    }
+    });
 }
 
 // refuses bad targets (st says which), else leaves the caller's indices in Peano order in sph_tg_ord + nt
@@ -1355,8 +1359,8 @@ static int sph_targets_order(ngravs_ctx *c, long long nt, int hydro, SphSumsStat
                      c->cfg.box_size, c->dom[0], c->dom[1], c->dom[2], c->dom[6], clamped, c->sph_tg_ord.p, c->sph_counters.p);
   HIP_TRY(c, hipGetLastError());
   unsigned long long h[SPH_C_COUNT];
-  HIP_TRY(c, hipMemcpyAsync(h, c->sph_counters.p, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if(int rc = sph_read_counters(c, h))
+    return rc;
   st->bad_hsml = (long long)h[SPH_H_BADH];
   st->bad_density = (long long)h[SPH_H_BADRHO];
   st->bad_pressure = (long long)h[SPH_H_BADP];
@@ -1377,17 +1381,6 @@ static int sph_targets_order(ngravs_ctx *c, long long nt, int hydro, SphSumsStat
   return NGRAVS_OK;
 }
 
-static int sph_sums_counters(ngravs_ctx *c, SphSumsStats *st)
-{
-  unsigned long long h[SPH_C_COUNT];
-  HIP_TRY(c, hipMemcpyAsync(h, c->sph_counters.p, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  st->stack_ovf = (long long)h[SPH_C_OVF];
-  st->candidates = (long long)h[SPH_C_CAND];
-  st->pairs = (long long)h[SPH_C_NGB];
-  return NGRAVS_OK;
-}
-
 int sph_density_sums_run(ngravs_ctx *c, long long nt, SphSumsStats *st)
 {
   memset(st, 0, sizeof(*st));
@@ -1400,36 +1393,24 @@ int sph_density_sums_run(ngravs_ctx *c, long long nt, SphSumsStats *st)
   if(!good)
     return NGRAVS_OK;
   SphParams sp = {};
-  sp.periodic = c->cfg.periodic;
-  sp.box = c->cfg.box_size;
-  sp.boxhalf = 0.5 * c->cfg.box_size;
-  const long long nwaves = (nt + 63) / 64;
-  const unsigned nb = (unsigned)((nwaves + SPH_WAVES - 1) / SPH_WAVES);
-  hipLaunchKernelGGL(k_sph_density_sums, dim3(nb), dim3(64 * SPH_WAVES), 0, c->stream, sph_tree_view(c), c->s_pm.p, c->s_type.p, c->sph_vel.p,
-                     (long long)c->n, c->sph_tg_in.p, c->sph_tg_ord.p + nt, nt, sp, c->sph_tg_res.p, c->sph_counters.p);
+  sph_set_box(c, &sp);
+  hipLaunchKernelGGL(k_sph_density_sums, dim3(sph_wave_grid(nt, SPH_WAVES)), dim3(64 * SPH_WAVES), 0, c->stream, sph_tree_view(c), c->s_pm.p,
+                     c->s_type.p, c->sph_vel.p, (long long)c->n, c->sph_tg_in.p, c->sph_tg_ord.p + nt, nt, sp, c->sph_tg_res.p, c->sph_counters.p);
   HIP_TRY(c, hipGetLastError());
-  return sph_sums_counters(c, st);
+  return sph_walk_counters(c, st);
 }
 
 int sph_hydro_sums_run(ngravs_ctx *c, const SphHydroParams &hp, long long nt, int have_tts, SphSumsStats *st, SphHydroStats *own)
 {
   memset(st, 0, sizeof(*st));
   memset(own, 0, sizeof(*own));
-  const long long n = c->n;
   if(c->sph_counters.ensure(SPH_C_COUNT + 1) || c->sph_tg_key.ensure(2 * (size_t)nt) || c->sph_tg_ord.ensure(2 * (size_t)nt) ||
-     c->sph_tg_res.ensure((size_t)SPH_HY_NRES * nt) || c->sph_hsrc.ensure((size_t)SPH_HS_NCOL * n) || c->sph_hmax.ensure((size_t)c->nnodes))
+     c->sph_tg_res.ensure((size_t)SPH_HY_NRES * nt))
     return NGRAVS_ERR_NOMEM;
-  // the engine's own gas: sph_hsrc and the nodes' hmax, as sph_hydro_run prepares them
+  // the engine's own gas first, as sph_hydro_run prepares it
   HIP_TRY(c, hipMemsetAsync(c->sph_counters.p, 0, (SPH_C_COUNT + 1) * sizeof(unsigned long long), c->stream));
-  hipLaunchKernelGGL(k_sph_hydro_prep, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->s_type.p, c->s_idx.p, n, c->sph_vel_in.p,
-                     c->sph_h_in.p, c->sph_col_in.p, c->sph_ts_in.p, hp, c->sph_hsrc.p, c->sph_counters.p);
-  HIP_TRY(c, hipGetLastError());
-  unsigned long long h[SPH_C_COUNT];
-  HIP_TRY(c, hipMemcpyAsync(h, c->sph_counters.p, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  own->bad_hsml = (long long)h[SPH_H_BADH];
-  own->bad_density = (long long)h[SPH_H_BADRHO];
-  own->bad_pressure = (long long)h[SPH_H_BADP];
+  if(int rc = sph_hydro_sources(c, hp, own))
+    return rc;
   if(own->bad_hsml || own->bad_density || own->bad_pressure)
     return NGRAVS_OK;   // the caller refuses; nothing is walked with such a column
   bool good;
@@ -1439,12 +1420,11 @@ int sph_hydro_sums_run(ngravs_ctx *c, const SphHydroParams &hp, long long nt, in
     return NGRAVS_OK;
   if(int rc = sph_hmax_levels(c))
     return rc;
-  const long long nwaves = (nt + 63) / 64;
-  const unsigned nb = (unsigned)((nwaves + SPH_HWAVES - 1) / SPH_HWAVES);
-  hipLaunchKernelGGL(k_sph_hydro_sums, dim3(nb), dim3(64 * SPH_HWAVES), 0, c->stream, sph_tree_view(c), c->s_pm.p, c->s_type.p, c->sph_hsrc.p,
-                     c->sph_hmax.p, n, c->sph_tg_in.p, have_tts ? c->sph_tg_ts.p : nullptr, c->sph_tg_ord.p + nt, nt, hp, c->sph_tg_res.p, c->sph_counters.p);
+  hipLaunchKernelGGL(k_sph_hydro_sums, dim3(sph_wave_grid(nt, SPH_HWAVES)), dim3(64 * SPH_HWAVES), 0, c->stream, sph_tree_view(c), c->s_pm.p,
+                     c->s_type.p, c->sph_hsrc.p, c->sph_hmax.p, (long long)c->n, c->sph_tg_in.p, have_tts ? c->sph_tg_ts.p : nullptr,
+                     c->sph_tg_ord.p + nt, nt, hp, c->sph_tg_res.p, c->sph_counters.p);
   HIP_TRY(c, hipGetLastError());
-  return sph_sums_counters(c, st);
+  return sph_walk_counters(c, st);
 }
 
 __global__ void k_sph_density_update(long long n, const double *__restrict__ sums, double *__restrict__ h, double *__restrict__ left,
