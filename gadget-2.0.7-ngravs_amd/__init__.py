@@ -30,7 +30,7 @@ EXPORTS = [
     "ngravs_set_fatal_handler", "ngravs_set_opening", "ngravs_set_walk_mode", "ngravs_set_softening", "ngravs_dd_record_bytes", "ngravs_get_config", "ngravs_set_tuning",
     "ngravs_memcpy", "ngravs_device_alloc", "ngravs_device_free",
     "ngravs_set_particles",
-    "ngravs_set_old_acc", "ngravs_update_particles", "ngravs_force_update_tree", "ngravs_domain_decomposition", "ngravs_discard_grav_pm",
+    "ngravs_set_old_acc", "ngravs_set_gas_softening", "ngravs_update_particles", "ngravs_force_update_tree", "ngravs_domain_decomposition", "ngravs_discard_grav_pm",
     "ngravs_force_treebuild", "ngravs_gravity_tree",
     "ngravs_pmforce_periodic", "ngravs_compute_accelerations", "ngravs_get_accel", "ngravs_get_stats", "ngravs_walk_unopened",
     "ngravs_get_domain", "ngravs_get_keys", "ngravs_get_order", "ngravs_get_shard", "ngravs_last_error",
@@ -92,6 +92,7 @@ def lib():
         L.ngravs_dd_record_bytes.argtypes = [C.c_void_p, C.c_int]
         L.ngravs_set_particles.argtypes = [C.c_void_p, C.c_void_p]
         L.ngravs_set_old_acc.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int]
+        L.ngravs_set_gas_softening.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int]
         L.ngravs_get_accel.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                        C.c_void_p, C.c_int64, C.c_int, C.c_int]
         L.ngravs_set_tuning.argtypes = [C.c_void_p, C.c_char_p, C.c_double]
@@ -439,6 +440,23 @@ class Engine:
     def set_old_acc_device(self, ptr):
         """OldAcc from a HIP device pointer (N contiguous doubles, caller order)"""
         self._check(lib().ngravs_set_old_acc(self._h, ptr, 8, 1), "ngravs_set_old_acc")
+
+    def set_gas_softening(self, hsml):
+        """adaptive gravitational softening for gas (ADAPTIVE_GRAVSOFT_FORGAS): one length per own row, caller order; rows that
+        are not type 0 are never read.  hsml: a numpy array, a device tensor (float64, contiguous), or None to switch back to the
+        lengths per type"""
+        if hsml is None:
+            rc = lib().ngravs_set_gas_softening(self._h, None, 0, 0)
+        elif hasattr(hsml, "data_ptr"):
+            if str(hsml.dtype) != "torch.float64" or not hsml.is_contiguous() or hsml.numel() != self.n:
+                raise ValueError("set_gas_softening: a device tensor must hold n contiguous float64 values")
+            rc = lib().ngravs_set_gas_softening(self._h, hsml.data_ptr(), 8, 1 if hsml.is_cuda else 0)
+        else:
+            hsml = np.ascontiguousarray(hsml, dtype=np.float64)
+            if hsml.shape != (self.n,):
+                raise ValueError("set_gas_softening: one value per particle")
+            rc = lib().ngravs_set_gas_softening(self._h, hsml.ctypes.data, 8, 0)
+        self._check(rc, "ngravs_set_gas_softening")
 
     def get_old_acc_device(self, ptr):
         """write OldAcc (caller order) to a HIP device pointer"""

@@ -21,7 +21,7 @@ LAW_USER0 = 64
 SPLINE_USER0 = 64
 MAX_USER_FNS = 8
 USER_ACCEL, USER_SPLINE, USER_GREENS, USER_NORMED = range(4)
-KERNEL_NONE, KERNEL_STRICT, KERNEL_STRICT_USER, KERNEL_GROUP, KERNEL_GROUP_USER = range(5)
+KERNEL_NONE, KERNEL_STRICT, KERNEL_STRICT_USER, KERNEL_GROUP, KERNEL_GROUP_USER, KERNEL_STRICT_ADAPTIVE, KERNEL_GROUP_ADAPTIVE = range(7)
 # the reference's `gravity` type (allvars.h:134): double f(double target, double source, double r2_or_h_or_k2, double r_or_k, long N)
 GravityFn = C.CFUNCTYPE(C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_long)
 

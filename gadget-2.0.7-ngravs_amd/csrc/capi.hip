@@ -348,6 +348,10 @@ extern "C" void ngravs_destroy(ngravs_ctx *c)
   c->in_pos.release();
   c->in_mass.release();
   c->in_oldacc.release();
+  c->in_gsoft.release();
+  c->gsoft_stage.release();
+  c->s_soft.release();
+  c->n_maxsoft.release();
   c->in_type.release();
   c->in_active.release();
   c->in_key.release();
@@ -485,6 +489,7 @@ extern "C" int ngravs_set_softening(ngravs_ctx *c, const double force_softening[
       }
   for(int t = 0; t < NGRAVS_NTYPES; t++)
     c->cfg.force_softening[t] = force_softening[t];
+  c->gsoft_col_stale = c->gsoft_node_stale = true;   // adaptive softening: the other types' lengths enter both columns
   return NGRAVS_OK;
 }
 
@@ -649,6 +654,7 @@ static int set_particles_impl(ngravs_ctx *c, const ngravs_particles_t *p, bool k
       c->walk_unit_state = 4;
       c->have_particles = true;
       c->have_order = c->have_tree = c->have_pm = c->have_acc = false;
+      c->gsoft_on = false;
       c->top.on = false;
       c->pm_parked = false;
       return NGRAVS_OK;
@@ -781,6 +787,7 @@ static int set_particles_impl(ngravs_ctx *c, const ngravs_particles_t *p, bool k
   else
     {
       c->have_order = c->have_tree = c->have_pm = c->have_acc = false;   // new P[]: nothing carries over ...
+      c->gsoft_on = false;     // ... a new set has no gas softening lengths
       c->top.on = false;   // (the top tree itself is kept: it is the first guess of the next decomposition)
       c->pm_parked = false;
       if(p->grav_pm && c->cfg.pmgrid)
@@ -824,6 +831,7 @@ extern "C" int ngravs_force_update_tree(ngravs_ctx *c)
   c->stats.t_domain = c->stats.t_peano = 0;
   c->tree_stale = false;
   c->tree_refit = true;
+  c->gsoft_node_stale = true;
   return NGRAVS_OK;
 }
 
@@ -842,6 +850,81 @@ extern "C" int ngravs_set_old_acc(ngravs_ctx *c, const double *old_acc, int64_t 
   if(c->have_order)
     hipLaunchKernelGGL(k_permute_f64, GRID1(c->n), 0, c->stream, c->s_idx.p, (long long)c->n, 1, c->in_oldacc.p, c->s_oldacc.p);
   HIP_TRY(c, hipGetLastError());
+  return NGRAVS_OK;
+}
+
+// type-0 rows whose length is negative or not finite are counted; rows of other types are not read and staged as 0
+__global__ void k_gsoft_stage(const unsigned char *__restrict__ src, long long stride, int strided_src, const int *__restrict__ type,
+                              long long n, double *__restrict__ dst, int *__restrict__ nbad)
+{
+  const long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+  if(i >= n)
+    return;
+  double h = 0.0;
+  if(type[i] == 0)
+    {
+      h = strided_src ? *reinterpret_cast<const double *>(src + i * stride) : dst[i];
+      if(!(h >= 0.0) || isinf(h))
+        atomicAdd(nbad, 1);
+    }
+  dst[i] = h;
+}
+
+// ADAPTIVE_GRAVSOFT_FORGAS (forcetree.c:1398-1413): the caller-order copy of the gas lengths; the sorted column and the node
+// column are derived from it when a walk or a direct sum needs them (adaptive_refresh)
+extern "C" int ngravs_set_gas_softening(ngravs_ctx *c, const double *hsml, int64_t stride, int on_device)
+{
+  if(!c)
+    return NGRAVS_ERR_ARG;
+  if(!hsml)
+    {
+      c->gsoft_on = false;
+      return NGRAVS_OK;
+    }
+  if(!c->have_particles || c->n_local <= 0)
+    {
+      ngravs_report(c, NGRAVS_ERR_ARG, "ngravs_set_gas_softening: no particles handed over yet");
+      return NGRAVS_ERR_ARG;
+    }
+  if(c->cfg.world_size > 1 || c->n_local != c->n || c->top.on)
+    {
+      ngravs_report(c, NGRAVS_ERR_STATE, "ngravs_set_gas_softening: single task only (imported copies and top-leaf sums carry no "
+                                         "softening length)");
+      return NGRAVS_ERR_STATE;
+    }
+  if(cfg_has_user(c->cfg))
+    {
+      ngravs_report(c, NGRAVS_ERR_ARG, "ngravs_set_gas_softening: not with user-defined laws (their spline tables are sampled per "
+                                       "softening length)");
+      return NGRAVS_ERR_ARG;
+    }
+  (void)hipSetDevice(c->cfg.device);
+  const int64_t n = c->n_local;
+  DevBuf<double> &stage = c->gsoft_stage;   // checked here, swapped in when the call succeeds: a refused call changes nothing
+  if(stage.ensure(n) || c->d_counters.ensure(16))
+    return NGRAVS_ERR_NOMEM;
+  // host columns are packed on the host (only type-0 rows would have to be read, but the packed copy is checked on the device
+  // against the types there); device columns are read in place, type-0 rows only
+  int nbad = 0, rc = NGRAVS_OK;
+  if(!on_device && (rc = upload_column_f64(c, hsml, stride, 1, n, 0, stage.p)))
+    return rc;
+  if(hipMemsetAsync(c->d_counters.p + 15, 0, sizeof(int), c->stream) != hipSuccess)
+    rc = NGRAVS_ERR_NO_DEVICE;
+  hipLaunchKernelGGL(k_gsoft_stage, GRID1(n), 0, c->stream, (const unsigned char *)hsml, (long long)stride, on_device ? 1 : 0, c->in_type.p,
+                     (long long)n, stage.p, c->d_counters.p + 15);
+  if(!rc && (hipMemcpyAsync(&nbad, c->d_counters.p + 15, sizeof(int), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+             hipStreamSynchronize(c->stream) != hipSuccess || hipGetLastError() != hipSuccess))
+    rc = NGRAVS_ERR_NO_DEVICE;
+  if(!rc && nbad)
+    {
+      ngravs_report(c, NGRAVS_ERR_ARG, "ngravs_set_gas_softening: " + std::to_string(nbad) + " type-0 rows with a negative or non-finite length");
+      rc = NGRAVS_ERR_ARG;
+    }
+  if(rc)
+    return rc;
+  std::swap(c->in_gsoft, c->gsoft_stage);
+  c->gsoft_on = true;
+  c->gsoft_col_stale = c->gsoft_node_stale = true;
   return NGRAVS_OK;
 }
 
@@ -922,6 +1005,7 @@ static int domain_decomposition_impl(ngravs_ctx *c, bool keep_pm)
   c->shard_count = hi - lo;
   c->have_order = true;
   c->have_tree = false;   // TreeReconstructFlag = 1 (domain.c:84)
+  c->gsoft_col_stale = c->gsoft_node_stale = true;
   c->tree_stale = false;
   if(c->have_pm)
     {
@@ -970,6 +1054,7 @@ extern "C" int64_t ngravs_force_treebuild(ngravs_ctx *c)
   c->stats.t_treebuild = ev_ms(c) * 1e-3;
   c->have_tree = true;
   c->tree_refit = false;
+  c->gsoft_node_stale = true;
   return c->nnodes;
 }
 
@@ -1665,6 +1750,12 @@ extern "C" int ngravs_direct_sum_targets(ngravs_ctx *c, const double *pos, const
   for(int64_t k = 0; k < nt; k++)
     if(type[k] < 0 || type[k] >= NGRAVS_NTYPES)
       return NGRAVS_ERR_ARG;
+  if(c->gsoft_on)
+    {
+      ngravs_report(c, NGRAVS_ERR_STATE, "ngravs_direct_sum_targets: adaptive gas softening is on and explicit targets carry no "
+                                         "softening length (ngravs_set_gas_softening(ctx, NULL, 0, 0) switches it off)");
+      return NGRAVS_ERR_STATE;
+    }
   (void)hipSetDevice(c->cfg.device);
   DevBuf<double4> dt;
   DevBuf<int> dty;

@@ -174,6 +174,9 @@ struct TreeView
   const int *ltab;
   int ltab_level;          // 0: none, walks start at the root
   double ltab_corner[3], ltab_cl;
+  // adaptive softening for gas (ngravs_set_gas_softening; read by the ADA instantiations alone, null otherwise)
+  const double *soft;      // per sorted particle: Hsml of a type-0 row, fsoft[type] of any other
+  const double *maxsoft;   // per node: the largest of them below it (0: empty node)
 };
 
 // ngravs_set_tuning(): performance / test parameters, set explicitly by the host (no environment variables)
@@ -354,6 +357,14 @@ struct ngravs_ctx
   bool user_ready = false;
   double user_soft[NGRAVS_NTYPES] = {0, 0, 0, 0, 0, 0};   // the softenings the tables were built for
   int last_walk_kernel = 0;   // NGRAVS_KERNEL_*
+  // adaptive softening for gas (ngravs_set_gas_softening): the caller's lengths, own rows in caller order; what the walks read
+  // is derived from them on demand (adaptive_refresh)
+  bool gsoft_on = false;
+  bool gsoft_col_stale = true, gsoft_node_stale = true;
+  DevBuf<double> in_gsoft;    // [n_local] caller order; rows of other types hold 0
+  DevBuf<double> gsoft_stage; // the next column while ngravs_set_gas_softening checks it
+  DevBuf<double> s_soft;      // TreeView::soft
+  DevBuf<double> n_maxsoft;   // TreeView::maxsoft
   // PM beside the walk (ngravs_compute_accelerations): two streams masked to disjoint sets of CUs
   hipStream_t pm_stream = nullptr, walk_stream = nullptr;
   int pm_stream_cus = 0;      // CUs of pm_stream's mask (0: no masked streams); walk_stream has the device's other CUs
@@ -480,6 +491,9 @@ int walk_complete(ngravs_ctx *c);
 int walk_finish(ngravs_ctx *c);
 int direct_run(ngravs_ctx *c, const int *d_idx, int64_t nt, double *d_acc);
 int direct_run_targets(ngravs_ctx *c, const double4 *d_tpm, const int *d_ttype, int64_t nt, double *d_acc, double r_need = 0);
+// adaptive softening: s_soft from in_gsoft and the order, n_maxsoft bottom-up from the tree (nodes: also the node column), each
+// only when stale
+int adaptive_refresh(ngravs_ctx *c, bool nodes);
 // ---- kernels_eval.hip
 int eval_ring_slots(const WalkParams &wp, bool yuk, int waves);
 int launch_eval_ring(ngravs_ctx *c, const TreeView &tv, const WalkParams &wp, bool yuk, int nblk, int waves, int K, const int *region,

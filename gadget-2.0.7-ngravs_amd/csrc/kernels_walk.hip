@@ -247,7 +247,8 @@ __device__ __forceinline__ void lat_lookup(const double *__restrict__ t3, double
 // =============================================================================================
 #pragma clang fp contract(off)
 
-template <int NG, bool PM, bool LATT, bool USER = false>   // USER: tree-only wirings with a user-defined law
+// ADA: adaptive softening for gas (forcetree.c:1398-1413, :1503-1516 / :1745-1760, :1928-1941): tv.soft, tv.maxsoft
+template <int NG, bool PM, bool LATT, bool USER = false, bool ADA = false>   // USER: tree-only wirings with a user-defined law
 __global__ __launch_bounds__(256) void k_walk_strict(TreeView tv, const double4 *__restrict__ s_pm,
                                                      const unsigned char *__restrict__ s_type,
                                                      const double *__restrict__ s_oldacc,
@@ -275,6 +276,8 @@ __global__ __launch_bounds__(256) void k_walk_strict(TreeView tv, const double4 
       ptype = s_type[ti];
       tg = wp.t2g[ptype];
       hT = wp.fsoft[ptype];
+      if constexpr(ADA)
+        hT = tv.soft[ti];
       aold = wp.errtol_acc * s_oldacc[ti];
     }
   double ax = 0, ay = 0, az = 0;
@@ -340,7 +343,13 @@ __global__ __launch_bounds__(256) void k_walk_strict(TreeView tv, const double4 
           }
         double r2 = dx * dx + dy * dy + dz * dz;
         double h = hT;
-        if(h < wp.fsoft[qt])
+        if constexpr(ADA)
+          {
+            const double hq = tv.soft[p];   // uniform address: the source's own length (its Hsml, or its type's)
+            if(h < hq)
+              h = hq;
+          }
+        else if(h < wp.fsoft[qt])
           h = wp.fsoft[qt];
         bool added = interact(sg, dx, dy, dz, r2, q.w, h);
         if(added || !PM)
@@ -420,7 +429,17 @@ __global__ __launch_bounds__(256) void k_walk_strict(TreeView tv, const double4 
               open = true;                                             // empty node: nothing below, harmless
             else
               {
-                if(h < wp.fsoft[mst])
+                if constexpr(ADA)
+                  {
+                    const double hn = tv.maxsoft[c];
+                    if(h < hn)
+                      {
+                        h = hn;
+                        if(r2max < h * h)                              // forcetree.c:1503-1516, :1928-1941: no mixed-softening bit
+                          open = true;
+                      }
+                  }
+                else if(h < wp.fsoft[mst])
                   {
                     h = wp.fsoft[mst];
                     if(r2max < h * h && ((fl >> 5) & 1))               // forcetree.c:1488-1499
@@ -609,6 +628,9 @@ __global__ __launch_bounds__(256) void k_walk_strict(TreeView tv, const double4 
 // the group's box centre and its square for the packed-fp32 reach pre-test, 1 byte = softening type)
 // per wave: [NULL entry (double4)] [128 x double4 position/mass] [4 x 128 floats] [128 type bytes] -- 16-byte multiple
 #define GW2_WAVE_LDS (sizeof(double4) + (sizeof(double4) + 4 * sizeof(float) + 1) * 128)
+// adaptive softening (ADA): behind it one fp64 softening length per pool entry
+#define GW2_WAVE_LDS_ADA (GW2_WAVE_LDS + sizeof(double) * 128)
+static_assert(GW2_WAVE_LDS % 8 == 0 && GW2_WAVE_LDS_ADA % 16 == 0, "the per-entry lengths are doubles; every wave's pool starts 16-byte aligned");
 #define GW_NLEAF 8          // an opened node with <= NLEAF particles hands over its particles directly
 static_assert(GW_NLEAF <= FLAG_SPECIES_SLOTS, "a node handed over as a leaf must be range-coded (k_moments)");
 
@@ -640,7 +662,9 @@ static_assert(GW_NLEAF <= FLAG_SPECIES_SLOTS, "a node handed over as a leaf must
 
 // USR: wirings with a user-defined law in TreePM (PM) and periodic tree-only (LATT) runs (their own instantiations; the ring
 // kernel never sees them)
-template <int NG, bool PM, bool YUK, bool TAB_LDS, bool LATT, int MODE, bool USR = false>
+// ADA: adaptive softening for gas (ngravs_set_gas_softening): targets and sources carry their own length (tv.soft), a monopole
+// its node's largest (tv.maxsoft), and the traversal opens by the reference's maxsoft rule (forcetree.c:1503-1516, :1928-1941)
+template <int NG, bool PM, bool YUK, bool TAB_LDS, bool LATT, int MODE, bool USR = false, bool ADA = false>
 __global__ __launch_bounds__(MODE == 1 ? GW3_TBLOCK : (MODE == 2 ? GW2_MAXWAVES : GW_MAXWAVES) * 64) void k_walk_group2(
     TreeView tv, const double4 *__restrict__ s_pm, const unsigned char *__restrict__ s_type,
     const double *__restrict__ s_oldacc, const unsigned char *__restrict__ s_active,
@@ -663,12 +687,13 @@ __global__ __launch_bounds__(MODE == 1 ? GW3_TBLOCK : (MODE == 2 ? GW2_MAXWAVES 
   const size_t tab_bytes = (PM && TAB_LDS) ? sizeof(double) * ntabs * NTAB : 0;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   double *expT = reinterpret_cast<double *>(smem + tab_bytes);
-  unsigned char *wbase = smem + tab_bytes + 40 * sizeof(double) + (size_t)wave * GW2_WAVE_LDS;
+  unsigned char *wbase = smem + tab_bytes + 40 * sizeof(double) + (size_t)wave * (ADA ? GW2_WAVE_LDS_ADA : GW2_WAVE_LDS);
   double *fsT = expT + 32;   // softening length per particle type (8 entries; index 7 = empty node)
   double4 *lpos = reinterpret_cast<double4 *>(wbase) + 1;   // lpos[-1]: the NULL entry
   float *lfx = reinterpret_cast<float *>(wbase + sizeof(double4) * (2 * WAVE + 1));
   float *lfy = lfx + 2 * WAVE, *lfz = lfx + 4 * WAVE, *le2 = lfx + 6 * WAVE;
   unsigned char *lty = wbase + sizeof(double4) + (sizeof(double4) + 4 * sizeof(float)) * 2 * WAVE;
+  double *lhs = reinterpret_cast<double *>(wbase + GW2_WAVE_LDS);   // ADA: softening length per pool entry (not there otherwise)
   if(MODE != 1)
     {
       if(threadIdx.x < 32)
@@ -693,6 +718,8 @@ __global__ __launch_bounds__(MODE == 1 ? GW3_TBLOCK : (MODE == 2 ? GW2_MAXWAVES 
       lpos[127] = z;
       lpos[-1] = z;   // a lane whose mask is exhausted computes index -1 (v_ffbl_b32 of 0), see the force loop
       lty[127] = 7;   // fsT[7] = 0: unsoftened
+      if constexpr(ADA)
+        lhs[127] = 0.0;
       lfx[127] = lfy[127] = lfz[127] = 1e10f;
       le2[127] = 3e20f;
     }
@@ -737,6 +764,13 @@ __global__ __launch_bounds__(MODE == 1 ? GW3_TBLOCK : (MODE == 2 ? GW2_MAXWAVES 
     {
       h2max = fmax(h2max, wp.fsoft[q] * wp.fsoft[q]);
       usoft = usoft && wp.fsoft[q] == wp.fsoft[0];
+    }
+  if constexpr(ADA)
+    {
+      // the root's maxsoft bounds every length of the set, the gas lengths too (uniform address: a scalar load)
+      const double hr = tv.maxsoft[0];
+      h2max = hr * hr;
+      usoft = false;
     }
 
   // XCD-aware group assignment: the Peano order is cut into 8 contiguous segments, one per XCD (own L2), and a
@@ -819,6 +853,8 @@ __global__ __launch_bounds__(MODE == 1 ? GW3_TBLOCK : (MODE == 2 ? GW2_MAXWAVES 
           int ptype = s_type[ti];
           tg = wp.t2g[ptype];
           hT = wp.fsoft[ptype];
+          if constexpr(ADA)
+            hT = tv.soft[ti];
           aold = wp.errtol_acc * s_oldacc[ti];
         }
       // per-lane extremes over the targets this lane stands for (one; the traversal of a unit: one per group of the unit)
@@ -842,7 +878,10 @@ __global__ __launch_bounds__(MODE == 1 ? GW3_TBLOCK : (MODE == 2 ? GW2_MAXWAVES 
                 mnz = fmin(mnz, p.z);
                 mxz = fmax(mxz, p.z);
                 mna = fmin(mna, wp.errtol_acc * s_oldacc[tij]);
-                mnh = fmin(mnh, wp.fsoft[ptype]);
+                if constexpr(ADA)
+                  mnh = fmin(mnh, tv.soft[tij]);
+                else
+                  mnh = fmin(mnh, wp.fsoft[ptype]);
                 anyvalid = true;
               }
           }
@@ -956,6 +995,13 @@ __global__ __launch_bounds__(MODE == 1 ? GW3_TBLOCK : (MODE == 2 ? GW2_MAXWAVES 
           asm volatile("" : "+s"(am));
           return ((am >> lane) & 1ull) != 0;
         };
+        // softening length of pool entry je: its type's through the LDS table, or (ADA) its own
+        auto pool_h = [&](int je) -> double {
+          if constexpr(ADA)
+            return lhs[je];
+          else
+            return fsT[lty[je]];
+        };
         constexpr bool LW = decltype(lw_tag)::value;
         constexpr bool ET = decltype(et_tag)::value;   // Yukawa factor through the table bins (wp.exp_tab, hoisted by the caller)
         double dx[ES], dy[ES], dz[ES], r2[ES], rinv[ES], r[ES], fac[ES], mw[ES];
@@ -1041,7 +1087,7 @@ __global__ __launch_bounds__(MODE == 1 ? GW3_TBLOCK : (MODE == 2 ? GW2_MAXWAVES 
 #pragma unroll
             for(int k = 0; k < ES; k++)
               {
-                const double h = __builtin_fmax(hT, fsT[lty[is_act(k) ? jj[k] : 127]]);     // the pair's softening (forcetree.c:1415-1417)
+                const double h = __builtin_fmax(hT, pool_h(is_act(k) ? jj[k] : 127));     // the pair's softening (forcetree.c:1415-1417)
                 const bool soft = r[k] < h;
                 double h_inv = 1 / h, u = r[k] * h_inv;
                 double v = (u < 0.5) ? (10.666666666667 + u * u * (32.0 * u - 38.4))
@@ -1059,7 +1105,7 @@ __global__ __launch_bounds__(MODE == 1 ? GW3_TBLOCK : (MODE == 2 ? GW2_MAXWAVES 
                 {
                   // forcetree.c:1534-1583 with AccelFxns / AccelSplines of the BAM family: f(target mass, source mass, r, N)
                   const int je = is_act(k) ? jj[k] : 127;
-                  const double h = __builtin_fmax(hT, fsT[lty[je]]);
+                  const double h = __builtin_fmax(hT, pool_h(je));
                   const double Nn = (double)__float_as_int(le2[je]);
                   double f = 0.0;
                   if(mw[k] != 0.0)   // (the NULL entry: no mass, and its slot holds no particle number)
@@ -1076,7 +1122,7 @@ __global__ __launch_bounds__(MODE == 1 ? GW3_TBLOCK : (MODE == 2 ? GW2_MAXWAVES 
                 // forcetree.c:1953-1974 through the wired ids: (accel(r) - m utor2wpi T[tab]) / r, the spline inside the softening
                 // (slots beyond the exact cut and the NULL entry carry mass 0)
                 const int je = is_act(k) ? jj[k] : 127;
-                const double h = __builtin_fmax(hT, fsT[lty[je]]);
+                const double h = __builtin_fmax(hT, pool_h(je));
                 double f = 0.0;
                 if(mw[k] != 0.0)
                   {
@@ -1096,7 +1142,7 @@ __global__ __launch_bounds__(MODE == 1 ? GW3_TBLOCK : (MODE == 2 ? GW2_MAXWAVES 
                 // periodic tree-only wirings with a user-defined law (LATT): forcetree.c:1534-1583 through the wired ids, the
                 // nearest image here and the lattice correction below (the NULL entry carries mass 0)
                 const int je = is_act(k) ? jj[k] : 127;
-                const double h = __builtin_fmax(hT, fsT[lty[je]]);
+                const double h = __builtin_fmax(hT, pool_h(je));
                 double f = 0.0;
                 if(mw[k] != 0.0)
                   f = r[k] >= h ? law_accel_any(lawA, mw[k], r2[k], r[k], wp, 1.0, 1.0) * rinv[k]
@@ -1295,7 +1341,7 @@ __global__ __launch_bounds__(MODE == 1 ? GW3_TBLOCK : (MODE == 2 ? GW2_MAXWAVES 
           slot += step64;
           slot = slot >= M ? slot - M : slot;
         };
-        auto fetch_rec = [&](bool hv, int item, double4 &q, int &hs) {   // hs: softening TYPE of the source (fsT index)
+        auto fetch_rec = [&](bool hv, int item, double4 &q, int &hs, double &hd) {   // hs: softening TYPE of the source (fsT index); hd (ADA): its length
           // (without a record q and hs keep their previous contents: the consumer tests `have` first)
           if(hv)
             {
@@ -1325,6 +1371,8 @@ __global__ __launch_bounds__(MODE == 1 ? GW3_TBLOCK : (MODE == 2 ? GW2_MAXWAVES 
                   else
                     ty = (tv.flags[k / NG] >> 2) & 7;
                   hs = ty | nsrc;
+                  if constexpr(ADA)
+                    hd = isp ? tv.soft[item] : tv.maxsoft[k / NG];
                 }
             }
         };
@@ -1334,8 +1382,9 @@ __global__ __launch_bounds__(MODE == 1 ? GW3_TBLOCK : (MODE == 2 ? GW2_MAXWAVES 
         double4 q1;
         q1.x = q1.y = q1.z = q1.w = 0;
         int hs1 = 0;
+        double hd1 = 0;
         bool have1 = nv > 0;
-        fetch_rec(have1, qd.x, q1, hs1);
+        fetch_rec(have1, qd.x, q1, hs1, hd1);
         double4 *pp = lpos;
         unsigned char *ph = lty;
         for(int cc = 0; cc <= nchunks; cc++)
@@ -1345,6 +1394,7 @@ __global__ __launch_bounds__(MODE == 1 ? GW3_TBLOCK : (MODE == 2 ? GW2_MAXWAVES 
             // the same registers -- no copies -- and the request is in flight during the mask / force section below.
             double4 q = q1;
             const int hs = hs1;
+            const double hd = hd1;
             bool live = have1 && q.w != 0.0;
             double ex = q.x - bcx, ey = q.y - bcy, ez = q.z - bcz;
             if(!nowrap)
@@ -1372,6 +1422,8 @@ __global__ __launch_bounds__(MODE == 1 ? GW3_TBLOCK : (MODE == 2 ? GW2_MAXWAVES 
                 const int o = npool + lane_prefix(lm);
                 pp[o] = q;
                 ph[o] = (unsigned char)(hs & 7);
+                if constexpr(ADA)
+                  lhs[o] = hd;
                 const float fx = (float)ex, fy = (float)ey, fz = (float)ez;
                 lfx[o] = fx;
                 lfy[o] = fy;
@@ -1389,7 +1441,7 @@ __global__ __launch_bounds__(MODE == 1 ? GW3_TBLOCK : (MODE == 2 ? GW2_MAXWAVES 
                 fetch_quad((cc + 1) / 4, qd, nv);
               const int itn = bn == 0 ? qd.x : (bn == 1 ? qd.y : (bn == 2 ? qd.z : qd.w));
               have1 = cc + 1 < nchunks && bn < nv;
-              fetch_rec(have1, itn, q1, hs1);
+              fetch_rec(have1, itn, q1, hs1, hd1);
             }
             wave_sync();
             if(npool >= WAVE || (last && npool > 0))
@@ -1486,7 +1538,7 @@ __global__ __launch_bounds__(MODE == 1 ? GW3_TBLOCK : (MODE == 2 ? GW2_MAXWAVES 
                 nint += direct ? (valid ? nc : 0) : __popcll(m);   // evalN takes the (rare) slots beyond the exact cut off again
                 bool direct_done = false;
                 if constexpr(!PM && !LATT)
-                  if(direct && !lanewrap && !(BAMCAP && wp.bam))
+                  if(direct && !lanewrap && !(BAMCAP && wp.bam) && !ADA)   // (the assembly loop reads the length per type)
                     {
                       // the common tree-only case in assembly (eval_asm.inc ER_DIRECT_ASM: unrolled twice, the next entry in flight,
                       // accumulators in place); a lane without a target takes part with zero coefficients
@@ -1590,11 +1642,14 @@ __global__ __launch_bounds__(MODE == 1 ? GW3_TBLOCK : (MODE == 2 ? GW2_MAXWAVES 
                 double4 tq;
                 unsigned char th = 0;
                 float t0 = 0, t1 = 0, t2 = 0, t3 = 0;
+                double td = 0;
                 tq.x = tq.y = tq.z = tq.w = 0;
                 if(lane < rem)
                   {
                     tq = pp[WAVE + lane];
                     th = ph[WAVE + lane];
+                    if constexpr(ADA)
+                      td = lhs[WAVE + lane];
                     t0 = lfx[WAVE + lane];
                     t1 = lfy[WAVE + lane];
                     t2 = lfz[WAVE + lane];
@@ -1605,6 +1660,8 @@ __global__ __launch_bounds__(MODE == 1 ? GW3_TBLOCK : (MODE == 2 ? GW2_MAXWAVES 
                   {
                     pp[lane] = tq;
                     ph[lane] = th;
+                    if constexpr(ADA)
+                      lhs[lane] = td;
                     lfx[lane] = t0;
                     lfy[lane] = t1;
                     lfz[lane] = t2;
@@ -1748,7 +1805,15 @@ __global__ __launch_bounds__(MODE == 1 ? GW3_TBLOCK : (MODE == 2 ? GW2_MAXWAVES 
                       // species' centres of mass -- is inside the softening length.  Every target's r2max is at least r2far (each
                       // distance to the box is a lower bound), so r2far < h^2 whenever any target would open: conservative, and
                       // for a one-target box exactly the reference's test
-                      if(!open && hT_min < hs_node && r2far < hs_node * hs_node && ((fl >> 5) & 1))
+                      if constexpr(ADA)
+                        {
+                          // forcetree.c:1503-1516, :1928-1941 in the same conservative form: the node's largest length for the
+                          // type's, and no mixed-softening bit in the condition
+                          const double hn = tv.maxsoft[my];
+                          if(!open && hT_min < hn && r2far < hn * hn)
+                            open = true;
+                        }
+                      else if(!open && hT_min < hs_node && r2far < hs_node * hs_node && ((fl >> 5) & 1))
                         open = true;
                       // A top leaf whose particles were not imported (FLAG_PSEUDO: global monopoles, no children) cannot be opened.
                       // The import decision covers every node a TARGET may open under the criterion in force at the decomposition; the
@@ -2072,12 +2137,13 @@ __global__ void k_finish(long long t_first, long long t_count, const unsigned ch
 // targets: particles tidx[k] of the working set, or (tidx == nullptr) explicit records t_pm[k] / t_type[k] -- a test particle of
 // ANOTHER task in the distributed gravity_forcetest(); own_only: the imported copies (active bit 1) are not sources, each task
 // contributes its own particles and the host adds the partial sums up
-template <bool USER = false>   // USER: tree-only wirings with a user-defined law
+template <bool USER = false, bool ADA = false>   // USER: tree-only wirings with a user-defined law; ADA: s_soft holds every particle's length
 __global__ __launch_bounds__(256) void k_direct(const double4 *__restrict__ s_pm, const unsigned char *__restrict__ s_type,
                                                  long long n, const int *__restrict__ tidx, long long nt, WalkParams wp,
                                                  LawIds li, double G, const double *__restrict__ lat, double *__restrict__ acc,
                                                  const double4 *__restrict__ t_pm = nullptr, const int *__restrict__ t_type = nullptr,
-                                                 const unsigned char *__restrict__ s_active = nullptr, int own_only = 0)
+                                                 const unsigned char *__restrict__ s_active = nullptr, int own_only = 0,
+                                                 const double *__restrict__ s_soft = nullptr)
 {
   // one block per target, threads stride over sources, fp64 block reduction
   long long k = blockIdx.x;
@@ -2085,11 +2151,14 @@ __global__ __launch_bounds__(256) void k_direct(const double4 *__restrict__ s_pm
     return;
   double4 p;
   int ptype;
+  double hT = 0;
   if(tidx)
     {
       const int t = tidx[k];
       p = s_pm[t];
       ptype = s_type[t];
+      if constexpr(ADA)
+        hT = s_soft[t];
     }
   else
     {
@@ -2105,6 +2174,8 @@ __global__ __launch_bounds__(256) void k_direct(const double4 *__restrict__ s_pm
       double4 q = s_pm[i];
       int qt = s_type[i], sg = wp.t2g[qt];
       double h = wp.fsoft[qt] > wp.fsoft[ptype] ? wp.fsoft[qt] : wp.fsoft[ptype];
+      if constexpr(ADA)
+        h = s_soft[i] > hT ? s_soft[i] : hT;   // forcetree.c:1398-1413 as the direct sum's pair rule
       double dx = q.x - p.x, dy = q.y - p.y, dz = q.z - p.z;
       if(wp.periodic)
         {
@@ -2291,6 +2362,8 @@ static TreeView tree_view(ngravs_ctx *c)
   tv.ltab_cl = c->lvl_table_level ? c->dom[6] / (double)(1 << c->lvl_table_level) : 0.0;
   for(int j = 0; j < 3; j++)
     tv.ltab_corner[j] = c->dom[j];
+  tv.soft = c->gsoft_on ? c->s_soft.p : nullptr;
+  tv.maxsoft = c->gsoft_on ? c->n_maxsoft.p : nullptr;
   return tv;
 }
 
@@ -2402,15 +2475,17 @@ static int ensure_lattice(ngravs_ctx *c)
 }
 
 // the instantiations of k_walk_strict<NG, PM, LATT, USER>: TreePM, periodic tree-only, tree-only; each with and without a user law
-template <int NG> using StrictRowsNG = Table<Row<NG, 1, 0, 0>, Row<NG, 1, 0, 1>, Row<NG, 0, 1, 0>, Row<NG, 0, 1, 1>, Row<NG, 0, 0, 0>, Row<NG, 0, 0, 1>>;
+// ... and the three regimes with adaptive gas softening (built-in laws only)
+template <int NG> using StrictRowsNG = Table<Row<NG, 1, 0, 0, 0>, Row<NG, 1, 0, 1, 0>, Row<NG, 0, 1, 0, 0>, Row<NG, 0, 1, 1, 0>, Row<NG, 0, 0, 0, 0>, Row<NG, 0, 0, 1, 0>,
+                                             Row<NG, 1, 0, 0, 1>, Row<NG, 0, 1, 0, 1>, Row<NG, 0, 0, 0, 1>>;
 using StrictRows = decltype(StrictRowsNG<1>{} + StrictRowsNG<2>{} + StrictRowsNG<3>{});
 
-template <int NG, int PM, int LATT, int USER>
-static int launch_strict(Row<NG, PM, LATT, USER>, ngravs_ctx *c, const WalkParams &wp, const LawIds &li)
+template <int NG, int PM, int LATT, int USER, int ADA>
+static int launch_strict(Row<NG, PM, LATT, USER, ADA>, ngravs_ctx *c, const WalkParams &wp, const LawIds &li)
 {
   long long ngroups = (c->shard_count + WAVE - 1) / WAVE;
   unsigned nb = (unsigned)((ngroups + 3) / 4);
-  hipLaunchKernelGGL((k_walk_strict<NG, PM, LATT, USER>), dim3(nb), dim3(256), 0, c->stream, tree_view(c), c->s_pm.p, c->s_type.p,
+  hipLaunchKernelGGL((k_walk_strict<NG, PM, LATT, USER, ADA>), dim3(nb), dim3(256), 0, c->stream, tree_view(c), c->s_pm.p, c->s_type.p,
                      c->s_oldacc.p, c->s_active.p, LATT ? c->lat.p : c->table.p, wp, li, (long long)c->shard_first,
                      (long long)c->shard_count, c->r_acc.p, c->r_nint.p, c->walk_counters.p + 1);
   return NGRAVS_OK;
@@ -2475,15 +2550,16 @@ struct EvalLds
   int waves;
   size_t bytes;
 };
-static EvalLds eval_lds(const WalkParams &wp, bool tables, int max_waves)
+static EvalLds eval_lds(const WalkParams &wp, bool tables, int max_waves, bool ada = false)
 {
   const size_t fixed = (tables ? sizeof(double) * (wp.ntab_lds + wp.exp_tab) * NTAB : 0) + 40 * sizeof(double);
-  int waves = (int)((160 * 1024 - fixed) / GW2_WAVE_LDS);
+  const size_t per_wave = ada ? GW2_WAVE_LDS_ADA : GW2_WAVE_LDS;
+  int waves = (int)((160 * 1024 - fixed) / per_wave);
   if(waves > max_waves)
     waves = max_waves;
   if(waves < 1)
     waves = 1;
-  return {waves, fixed + (size_t)waves * GW2_WAVE_LDS};
+  return {waves, fixed + (size_t)waves * per_wave};
 }
 
 // hipFuncAttributeMaxDynamicSharedMemorySize of a walk kernel: set when the kernel is first launched with this size, not on every
@@ -2504,8 +2580,8 @@ static int walk_dyn_lds(ngravs_ctx *c, const void *kern, size_t lds)
   return NGRAVS_OK;
 }
 
-template <int NG, int PM, int YUK, int TAB_LDS, int LATT, int USR>
-static int launch_group2_t(Row<NG, PM, YUK, TAB_LDS, LATT, USR>, ngravs_ctx *c, const WalkParams &wp, int *glist, int nlist)
+template <int NG, int PM, int YUK, int TAB_LDS, int LATT, int USR, int ADA>
+static int launch_group2_t(Row<NG, PM, YUK, TAB_LDS, LATT, USR, ADA>, ngravs_ctx *c, const WalkParams &wp, int *glist, int nlist)
 {
   // lanes per target: the walk's own S, or for the leftover pass (glist) enough to give the few scattered groups many waves
   const int S0 = c->walk_spread > 1 ? c->walk_spread : 1, G0 = (WAVE / S0) * (glist ? c->walk_sg : 1);
@@ -2518,7 +2594,7 @@ static int launch_group2_t(Row<NG, PM, YUK, TAB_LDS, LATT, USR>, ngravs_ctx *c, 
   const int G = WAVE / S;
   const int ncu = walk_cus(c);
   // one persistent workgroup per CU; register-limited: 3 waves per SIMD (__launch_bounds__)
-  const EvalLds l = eval_lds(wp, PM && TAB_LDS, GW_MAXWAVES);
+  const EvalLds l = eval_lds(wp, PM && TAB_LDS, GW_MAXWAVES, ADA);
   const int waves = l.waves;
   const size_t lds = l.bytes;
   long long ngroups = glist ? (long long)nlist * (G0 / G) : (walk_tcount(c) + G - 1) / G;
@@ -2533,7 +2609,7 @@ static int launch_group2_t(Row<NG, PM, YUK, TAB_LDS, LATT, USR>, ngravs_ctx *c, 
     HIP_TRY(c, hipMemsetAsync(c->walk_counters.p + 8, 0, sizeof(int) * 8, c->stream));
   else
     HIP_TRY(c, hipMemsetAsync(c->walk_counters.p, 0, sizeof(int) * 32, c->stream));
-  auto kern = k_walk_group2<NG, PM, YUK, TAB_LDS, LATT, 0, USR>;
+  auto kern = k_walk_group2<NG, PM, YUK, TAB_LDS, LATT, 0, USR, ADA>;
   if(int rl = walk_dyn_lds(c, reinterpret_cast<const void *>(kern), lds))
     return rl;
   hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(waves * 64), lds, c->stream, tree_view(c), c->s_pm.p,
@@ -2564,13 +2640,13 @@ static int walk_unit_next(int st, double r)
 
 // split walk: per batch of groups a high-occupancy traversal kernel (MODE 1) writes the item lists, then the persistent
 // evaluation kernel (MODE 2) consumes them.  Same results as the fused kernel (same lists, same order).
-template <int NG, int PM, int YUK, int TAB_LDS, int LATT, int USR>
-static int launch_group3_t(Row<NG, PM, YUK, TAB_LDS, LATT, USR>, ngravs_ctx *c, const WalkParams &wp)
+template <int NG, int PM, int YUK, int TAB_LDS, int LATT, int USR, int ADA>
+static int launch_group3_t(Row<NG, PM, YUK, TAB_LDS, LATT, USR, ADA>, ngravs_ctx *c, const WalkParams &wp)
 {
   const int ncu = walk_cus(c);
   // register-limited: 4 waves per SIMD (__launch_bounds__), one workgroup per CU; tuning: fewer waves per evaluation workgroup
   const int max_waves = c->tune.walk_waves > 0 && c->tune.walk_waves < GW2_MAXWAVES ? c->tune.walk_waves : GW2_MAXWAVES;
-  const EvalLds l = eval_lds(wp, PM && TAB_LDS, max_waves);
+  const EvalLds l = eval_lds(wp, PM && TAB_LDS, max_waves, ADA);
   int waves = l.waves;
   const size_t lds = l.bytes;
   const int S = c->walk_spread > 1 ? c->walk_spread : 1, G = WAVE / S;
@@ -2638,13 +2714,13 @@ static int launch_group3_t(Row<NG, PM, YUK, TAB_LDS, LATT, USR>, ngravs_ctx *c, 
     return NGRAVS_ERR_NOMEM;
   int *region = c->walk_stack.p, *gcount = c->walk_stack.p + (size_t)batch * region_ints;
   HIP_TRY(c, hipMemsetAsync(c->walk_counters.p, 0, sizeof(int) * 32, c->stream));
-  auto kt = k_walk_group2<NG, PM, YUK, TAB_LDS, LATT, 1, USR>;
-  auto ke = k_walk_group2<NG, PM, YUK, TAB_LDS, LATT, 2, USR>;
+  auto kt = k_walk_group2<NG, PM, YUK, TAB_LDS, LATT, 1, USR, ADA>;
+  auto ke = k_walk_group2<NG, PM, YUK, TAB_LDS, LATT, 2, USR, ADA>;
   if(int rl = walk_dyn_lds(c, reinterpret_cast<const void *>(ke), lds))
     return rl;
   // TreePM lists with the tables in LDS go through the ring-pool evaluation kernel when at least 4 slots per wave fit
   int ringK = 0, ring_waves = waves;
-  if constexpr(PM && TAB_LDS && !LATT && !USR)
+  if constexpr(PM && TAB_LDS && !LATT && !USR && !ADA)   // (the ring kernel reads the softening length per type)
     if(c->tune.walk_ring)
       {
         ring_waves = max_waves;
@@ -2703,12 +2779,17 @@ struct GroupVariant
 {
   bool pm, yuk, tab, latt, usr;
   int reports;
+  bool ada = false;
 };
 // ... chosen here and nowhere else
 static GroupVariant group_variant(const ngravs_ctx *c, const WalkParams &wp, int ng)
 {
   const bool yuk = has_yukawa(c), usr = wp.user != 0;
   const int id = usr ? NGRAVS_KERNEL_GROUP_USER : NGRAVS_KERNEL_GROUP;
+  // adaptive gas softening (launch_group has refused what is not listed here): periodic TreePM and tree-only, each ONE variant
+  // per N_GRAVS -- the one with the Yukawa code, whose coefficient is 0 where no Yukawa law is wired
+  if(c->gsoft_on)
+    return {c->cfg.pmgrid != 0, true, c->cfg.pmgrid != 0 && ng <= 2, false, false, NGRAVS_KERNEL_GROUP_ADAPTIVE, true};
   // a wiring with a user-defined law in a TreePM or periodic tree-only run has its own evaluation variant (USR, without the Yukawa
   // code; never the ring kernel)
   if(c->cfg.pmgrid)
@@ -2726,11 +2807,13 @@ static GroupVariant group_variant(const ngravs_ctx *c, const WalkParams &wp, int
   return {false, yuk && !bam, bam, false, false, bam ? id : NGRAVS_KERNEL_GROUP};
 }
 // ... and instantiated for these rows <NG, PM, YUK, TAB_LDS, LATT, USR> alone (NG <= 2: the first TreePM line repeats two rows of the second)
+// (last column ADA: adaptive gas softening, two rows per N_GRAVS)
 template <int NG>
-using GroupRowsNG = Table<Row<NG, 1, 0, NG <= 2, 0, 1>, Row<NG, 1, 0, NG <= 2, 0, 0>, Row<NG, 1, 1, NG <= 2, 0, 0>,   // TreePM
-                          Row<NG, 1, 0, 1, 0, 0>, Row<NG, 1, 1, 1, 0, 0>,                                            // TreePM, tables in LDS
-                          Row<NG, 0, 0, 0, 1, 1>, Row<NG, 0, 0, 0, 1, 0>, Row<NG, 0, 1, 0, 1, 0>,                     // periodic tree-only
-                          Row<NG, 0, 0, 1, 0, 0>, Row<NG, 0, 0, 0, 0, 0>, Row<NG, 0, 1, 0, 0, 0>>;                    // tree-only: law ids, plain
+using GroupRowsNG = Table<Row<NG, 1, 0, NG <= 2, 0, 1, 0>, Row<NG, 1, 0, NG <= 2, 0, 0, 0>, Row<NG, 1, 1, NG <= 2, 0, 0, 0>,   // TreePM
+                          Row<NG, 1, 0, 1, 0, 0, 0>, Row<NG, 1, 1, 1, 0, 0, 0>,                                               // TreePM, tables in LDS
+                          Row<NG, 0, 0, 0, 1, 1, 0>, Row<NG, 0, 0, 0, 1, 0, 0>, Row<NG, 0, 1, 0, 1, 0, 0>,                     // periodic tree-only
+                          Row<NG, 0, 0, 1, 0, 0, 0>, Row<NG, 0, 0, 0, 0, 0, 0>, Row<NG, 0, 1, 0, 0, 0, 0>,                     // tree-only: law ids, plain
+                          Row<NG, 1, 1, NG <= 2, 0, 0, 1>, Row<NG, 0, 1, 0, 0, 0, 1>>;                                         // adaptive: TreePM, tree-only
 using GroupRows = decltype(GroupRowsNG<1>{} + GroupRowsNG<2>{} + GroupRowsNG<3>{});
 
 // the whole walk (split into traversal / evaluation kernel pairs unless the tuning asks for the fused kernel), or the groups of
@@ -2743,9 +2826,22 @@ static int launch_group(ngravs_ctx *c, const WalkParams &wp, bool *used_split, i
       c->walk_batches = 0;
       *used_split = split;
     }
+  if(c->gsoft_on)
+    {
+      // the group walk has adaptive kernels for the built-in non-BAM laws, tree-only without periodic boundaries and periodic
+      // TreePM; nothing else is walked in another mode behind the caller's back
+      const char *what = cfg_has_bam(c->cfg) ? "a BAM law" : (c->cfg.periodic && !c->cfg.pmgrid ? "a periodic tree-only run" :
+                         (!c->cfg.periodic && c->cfg.pmgrid ? "a non-periodic TreePM run" : nullptr));
+      if(what)
+        {
+          ngravs_report(c, NGRAVS_ERR_ARG, std::string("the group walk has no kernel for adaptive gas softening with ") + what +
+                                               ": NGRAVS_WALK_STRICT serves this configuration");
+          return NGRAVS_ERR_ARG;
+        }
+    }
   const GroupVariant v = group_variant(c, wp, c->cfg.n_gravs);
   c->last_walk_kernel = v.reports;
-  const int key[] = {c->cfg.n_gravs, v.pm, v.yuk, v.tab, v.latt, v.usr};
+  const int key[] = {c->cfg.n_gravs, v.pm, v.yuk, v.tab, v.latt, v.usr, v.ada};
   return dispatch(c, GroupRows{}, key, [&](auto row) {
     if(split)
       return launch_group3_t(row, c, wp);
@@ -2803,6 +2899,88 @@ static int walk_read_back(ngravs_ctx *c, int *flag, unsigned long long (&st64)[4
   return NGRAVS_OK;
 }
 
+// ---- adaptive softening for gas: the columns the ADA kernels read ------------------------------------------------------------
+__global__ void k_soft_column(const unsigned int *__restrict__ s_idx, const unsigned char *__restrict__ s_type,
+                              const double *__restrict__ in_gsoft, long long n, WalkParams wp, double *__restrict__ s_soft)
+{
+  const long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+  if(i >= n)
+    return;
+  const int t = s_type[i];
+  s_soft[i] = t == 0 ? in_gsoft[s_idx[i]] : wp.fsoft[t];
+}
+// force_update_node_recursive's maxsoft (forcetree.c:518-523, :600-601, :645-654, :705-709): the nodes of one level from their
+// children, the levels bottom-up (as k_sph_hmax); an empty node holds 0
+__global__ void k_node_maxsoft(const int *__restrict__ n_child, const int *__restrict__ n_first, const int *__restrict__ n_count,
+                               const int *__restrict__ n_flags, const double *__restrict__ s_soft, long long n, int node0,
+                               int nnodes_level, double *__restrict__ maxsoft)
+{
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if(t >= nnodes_level)
+    return;
+  const int node = node0 + t;
+  double m = 0;
+  if(n_flags[node] & FLAG_BUCKET)
+    {
+      const long long f = n_first[node], cnt = n_count[node];
+      for(long long p = f; p < f + cnt && p < n; p++)
+        m = fmax(m, s_soft[p]);
+    }
+  else
+    for(int k = 0; k < 8; k++)
+      {
+        const int ch = n_child[8ll * node + k];
+        if(ch >= 0)
+          m = fmax(m, maxsoft[ch]);
+        else if(ch <= -2 && -2 - ch < n)
+          m = fmax(m, s_soft[-2 - ch]);
+      }
+  maxsoft[node] = m;
+}
+
+int adaptive_refresh(ngravs_ctx *c, bool nodes)
+{
+  if(!c->gsoft_on || !c->have_order)
+    return NGRAVS_ERR_STATE;
+  if(c->n_local != c->n || c->top.on || c->cfg.world_size > 1)
+    {
+      ngravs_report(c, NGRAVS_ERR_STATE, "adaptive gas softening: single task only (imported copies and top-leaf sums carry no "
+                                         "softening length)");
+      return NGRAVS_ERR_STATE;
+    }
+  const long long n = c->n;
+  if(c->gsoft_col_stale)
+    {
+      if(c->s_soft.ensure((size_t)n))
+        return NGRAVS_ERR_NOMEM;
+      WalkParams wp;
+      make_walk_params(c, &wp);
+      hipLaunchKernelGGL(k_soft_column, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->s_idx.p, c->s_type.p, c->in_gsoft.p,
+                         n, wp, c->s_soft.p);
+      HIP_TRY(c, hipGetLastError());
+      c->gsoft_col_stale = false;
+      c->gsoft_node_stale = true;
+    }
+  if(nodes && c->gsoft_node_stale)
+    {
+      if(!c->have_tree || c->nnodes <= 0)
+        return NGRAVS_ERR_STATE;
+      if(c->n_maxsoft.ensure((size_t)c->nnodes))
+        return NGRAVS_ERR_NOMEM;
+      for(int l = c->nlevels - 1; l >= 0; l--)
+        {
+          const long long l0 = c->level_start[l], lc = c->level_start[l + 1] - l0;
+          if(lc <= 0)
+            continue;
+          hipLaunchKernelGGL(k_node_maxsoft, dim3((unsigned)((lc + 127) / 128)), dim3(128), 0, c->stream, c->n_child.p, c->n_first.p,
+                             c->n_count.p, c->n_flags.p, c->s_soft.p, n, (int)l0, (int)lc, c->n_maxsoft.p);
+        }
+      HIP_TRY(c, hipGetLastError());
+      c->gsoft_node_stale = false;
+    }
+  return NGRAVS_OK;
+}
+
 // The walk in two halves: walk_enqueue() puts every launch of the walk on c->stream and returns without waiting for them;
 // walk_complete() waits, redoes what the split walk left over, and reads the statistics.  Between the two the host may enqueue
 // other work on another stream (PM beside the walk, ngravs_compute_accelerations).
@@ -2823,6 +3001,11 @@ int walk_enqueue(ngravs_ctx *c)
     if(rcu)
       return rcu;
   }
+  if(c->gsoft_on)
+    {
+      if(int rca = adaptive_refresh(c, true))
+        return rca;
+    }
   WalkParams wp;
   make_walk_params(c, &wp);
   LawIds li;
@@ -2865,8 +3048,8 @@ int walk_enqueue(ngravs_ctx *c)
       if(c->walk_counters.ensure(32))
         return NGRAVS_ERR_NOMEM;
       HIP_TRY(c, hipMemsetAsync(c->walk_counters.p, 0, sizeof(int) * 32, c->stream));
-      c->last_walk_kernel = wp.user ? NGRAVS_KERNEL_STRICT_USER : NGRAVS_KERNEL_STRICT;
-      const int key[] = {c->cfg.n_gravs, pm, latt, wp.user != 0};
+      c->last_walk_kernel = c->gsoft_on ? NGRAVS_KERNEL_STRICT_ADAPTIVE : (wp.user ? NGRAVS_KERNEL_STRICT_USER : NGRAVS_KERNEL_STRICT);
+      const int key[] = {c->cfg.n_gravs, pm, latt, wp.user != 0, c->gsoft_on ? 1 : 0};
       rc = dispatch(c, StrictRows{}, key, [&](auto row) { return launch_strict(row, c, wp, li); });
     }
   else
@@ -2993,8 +3176,8 @@ int walk_finish(ngravs_ctx *c)
 
 // The direct sum over the particles of this task: for the targets d_idx (indices), or for explicit target records d_tpm / d_ttype
 // over the OWN particles alone (distributed gravity_forcetest).  The two differ in the kernel's last five arguments only.
-using DirectRows = Table<Row<0>, Row<1>>;   // k_direct<USER>
-template <int USER> static auto direct_kernel(Row<USER>) { return k_direct<USER>; }
+using DirectRows = Table<Row<0, 0>, Row<1, 0>, Row<0, 1>>;   // k_direct<USER, ADA>
+template <int USER, int ADA> static auto direct_kernel(Row<USER, ADA>) { return k_direct<USER, ADA>; }
 static int direct_launch(ngravs_ctx *c, double r_need, const int *d_idx, int64_t nt, double *d_acc, const double4 *d_tpm, const int *d_ttype)
 {
   if(c->cfg.periodic && !user_lattice_complete(c))
@@ -3013,11 +3196,14 @@ static int direct_launch(ngravs_ctx *c, double r_need, const int *d_idx, int64_t
   make_law_ids(c, &li);
   if(latt && (rc = ensure_lattice(c)))
     return rc;
-  const int key[] = {wp.user != 0};
+  const bool ada = c->gsoft_on && !d_tpm;
+  if(ada && (rc = adaptive_refresh(c, false)))
+    return rc;
+  const int key[] = {wp.user != 0, ada ? 1 : 0};
   rc = dispatch(c, DirectRows{}, key, [&](auto row) {
     hipLaunchKernelGGL(direct_kernel(row), dim3((unsigned)nt), dim3(256), 0, c->stream, c->s_pm.p, c->s_type.p, (long long)c->n, d_idx, (long long)nt,
                        wp, li, c->cfg.G, latt ? c->lat.p : (const double *)nullptr, d_acc, d_tpm, d_ttype,
-                       d_tpm ? c->s_active.p : (const unsigned char *)nullptr, d_tpm ? 1 : 0);
+                       d_tpm ? c->s_active.p : (const unsigned char *)nullptr, d_tpm ? 1 : 0, ada ? c->s_soft.p : (const double *)nullptr);
     return NGRAVS_OK;
   });
   if(rc)

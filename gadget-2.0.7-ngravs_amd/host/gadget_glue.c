@@ -389,6 +389,27 @@ static void push_particles(int keep_tree)
   must(keep_tree ? ngravs_update_particles(Ctx, &p) : ngravs_set_particles(Ctx, &p), 1056);
 }
 
+#ifdef ADAPTIVE_GRAVSOFT_FORGAS
+/* forcetree.c:1398-1413: a gas particle's gravitational softening length is SphP[].Hsml as it is when the walk runs.  One column
+ * of NumPart doubles, row i < N_gas from SphP[i].Hsml (rows of other types are not read).  ngravs_set_particles() drops the
+ * library's copy, so this follows every push_particles(), in front of the walk.  Several tasks with gas never get here
+ * (endrun(1055) in ensure_ctx); without gas the switch changes nothing and nothing is handed over. */
+static void push_gas_softening(void)
+{
+  double *col;
+  int i;
+  if(N_gas <= 0 || NumPart <= 0)
+    return;
+  col = malloc(sizeof(double) * NumPart);
+  if(!col)
+    endrun(1090);
+  for(i = 0; i < NumPart; i++)
+    col[i] = i < N_gas ? SphP[i].Hsml : 0.0;
+  must(ngravs_set_gas_softening(Ctx, col, sizeof(double), 0), 1091);
+  free(col);
+}
+#endif
+
 /* domain_decompose() bookkeeping (domain.c:173-195) */
 static void count_types(void)
 {
@@ -779,6 +800,9 @@ void gravity_tree(void)
    * second time with the OldAcc the first call has just written -- the hand-over of the decomposition does not have it yet */
   if(NumPart > 0)
     must(ngravs_set_old_acc(Ctx, &P[0].OldAcc, sizeof(struct particle_data), 0), 1074);
+#ifdef ADAPTIVE_GRAVSOFT_FORGAS
+  push_gas_softening();
+#endif
   must(ngravs_gravity_tree(Ctx), 1063);
   if(KeptStep)
     {
@@ -805,6 +829,9 @@ void gravity_tree(void)
 	  All.NumForcesSinceLastDomainDecomp = 0;
 	  if(NumPart > 0)
 	    must(ngravs_set_old_acc(Ctx, &P[0].OldAcc, sizeof(struct particle_data), 0), 1074);
+#ifdef ADAPTIVE_GRAVSOFT_FORGAS
+	  push_gas_softening();
+#endif
 	  must(ngravs_gravity_tree(Ctx), 1063);
 	}
     }

@@ -207,7 +207,9 @@ typedef enum {
   NGRAVS_KERNEL_STRICT = 1,        /* k_walk_strict, built-in laws                                  */
   NGRAVS_KERNEL_STRICT_USER = 2,   /* k_walk_strict with the user-law tables                       */
   NGRAVS_KERNEL_GROUP = 3,         /* the group walk, built-in laws                                 */
-  NGRAVS_KERNEL_GROUP_USER = 4     /* the group walk with user laws: the law-id variant (tree-only) or k_walk_group2<..., USR> (TreePM) */
+  NGRAVS_KERNEL_GROUP_USER = 4,    /* the group walk with user laws: the law-id variant (tree-only) or k_walk_group2<..., USR> (TreePM) */
+  NGRAVS_KERNEL_STRICT_ADAPTIVE = 5, /* k_walk_strict with per-particle gas softening (ngravs_set_gas_softening)   */
+  NGRAVS_KERNEL_GROUP_ADAPTIVE = 6   /* the group walk with per-particle gas softening: k_walk_group2<..., ADA>    */
 } ngravs_walk_kernel_id;
 
 /* ---- lifecycle ------------------------------------------------------------------------- */
@@ -287,6 +289,17 @@ int ngravs_update_particles(ngravs_ctx *ctx, const ngravs_particles_t *p);
 /* Update OldAcc only (second pass of accel.c:48-52 without re-uploading positions): the caller's OWN rows (NumPart =
  * ngravs_dd_num_local() of them; the imported copies of a multi-task working set are sources only and keep what they came with). */
 int ngravs_set_old_acc(ngravs_ctx *ctx, const double *old_acc, int64_t stride, int on_device);
+/* Adaptive gravitational softening for gas (the reference's ADAPTIVE_GRAVSOFT_FORGAS): hsml addresses one length per OWN row in
+ * the caller's order (stride in bytes); rows that are not type 0 are never read.  From the next walk or direct sum on a type-0
+ * particle's softening length is its hsml value instead of force_softening[0]; a pair is softened with the larger of its two
+ * lengths, and a node is opened by the largest length below it (forcetree.c:1398-1413, :1503-1516).  hsml = NULL switches back to
+ * the lengths per type.  ngravs_update_particles() keeps the column, ngravs_set_particles() drops it; the call may come before
+ * or after the tree build.  Refused, with nothing changed: NGRAVS_ERR_ARG before particles were handed over, for a type-0 row
+ * whose value is negative or not finite, and for a context with user-defined laws (their spline tables are sampled per softening
+ * length); NGRAVS_ERR_STATE "single task only" with world_size > 1 or a multi-task working set.  While it is on,
+ * ngravs_direct_sum_targets() returns NGRAVS_ERR_STATE (explicit targets carry no length), and ngravs_gravity_tree() returns
+ * NGRAVS_ERR_ARG for a group-walk configuration that has no adaptive kernel (NGRAVS_WALK_STRICT serves every one). */
+int ngravs_set_gas_softening(ngravs_ctx *ctx, const double *hsml, int64_t stride, int on_device);
 
 /* ---- the path ---------------------------------------------------------------------------- */
 /* domain_findExtent + keys + Peano-Hilbert order (domain.c:882-944, peano.c:36-185).  Computes
