@@ -43,6 +43,7 @@ EXPORTS = [
     "ngravs_pm_slab_begin", "ngravs_pm_slab_pack", "ngravs_pm_slab_unpack", "ngravs_pm_slab_bytes",
     "ngravs_sph_density", "ngravs_sph_kernel", "ngravs_sph_hydro", "ngravs_sph_accelerations",
     "ngravs_sph_hsml_guess", "ngravs_sph_density_sums", "ngravs_sph_hydro_sums", "ngravs_sph_density_update",
+    "ngravs_gravity_tree_targets", "ngravs_pm_targets",
 ]
 # include/ngravs_host.h (plain-C multi-task drivers over a communicator vtable, linked into the same library)
 HOST_EXPORTS = ["ngravs_host_comm_selftest", "ngravs_host_kept_step", "ngravs_host_toptree_borrow", "ngravs_host_domain_decomposition", "ngravs_host_domain_owners", "ngravs_host_domain_halo",
@@ -139,6 +140,8 @@ def lib():
         L.ngravs_sph_hydro_sums.argtypes = abi.SPH_HYDRO_SUMS_ARGTYPES
         L.ngravs_sph_density_update.argtypes = abi.SPH_DENSITY_UPDATE_ARGTYPES
         L.ngravs_sph_density_update.restype = C.c_int64
+        L.ngravs_gravity_tree_targets.argtypes = abi.GRAVITY_TREE_TARGETS_ARGTYPES
+        L.ngravs_pm_targets.argtypes = abi.PM_TARGETS_ARGTYPES
         _LIB = L
     return _LIB
 
@@ -724,6 +727,58 @@ class Engine:
         self._check(lib().ngravs_direct_sum_targets(self._h, pos.ctypes.data, _ptr(mass), ptype.ctypes.data, len(pos), out.ctypes.data),
                     "ngravs_direct_sum_targets")
         return out
+
+    @staticmethod
+    def _grav_targets(pos, ptype, old_acc=None, mass=None):
+        """(abi.GravTargets, nt, on_device, the arrays it points to) for target records given as numpy arrays or torch tensors on
+        the device.  Needs no device: a pos that is not floating point [nt,3] or a ptype that is not integer [nt] is a ValueError."""
+        on_device = _is_device(pos)
+        if not on_device:
+            pos, ptype = np.asarray(pos), np.asarray(ptype)
+        if len(pos.shape) != 2 or pos.shape[1] != 3 or not ("float" in str(pos.dtype)):
+            raise ValueError("pos must be a floating-point array of shape [nt, 3], not %s %s" % (pos.dtype, tuple(pos.shape)))
+        nt = int(pos.shape[0])
+        if tuple(ptype.shape) != (nt,) or not ("int" in str(ptype.dtype)):
+            raise ValueError("ptype must be an integer array of shape [%d], not %s %s" % (nt, ptype.dtype, tuple(ptype.shape)))
+        if on_device:
+            import torch
+            ptype = ptype.to(torch.int32)   # (the other columns must be float64 as they are: _columns)
+        cols, addr = _columns(dict(pos=pos, type=ptype, old_acc=old_acc, mass=mass), dict(pos=(nt, 3), type=(nt,), old_acc=(nt,), mass=(nt,)),
+                              on_device, int_keys=("type",))
+        tg = abi.GravTargets()
+        _set_columns(tg, cols, addr)
+        tg.on_device = int(on_device)
+        return tg, nt, on_device, cols
+
+    def gravity_tree_targets(self, pos, ptype, old_acc=None, mass=None, want_nint=False):
+        """The tree force of this engine's particles at targets that need not be its particles (the reference's walk for imported
+        particles, force_treeevaluate(j, 1) / _shortrange(j, 1), gravtree.c:133-285): pos [nt,3], ptype [nt], old_acc [nt] or None
+        (0: the relative criterion then opens every node), mass [nt] or None (1; only the BAM laws read it), in any order.  Always
+        the strict walk, with the engine's current opening criterion; TreePM engines give the short-range force (add pm_targets()).
+        numpy arrays, or torch tensors on the device.  Returns acc [nt,3] (x G), or (acc, nint) with the interaction counts.  The
+        engine's own accelerations are not touched."""
+        tg, nt, on_device, keep = self._grav_targets(pos, ptype, old_acc, mass)
+        acc = _zeros((nt, 3), pos, on_device)
+        nint = _zeros(nt, pos, on_device, np.int32)
+        ms = C.c_double(0)
+        if nt > 0:
+            addr = (lambda a: a.data_ptr()) if on_device else (lambda a: a.ctypes.data)
+            self._check(lib().ngravs_gravity_tree_targets(self._h, C.byref(tg), nt, addr(acc), addr(nint), C.byref(ms)),
+                        "ngravs_gravity_tree_targets")
+        self.last_targets_ms = float(ms.value)
+        del keep
+        return (acc, nint) if want_nint else acc
+
+    def pm_targets(self, pos, ptype):
+        """GravPM of the last PM step's mesh at targets that need not be this engine's particles: pos [nt,3] inside [0, BoxSize],
+        ptype [nt]; numpy arrays, or torch tensors on the device.  Returns grav_pm [nt,3], G included.  The mesh stays valid across
+        steps without PM."""
+        tg, nt, on_device, keep = self._grav_targets(pos, ptype)
+        pm = _zeros((nt, 3), pos, on_device)
+        if nt > 0:
+            self._check(lib().ngravs_pm_targets(self._h, C.byref(tg), nt, pm.data_ptr() if on_device else pm.ctypes.data), "ngravs_pm_targets")
+        del keep
+        return pm
 
     def direct_sum(self, idx):
         idx = np.ascontiguousarray(idx, dtype=np.int32)

@@ -205,6 +205,19 @@ SPH_HYDRO_SUMS_ARGTYPES = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_vo
 SPH_DENSITY_UPDATE_ARGTYPES = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double,
                                C.c_void_p, C.c_int32]
 
+GRAV_TARGET_NAMES = ("pos", "type", "old_acc", "mass")
+
+
+class GravTargets(C.Structure):
+    """ngravs_grav_targets_t"""
+    _fields_ = [f for k in GRAV_TARGET_NAMES for f in ((k, C.c_void_p), (k + "_stride", C.c_int64))] + [("on_device", C.c_int32)]
+
+
+# int ngravs_gravity_tree_targets(ctx, targets, nt, acc, nint, kernel_ms)
+GRAVITY_TREE_TARGETS_ARGTYPES = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+# int ngravs_pm_targets(ctx, targets, nt, grav_pm)
+PM_TARGETS_ARGTYPES = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+
 
 def make_config(n_gravs=1, periodic=0, pmgrid=0, box_size=0.0, G=1.0, theta=0.5, err_tol_force_acc=0.005,
                 softening=None, type_to_grav=None, wiring="newton", yukawa_imass=60.0, walk_mode=WALK_STRICT,

@@ -409,6 +409,7 @@ extern "C" void ngravs_destroy(ngravs_ctx *c)
   c->r_nint.release();
   c->pm_rho.release();
   c->pm_phi.release();
+  c->pm_mesh_valid = false;
   c->pm_force.release();
   c->pm_orig.release();
   c->out_tmp.release();
@@ -436,6 +437,14 @@ extern "C" void ngravs_destroy(ngravs_ctx *c)
   c->sph_tg_key.release();
   c->sph_tg_ord.release();
   c->sph_tg_res.release();
+  c->gt_in.release();
+  c->gt_type.release();
+  c->gt_key.release();
+  c->gt_ord.release();
+  c->gt_tmp.release();
+  c->gt_acc.release();
+  c->gt_nint.release();
+  c->gt_counters.release();
   (void)hipEventDestroy(c->ev0);
   (void)hipEventDestroy(c->ev1);
   (void)hipEventDestroy(c->evk0);
@@ -556,6 +565,8 @@ extern "C" int ngravs_set_tuning(ngravs_ctx *c, const char *name, double v)
     t.dd_keep = v;
   else if(k == "pm_cus" && (iv == -1 || (iv >= 0 && iv <= 32 && iv % 8 == 0)))   // multiples of 8: the same share of every XCD
     t.pm_cus = (int)iv;
+  else if(k == "walk_tg_sort")
+    t.walk_tg_sort = iv != 0;
   else if(k == "sph_verbose")
     t.sph_verbose = iv != 0;
   else
@@ -2611,4 +2622,139 @@ extern "C" int ngravs_sph_kernel(double h, const double *r, int64_t n, double *w
         sph_spline(r[i] * hinv, hinv3, hinv4, &wk[i], &dwk[i]);
     }
   return NGRAVS_OK;
+}
+
+// ---- gravity for targets that are not own rows: the tree walk of force_treeevaluate(j, 1) / force_treeevaluate_shortrange(j, 1) /
+// force_treeevaluate_lattice_correction(j, 1) for one task (gravtree.c:133-285), and GravPM of the last PM step at their places ------
+static_assert(sizeof(ngravs_grav_targets_t) == 72, "the Python mirror (abi.GravTargets) assumes this layout");
+
+// What both calls refuse before anything is staged: NULL arguments and nt < 0, several tasks, adaptive gas softening
+static int grav_targets_refusals(ngravs_ctx *c, const SphRefuse &refuse, const ngravs_grav_targets_t *t, int64_t nt, const void *result,
+                                 const char *result_name)
+{
+  if(!t)
+    return refuse(NGRAVS_ERR_ARG, "targets is NULL");
+  if(!t->pos)
+    return refuse(NGRAVS_ERR_ARG, "targets->pos is NULL");
+  if(!t->type)
+    return refuse(NGRAVS_ERR_ARG, "targets->type is NULL");
+  if(!result)
+    return refuse(NGRAVS_ERR_ARG, (std::string(result_name) + " is NULL").c_str());
+  if(nt < 0 || nt > 0x7fffffff)
+    return refuse(NGRAVS_ERR_ARG, "nt must be >= 0 (and below 2^31)");
+  if(c->cfg.world_size > 1 || c->top.on || c->n_local != c->n)
+    return refuse(NGRAVS_ERR_STATE, "single task only (the top-level short-cuts of the reference's walk for imported targets, "
+                                    "forcetree.c:1424-1434, and a mesh in slabs are not served)");
+  if(c->gsoft_on)
+    return refuse(NGRAVS_ERR_STATE, "adaptive gas softening is on and explicit targets carry no softening length "
+                                    "(ngravs_set_gas_softening(ctx, NULL, 0, 0) switches it off)");
+  return NGRAVS_OK;
+}
+
+// The records into gt_in (pos[nt][3], old_acc[nt], mass[nt]) and gt_type; refused, with nothing written: a type outside 0..5, a
+// position that is not finite, or outside [0, BoxSize] in a periodic configuration.  *far: grav_targets_check
+static int grav_targets_stage(ngravs_ctx *c, const SphRefuse &refuse, const ngravs_grav_targets_t *t, int64_t nt, double *far)
+{
+  if(c->gt_in.ensure(8 * (size_t)nt) || c->gt_type.ensure((size_t)nt))
+    return refuse(NGRAVS_ERR_NOMEM, "device allocation failed");
+  int rc;
+  if((rc = upload_column_f64(c, t->pos, t->pos_stride, 3, nt, t->on_device, c->gt_in.p)) ||
+     (rc = upload_column_i32(c, t->type, t->type_stride, nt, t->on_device, c->gt_type.p)))
+    return rc;
+  if(t->old_acc)
+    rc = upload_column_f64(c, t->old_acc, t->old_acc_stride, 1, nt, t->on_device, c->gt_in.p + 3 * nt);
+  else
+    hipLaunchKernelGGL(k_fill_f64, GRID1(nt), 0, c->stream, c->gt_in.p + 3 * nt, (long long)nt, 0.0);
+  if(rc)
+    return rc;
+  if(t->mass)
+    rc = upload_column_f64(c, t->mass, t->mass_stride, 1, nt, t->on_device, c->gt_in.p + 4 * nt);
+  else
+    hipLaunchKernelGGL(k_fill_f64, GRID1(nt), 0, c->stream, c->gt_in.p + 4 * nt, (long long)nt, 1.0);
+  if(rc)
+    return rc;
+  HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
+  GravTargetsStats st;
+  if((rc = grav_targets_check(c, nt, &st, far)))
+    return rc;
+  if(st.bad_type)
+    return refuse(NGRAVS_ERR_ARG, "a target's type is outside 0..5");
+  if(st.bad_pos)
+    return refuse(NGRAVS_ERR_ARG, "a target's position is not finite, or outside [0, BoxSize] in a periodic run");
+  return NGRAVS_OK;
+}
+
+// a device result column (NULL: zeros) -> the caller's contiguous array
+static int grav_targets_deliver(ngravs_ctx *c, const void *res, size_t bytes, void *out, int on_device)
+{
+  if(res)
+    HIP_TRY(c, hipMemcpyAsync(out, res, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+  else if(on_device)
+    HIP_TRY(c, hipMemsetAsync(out, 0, bytes, c->stream));
+  else
+    memset(out, 0, bytes);
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return NGRAVS_OK;
+}
+
+extern "C" int ngravs_gravity_tree_targets(ngravs_ctx *c, const ngravs_grav_targets_t *t, int64_t nt, double *acc, int32_t *nint,
+                                           double *kernel_ms)
+{
+  if(!c)
+    return NGRAVS_ERR_ARG;
+  const SphRefuse refuse = {c, "ngravs_gravity_tree_targets"};
+  int rc;
+  if((rc = grav_targets_refusals(c, refuse, t, nt, acc, "acc")))
+    return rc;
+  if(!c->have_order || !c->have_tree)
+    return refuse(NGRAVS_ERR_STATE, "needs a built tree of the current particle set");
+  if(kernel_ms)
+    *kernel_ms = 0;
+  if(nt == 0)
+    return NGRAVS_OK;
+  (void)hipSetDevice(c->cfg.device);
+  if(c->tree_stale && (rc = ngravs_force_update_tree(c)))   // drifted tree: refresh columns and moments first, as ngravs_gravity_tree does
+    return rc;
+  if((rc = ensure_table(c)))
+    return rc;
+  double far = 0;
+  if((rc = grav_targets_stage(c, refuse, t, nt, &far)))
+    return rc;
+  const bool empty = c->n_local == 0 || c->nnodes <= 0;   // nothing to walk: no force, no interaction
+  if(!empty)
+    {
+      if((rc = walk_targets_run(c, nt, far)))
+        return rc;
+      HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
+      if(kernel_ms)
+        *kernel_ms = ev_ms(c);
+    }
+  if((rc = grav_targets_deliver(c, empty ? nullptr : c->gt_acc.p, sizeof(double) * 3 * (size_t)nt, acc, t->on_device)))
+    return rc;
+  return nint ? grav_targets_deliver(c, empty ? nullptr : c->gt_nint.p, sizeof(int) * (size_t)nt, nint, t->on_device) : NGRAVS_OK;
+}
+
+extern "C" int ngravs_pm_targets(ngravs_ctx *c, const ngravs_grav_targets_t *t, int64_t nt, double *grav_pm)
+{
+  if(!c)
+    return NGRAVS_ERR_ARG;
+  const SphRefuse refuse = {c, "ngravs_pm_targets"};
+  int rc;
+  if((rc = grav_targets_refusals(c, refuse, t, nt, grav_pm, "grav_pm")))
+    return rc;
+  if(!c->cfg.pmgrid)
+    return refuse(NGRAVS_ERR_STATE, "the configuration has no mesh (PMGRID = 0)");
+  if(!c->pm_mesh_valid)
+    return refuse(NGRAVS_ERR_STATE, "no valid mesh: needs the potential of a PM step (ngravs_pmforce_periodic) of this task");
+  if(nt == 0)
+    return NGRAVS_OK;
+  (void)hipSetDevice(c->cfg.device);
+  double far = 0;
+  if((rc = grav_targets_stage(c, refuse, t, nt, &far)))
+    return rc;
+  if(c->gt_acc.ensure(3 * (size_t)nt))
+    return refuse(NGRAVS_ERR_NOMEM, "device allocation failed");
+  if((rc = pm_targets_run(c, nt, c->gt_acc.p)))
+    return rc;
+  return grav_targets_deliver(c, c->gt_acc.p, sizeof(double) * 3 * (size_t)nt, grav_pm, t->on_device);
 }

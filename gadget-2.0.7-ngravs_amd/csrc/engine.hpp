@@ -190,6 +190,7 @@ struct Tuning
   int walk_ring = 1;        // TreePM evaluation through the ring-pool kernel (kernels_eval.hip); 0: k_walk_group2<...,2>
   int walk_ring_k = 0;      // ... with at most this many slots per wave (0: as many as fit, at most 8)
   int pm_cus = -1;          // PM beside the walk on this many reserved CUs (-1: chosen per step, 0: PM and walk one after another)
+  int walk_tg_sort = 1;     // ngravs_gravity_tree_targets walks its targets in Peano order (0: in the caller's order, for measurements)
   int sph_verbose = 0;      // ngravs_sph_density prints its iteration statistics (targets, rounds, candidates, neighbours) to stdout
 };
 
@@ -404,6 +405,19 @@ struct ngravs_ctx
   DevBuf<unsigned long long> sph_tg_key; // [2][nt]: the targets' Peano keys (coordinates clamped to the domain cube), unsorted and sorted
   DevBuf<unsigned int> sph_tg_ord;       // [2][nt]: 0 .. nt-1, and the caller's indices in Peano order
   DevBuf<double> sph_tg_res;             // [nt][7] or [nt][5], caller order: copied out only when the whole call succeeded
+  // gravity for targets that are not own rows (ngravs_gravity_tree_targets / ngravs_pm_targets); empty until they are used.  The
+  // walk's own results (r_acc, r_nint, walk_counters, walk_tlist) are never written by these calls
+  DevBuf<double> gt_in;                  // the caller's target columns, caller order: pos[nt][3], old_acc[nt], mass[nt]; then the positions clamped to the domain cube [nt][3]
+  DevBuf<int> gt_type;                   // the targets' types
+  DevBuf<unsigned long long> gt_key;     // [2][nt]: the targets' Peano keys, unsorted and sorted
+  DevBuf<unsigned int> gt_ord;           // [2][nt]: 0 .. nt-1, and the caller's indices in Peano order
+  DevBuf<unsigned char> gt_tmp;          // scratch of the radix sort
+  DevBuf<double> gt_acc;                 // [nt][3], caller order: copied out only when the whole call succeeded
+  DevBuf<int> gt_nint;                   // [nt]
+  DevBuf<unsigned long long> gt_counters;   // GT_C_*: refused records, the farthest target, the walk's flag word
+  // pm_phi holds the complete potentials of the last single-mesh PM step (pm_finish); false before one, while they are being
+  // rewritten, and when the last PM step went through the slab path, which has no whole mesh
+  bool pm_mesh_valid = false;
 };
 
 // Routes the context's launches to stream `s`, whose CU mask leaves them `cus` CUs, until the end of the scope (the kernels
@@ -494,6 +508,16 @@ int direct_run_targets(ngravs_ctx *c, const double4 *d_tpm, const int *d_ttype, 
 // adaptive softening: s_soft from in_gsoft and the order, n_maxsoft bottom-up from the tree (nodes: also the node column), each
 // only when stale
 int adaptive_refresh(ngravs_ctx *c, bool nodes);
+// The strict walk for target records that are not own rows.  Reads gt_in (pos, old_acc, mass) and gt_type; counts refused records
+// (st: type outside 0..5, position not finite or outside [0, BoxSize] in a periodic run -- nothing is walked then), orders the
+// targets along the Peano curve of the engine's domain, walks and writes gt_acc (x G) / gt_nint in caller order.
+enum { GT_C_BADTYPE = 0, GT_C_BADPOS, GT_C_FAR, GT_C_FLAG, GT_C_COUNT };
+struct GravTargetsStats
+{
+  long long bad_type, bad_pos;
+};
+int grav_targets_check(ngravs_ctx *c, long long nt, GravTargetsStats *st, double *far);   // far: the largest distance of a target from the domain's centre
+int walk_targets_run(ngravs_ctx *c, long long nt, double far);
 // ---- kernels_eval.hip
 int eval_ring_slots(const WalkParams &wp, bool yuk, int waves);
 int launch_eval_ring(ngravs_ctx *c, const TreeView &tv, const WalkParams &wp, bool yuk, int nblk, int waves, int K, const int *region,
@@ -650,6 +674,8 @@ int pm_run(ngravs_ctx *c);
 int pm_deposit(ngravs_ctx *c);
 int pm_finish(ngravs_ctx *c);
 void pm_release(ngravs_ctx *c);
+// GravPM from pm_phi (pm_mesh_valid) at the targets of gt_in / gt_type -> d_out [nt][3], G included
+int pm_targets_run(ngravs_ctx *c, long long nt, double *d_out);
 // ---- kernels_pmslab.hip
 int pmslab_begin(ngravs_ctx *c, int rank, int world, int bbox[6]);
 int pmslab_pack(ngravs_ctx *c, int stage, const int *all_bbox, int64_t *send_counts, int64_t *recv_counts, void **send, void **recv);

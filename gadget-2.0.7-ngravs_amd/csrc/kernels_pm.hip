@@ -60,29 +60,16 @@ __global__ void k_green(const double2 *__restrict__ rho, double2 *__restrict__ p
     phi[(size_t)b * total + idx] = out[b];                             // k = 0 -> 0 (pm_periodic.c:519-520)
 }
 
-// fused 4-point gradient at the 8 CIC corners + CIC gather (pm_periodic.c:681-763)
-__global__ void k_gradient_gather(const double4 *__restrict__ s_pm, const unsigned char *__restrict__ s_type,
-                                  const unsigned char *__restrict__ s_flag,
-                                  long long first, long long n, double to_slab, int N, const int *__restrict__ t2g_tab,
-                                  const double *__restrict__ phi, double fac, double *__restrict__ r_pm)
+// fused 4-point gradient at the 8 CIC corners + CIC gather (pm_periodic.c:681-763) of the potential mesh `grid` at one point
+// inside [0, BoxSize]^3
+__device__ __forceinline__ void gradient_gather_point(const double *__restrict__ grid, double px, double py, double pz, double to_slab, int N,
+                                                      double fac, double (&acc)[3])
 {
-  long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-  if(i >= n)
-    return;
-  i += first;
-  if(s_flag[i] & 2)
-    {
-      r_pm[3 * i + 0] = r_pm[3 * i + 1] = r_pm[3 * i + 2] = 0.0;
-      return;
-    }
-  double4 p = s_pm[i];
-  int g = t2g_tab[s_type[i]];
   const long long NZ = N + 2;
-  const double *grid = phi + (size_t)g * N * N * NZ;
   double dx, dy, dz;
-  int sx = cell_of(p.x, to_slab, N, &dx), sy = cell_of(p.y, to_slab, N, &dy), sz = cell_of(p.z, to_slab, N, &dz);
+  int sx = cell_of(px, to_slab, N, &dx), sy = cell_of(py, to_slab, N, &dy), sz = cell_of(pz, to_slab, N, &dz);
   double wx[2] = {1.0 - dx, dx}, wy[2] = {1.0 - dy, dy}, wz[2] = {1.0 - dz, dz};
-  double acc[3] = {0, 0, 0};
+  acc[0] = acc[1] = acc[2] = 0;
   auto wrap = [N](int a) { return a < 0 ? a + N : (a >= N ? a - N : a); };
   auto at = [&](int x, int y, int z) { return grid[((long long)x * N + y) * NZ + z]; };
   // corner order of the reference's gather (x outer, then y/z as written at pm_periodic.c:749-757)
@@ -101,9 +88,50 @@ __global__ void k_gradient_gather(const double4 *__restrict__ s_pm, const unsign
       acc[1] += fyv * w;
       acc[2] += fzv * w;
     }
+}
+
+// ... for the engine's own rows [first, first + n)
+__global__ void k_gradient_gather(const double4 *__restrict__ s_pm, const unsigned char *__restrict__ s_type,
+                                  const unsigned char *__restrict__ s_flag,
+                                  long long first, long long n, double to_slab, int N, const int *__restrict__ t2g_tab,
+                                  const double *__restrict__ phi, double fac, double *__restrict__ r_pm)
+{
+  long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+  if(i >= n)
+    return;
+  i += first;
+  if(s_flag[i] & 2)
+    {
+      r_pm[3 * i + 0] = r_pm[3 * i + 1] = r_pm[3 * i + 2] = 0.0;
+      return;
+    }
+  double4 p = s_pm[i];
+  int g = t2g_tab[s_type[i]];
+  double acc[3];
+  gradient_gather_point(phi + (size_t)g * N * N * (N + 2), p.x, p.y, p.z, to_slab, N, fac, acc);
   r_pm[3 * i + 0] = acc[0];
   r_pm[3 * i + 1] = acc[1];
   r_pm[3 * i + 2] = acc[2];
+}
+
+// ... and for target records handed in (ngravs_pm_targets): positions [nt][3] inside [0, BoxSize]^3 and types 0..5, both checked
+// by the caller; the target's species reads its own potential mesh
+struct TypeToGrav
+{
+  int g[NGRAVS_NTYPES];
+};
+__global__ void k_gradient_gather_targets(const double *__restrict__ tpos, const int *__restrict__ ttype, long long nt, double to_slab, int N,
+                                          TypeToGrav t2g, const double *__restrict__ phi, double fac, double *__restrict__ out)
+{
+  const long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+  if(t >= nt)
+    return;
+  const int g = t2g.g[ttype[t]];
+  double acc[3];
+  gradient_gather_point(phi + (size_t)g * N * N * (N + 2), tpos[3 * t], tpos[3 * t + 1], tpos[3 * t + 2], to_slab, N, fac, acc);
+  out[3 * t + 0] = acc[0];
+  out[3 * t + 1] = acc[1];
+  out[3 * t + 2] = acc[2];
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -429,6 +457,7 @@ int pm_deposit(ngravs_ctx *c)
       return NGRAVS_ERR_ARG;
     }
   const size_t real_elems = (size_t)N * N * (N + 2);
+  c->pm_mesh_valid = false;   // a new PM step: pm_phi is rewritten (and may move) before pm_finish has it complete again
   if(c->pm_rho.ensure(real_elems * ng) || c->pm_phi.ensure(real_elems * ng) || c->r_pm.ensure(3 * n) || c->d_counters.ensure(16))
     return NGRAVS_ERR_NOMEM;
   if(c->pm_plan_n != N)
@@ -545,6 +574,22 @@ int pm_finish(ngravs_ctx *c)
                        (long long)c->shard_count, to_slab, N, c->d_counters.p + 8, c->pm_phi.p, fac, c->r_pm.p);
   HIP_TRY(c, hipGetLastError());
   c->have_pm = true;
+  c->pm_mesh_valid = true;   // pm_phi: the complete potential of every target species, until the next deposit
+  return NGRAVS_OK;
+}
+
+int pm_targets_run(ngravs_ctx *c, long long nt, double *d_out)
+{
+  const int N = c->cfg.pmgrid;
+  const double L = c->cfg.box_size;
+  double fac = c->cfg.G / (M_PI * L);      // pm_periodic.c:237-238, as pm_finish
+  fac *= 1 / (2 * L / N);
+  TypeToGrav t2g;
+  for(int t = 0; t < NGRAVS_NTYPES; t++)
+    t2g.g[t] = c->cfg.type_to_grav[t];
+  hipLaunchKernelGGL(k_gradient_gather_targets, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, c->stream, c->gt_in.p, c->gt_type.p, nt, N / L, N,
+                     t2g, c->pm_phi.p, fac, d_out);
+  HIP_TRY(c, hipGetLastError());
   return NGRAVS_OK;
 }
 

@@ -497,6 +497,7 @@ int pmslab_begin(ngravs_ctx *c, int rank, int world, int bbox[6])
       ngravs_report(c, NGRAVS_ERR_ARG, "slab PM needs PERIODIC, PMGRID and at most PMGRID/2 tasks");
       return NGRAVS_ERR_ARG;
     }
+  c->pm_mesh_valid = false;   // this PM step's potential lives in the tasks' slabs: pm_phi (if any) is an older step's
   s.world = world;
   s.rank = rank;
   s.N = N;

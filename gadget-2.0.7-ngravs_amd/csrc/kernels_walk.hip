@@ -13,6 +13,8 @@
 //      that node's subtree (`lane_skip`: a stack depth).  Interaction set, interaction count and
 //      summation order per target equal the reference's (children are visited in Peano instead
 //      of Morton order, which only reorders the fp64 sum).
+//      k_walk_targets is the same walk (one body, strict_walk_lane) for target records that are
+//      not particles of the tree (ngravs_gravity_tree_targets; gravtree.c:133-285).
 //
 //  k_walk_group2 : the MI355X production walk, as a traversal kernel (MODE 1), an evaluation kernel (MODE 2) or both in
 //      one (MODE 0).  Traversal: the 64 lanes work cooperatively -- a LIFO of pending nodes is popped 64 at a time, each
@@ -247,39 +249,18 @@ __device__ __forceinline__ void lat_lookup(const double *__restrict__ t3, double
 // =============================================================================================
 #pragma clang fp contract(off)
 
+// One lane's walk, for a target given by value (StrictTarget, walk_device.hpp): the one body of k_walk_strict (the engine's own
+// rows) and k_walk_targets (records handed in).  sn / ss: the wave's node and slot stack in LDS.  A lane that is not `valid` walks
+// along without taking part.
 // ADA: adaptive softening for gas (forcetree.c:1398-1413, :1503-1516 / :1745-1760, :1928-1941): tv.soft, tv.maxsoft
-template <int NG, bool PM, bool LATT, bool USER = false, bool ADA = false>   // USER: tree-only wirings with a user-defined law
-__global__ __launch_bounds__(256) void k_walk_strict(TreeView tv, const double4 *__restrict__ s_pm,
-                                                     const unsigned char *__restrict__ s_type,
-                                                     const double *__restrict__ s_oldacc,
-                                                     const unsigned char *__restrict__ s_active,
-                                                     const double *__restrict__ table, WalkParams wp, LawIds li,
-                                                     long long t_first, long long t_count,
-                                                     double *__restrict__ r_acc, int *__restrict__ r_nint, int *__restrict__ err_flag)
+template <int NG, bool PM, bool LATT, bool USER, bool ADA>   // USER: tree-only wirings with a user-defined law
+__device__ __forceinline__ void strict_walk_lane(const TreeView &tv, const double4 *__restrict__ s_pm, const unsigned char *__restrict__ s_type,
+                                                 const double *__restrict__ table, const WalkParams &wp, const LawIds &li, const bool valid,
+                                                 const StrictTarget &T, int *sn, int *ss, int *__restrict__ err_flag, double (&acc)[3],
+                                                 int &nint_out)
 {
-  __shared__ int st_node[4][MAX_LEVELS + 2], st_slot[4][MAX_LEVELS + 2];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const long long grp = (long long)blockIdx.x * 4 + wave;
-  const long long ti = t_first + grp * WAVE + lane;
-  const bool valid = (grp * WAVE + lane) < t_count && (s_active[ti < t_first + t_count ? ti : t_first] & 1) != 0;
-  if(grp * WAVE >= t_count)
-    return;
-  double px = 0, py = 0, pz = 0, aold = 0, hT = 0, pmass = 1.0;
-  int ptype = 0, tg = 0;
-  if(valid)
-    {
-      double4 p = s_pm[ti];
-      px = p.x;
-      py = p.y;
-      pz = p.z;
-      pmass = p.w;
-      ptype = s_type[ti];
-      tg = wp.t2g[ptype];
-      hT = wp.fsoft[ptype];
-      if constexpr(ADA)
-        hT = tv.soft[ti];
-      aold = wp.errtol_acc * s_oldacc[ti];
-    }
+  const double px = T.x, py = T.y, pz = T.z, aold = T.aold, hT = T.h, pmass = T.mass;
+  const int tg = T.tg;
   double ax = 0, ay = 0, az = 0;
   int nint = 0;
   // The wave walks the tree in lock-step; a lane that has dealt with a node (used it, or pruned it) while another lane wants it
@@ -288,7 +269,6 @@ __global__ __launch_bounds__(256) void k_walk_strict(TreeView tv, const double4 
   // particle indices cannot tell from "behind the subtree".)
   const int NO_SKIP = 0x7fffffff;
   int lane_skip = valid ? NO_SKIP : -1;
-  int *sn = st_node[wave], *ss = st_slot[wave];
   int sp = -1;
 
   // one source (particle or one species of a node): forcetree.c:1534-1583 / :1953-2032
@@ -608,12 +588,99 @@ __global__ __launch_bounds__(256) void k_walk_strict(TreeView tv, const double4 
       };
       dfs(lat_visit, lat_particle);
     }
+  acc[0] = ax;
+  acc[1] = ay;
+  acc[2] = az;
+  nint_out = nint;
+}
+
+// targets: the engine's own Peano-ordered rows [t_first, t_first + t_count), 64 consecutive rows per wave
+template <int NG, bool PM, bool LATT, bool USER = false, bool ADA = false>
+__global__ __launch_bounds__(256) void k_walk_strict(TreeView tv, const double4 *__restrict__ s_pm,
+                                                     const unsigned char *__restrict__ s_type,
+                                                     const double *__restrict__ s_oldacc,
+                                                     const unsigned char *__restrict__ s_active,
+                                                     const double *__restrict__ table, WalkParams wp, LawIds li,
+                                                     long long t_first, long long t_count,
+                                                     double *__restrict__ r_acc, int *__restrict__ r_nint, int *__restrict__ err_flag)
+{
+  __shared__ int st_node[4][MAX_LEVELS + 2], st_slot[4][MAX_LEVELS + 2];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const long long grp = (long long)blockIdx.x * 4 + wave;
+  const long long ti = t_first + grp * WAVE + lane;
+  const bool valid = (grp * WAVE + lane) < t_count && (s_active[ti < t_first + t_count ? ti : t_first] & 1) != 0;
+  if(grp * WAVE >= t_count)
+    return;
+  StrictTarget T = {0, 0, 0, 0, 0, 1.0, 0};
   if(valid)
     {
-      r_acc[3 * ti + 0] = ax;
-      r_acc[3 * ti + 1] = ay;
-      r_acc[3 * ti + 2] = az;
+      double4 p = s_pm[ti];
+      T.x = p.x;
+      T.y = p.y;
+      T.z = p.z;
+      T.mass = p.w;
+      const int ptype = s_type[ti];
+      T.tg = wp.t2g[ptype];
+      T.h = wp.fsoft[ptype];
+      if constexpr(ADA)
+        T.h = tv.soft[ti];
+      T.aold = wp.errtol_acc * s_oldacc[ti];
+    }
+  double acc[3];
+  int nint;
+  strict_walk_lane<NG, PM, LATT, USER, ADA>(tv, s_pm, s_type, table, wp, li, valid, T, st_node[wave], st_slot[wave], err_flag, acc, nint);
+  if(valid)
+    {
+      r_acc[3 * ti + 0] = acc[0];
+      r_acc[3 * ti + 1] = acc[1];
+      r_acc[3 * ti + 2] = acc[2];
       r_nint[ti] = nint;
+    }
+}
+
+// targets: records handed in (ngravs_gravity_tree_targets; the reference's force_treeevaluate(j, 1) / _shortrange(j, 1) for one
+// task, gravtree.c:133-285): position [nt][3], OldAcc, mass and type columns in the caller's order, visited in
+// the order ord (the caller's indices along the Peano curve, so that the 64 lanes of a wave are neighbours in space).  Results
+// x G go to the caller's index.  Writes nothing of the engine's own walk.
+template <int NG, bool PM, bool LATT, bool USER>
+__global__ __launch_bounds__(256) void k_walk_targets(TreeView tv, const double4 *__restrict__ s_pm,
+                                                      const unsigned char *__restrict__ s_type,
+                                                      const double *__restrict__ table, WalkParams wp, LawIds li,
+                                                      const double *__restrict__ t_pos, const double *__restrict__ t_oldacc,
+                                                      const double *__restrict__ t_mass, const int *__restrict__ t_type,
+                                                      const unsigned int *__restrict__ ord, long long nt, double G,
+                                                      double *__restrict__ o_acc, int *__restrict__ o_nint, int *__restrict__ err_flag)
+{
+  __shared__ int st_node[4][MAX_LEVELS + 2], st_slot[4][MAX_LEVELS + 2];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const long long grp = (long long)blockIdx.x * 4 + wave;
+  const long long t = grp * WAVE + lane;
+  if(grp * WAVE >= nt)
+    return;
+  const bool valid = t < nt;
+  StrictTarget T = {0, 0, 0, 0, 0, 1.0, 0};
+  long long me = 0;
+  if(valid)
+    {
+      me = ord[t];
+      T.x = t_pos[3 * me];
+      T.y = t_pos[3 * me + 1];
+      T.z = t_pos[3 * me + 2];
+      T.mass = t_mass[me];
+      const int ptype = t_type[me];
+      T.tg = wp.t2g[ptype];
+      T.h = wp.fsoft[ptype];
+      T.aold = wp.errtol_acc * t_oldacc[me];
+    }
+  double acc[3];
+  int nint;
+  strict_walk_lane<NG, PM, LATT, USER, false>(tv, s_pm, s_type, table, wp, li, valid, T, st_node[wave], st_slot[wave], err_flag, acc, nint);
+  if(valid)
+    {
+      o_acc[3 * me + 0] = acc[0] * G;   // gravtree.c:332-334
+      o_acc[3 * me + 1] = acc[1] * G;
+      o_acc[3 * me + 2] = acc[2] * G;
+      o_nint[me] = nint;
     }
 }
 
@@ -2491,6 +2558,75 @@ static int launch_strict(Row<NG, PM, LATT, USER, ADA>, ngravs_ctx *c, const Walk
   return NGRAVS_OK;
 }
 
+// ---- the strict walk for targets that are not own rows (ngravs_gravity_tree_targets) ------------------------------------------------
+// one thread per target record: counts what the call refuses, notes the farthest target (a user-defined law is tabulated out to
+// it), and clamps the position to the domain cube for the Peano key only -- a foreign target may lie outside the cube of the
+// engine's own particles
+__global__ void k_grav_tg_prep(const double *__restrict__ tpos, const int *__restrict__ ttype, long long nt, int periodic, double box,
+                               double cx, double cy, double cz, double len, double mx, double my, double mz,
+                               double *__restrict__ clamped, unsigned int *__restrict__ iota, unsigned long long *__restrict__ counters)
+{
+  const long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+  if(t >= nt)
+    return;
+  const double BIG = 1e300;
+  const double corner[3] = {cx, cy, cz}, mid[3] = {mx, my, mz};
+  bool bad = false;
+  double d2 = 0;
+  for(int k = 0; k < 3; k++)
+    {
+      const double x = tpos[3 * t + k];
+      if(!(fabs(x) < BIG) || (periodic && !(x >= 0 && x <= box)))
+        bad = true;
+      d2 += (x - mid[k]) * (x - mid[k]);
+      // inside the cube with a cell to spare: (x - corner) * DomainFac stays below 2^TREE_BITS
+      clamped[3 * t + k] = fmin(fmax(x, corner[k]), corner[k] + len * (1 - 1e-6));
+    }
+  if(bad)
+    atomicAdd(&counters[GT_C_BADPOS], 1ull);
+  else
+    atomicMax(&counters[GT_C_FAR], (unsigned long long)__double_as_longlong(sqrt(d2)));   // (non-negative doubles order as their bits do)
+  if(ttype[t] < 0 || ttype[t] >= NGRAVS_NTYPES)
+    atomicAdd(&counters[GT_C_BADTYPE], 1ull);
+  iota[t] = (unsigned int)t;
+}
+
+int grav_targets_check(ngravs_ctx *c, long long nt, GravTargetsStats *st, double *far)
+{
+  if(c->gt_counters.ensure(GT_C_COUNT) || c->gt_ord.ensure(2 * (size_t)nt))
+    return NGRAVS_ERR_NOMEM;
+  HIP_TRY(c, hipMemsetAsync(c->gt_counters.p, 0, GT_C_COUNT * sizeof(unsigned long long), c->stream));
+  hipLaunchKernelGGL(k_grav_tg_prep, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, c->stream, c->gt_in.p, c->gt_type.p, nt, c->cfg.periodic,
+                     c->cfg.box_size, c->dom[0], c->dom[1], c->dom[2], c->dom[6], c->dom[3], c->dom[4], c->dom[5], c->gt_in.p + 5 * nt,
+                     c->gt_ord.p, c->gt_counters.p);
+  HIP_TRY(c, hipGetLastError());
+  unsigned long long h[GT_C_COUNT];
+  HIP_TRY(c, hipMemcpyAsync(h, c->gt_counters.p, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  st->bad_type = (long long)h[GT_C_BADTYPE];
+  st->bad_pos = (long long)h[GT_C_BADPOS];
+  long long bits = (long long)h[GT_C_FAR];
+  memcpy(far, &bits, sizeof(double));
+  return NGRAVS_OK;
+}
+
+template <int NG, int PM, int LATT, int USER, int ADA>
+static int launch_strict_targets(Row<NG, PM, LATT, USER, ADA>, ngravs_ctx *c, const WalkParams &wp, const LawIds &li, long long nt,
+                                 const unsigned int *ord)
+{
+  if constexpr(ADA)
+    return NGRAVS_ERR_STATE;   // (refused by the caller: explicit targets carry no softening length)
+  else
+    {
+      const long long ngroups = (nt + WAVE - 1) / WAVE;
+      const unsigned nb = (unsigned)((ngroups + 3) / 4);
+      hipLaunchKernelGGL((k_walk_targets<NG, PM, LATT, USER>), dim3(nb), dim3(256), 0, c->stream, tree_view(c), c->s_pm.p, c->s_type.p,
+                         LATT ? c->lat.p : c->table.p, wp, li, c->gt_in.p, c->gt_in.p + 3 * nt, c->gt_in.p + 4 * nt, c->gt_type.p, ord, nt, c->cfg.G,
+                         c->gt_acc.p, c->gt_nint.p, reinterpret_cast<int *>(c->gt_counters.p + GT_C_FLAG));
+      return NGRAVS_OK;
+    }
+}
+
 // targets of the group walk: all particles of the shard, or the compacted active ones (walk_select_targets)
 static inline long long walk_tcount(const ngravs_ctx *c) { return c->walk_ntargets >= 0 ? c->walk_ntargets : c->shard_count; }
 static inline const int *walk_tlist(const ngravs_ctx *c) { return c->walk_ntargets >= 0 ? c->walk_tlist.p : nullptr; }
@@ -3170,6 +3306,45 @@ int walk_finish(ngravs_ctx *c)
   hipLaunchKernelGGL(k_finish, dim3(nb), dim3(bs), 0, c->stream, (long long)c->shard_first, (long long)c->shard_count,
                      c->s_active.p, c->r_acc.p, c->r_pm.p, c->r_oldacc.p, c->cfg.G, (c->have_pm && c->cfg.pmgrid) ? 1 : 0,
                      c->r_nint.p, c->red_tmp.p);
+  HIP_TRY(c, hipGetLastError());
+  return NGRAVS_OK;
+}
+
+// ngravs_gravity_tree_targets: the targets that grav_targets_check passed, ordered along the Peano curve of the engine's domain
+// (the wave moves in lock-step: 64 targets far apart cost the union of their walks), walked by k_walk_targets
+int walk_targets_run(ngravs_ctx *c, long long nt, double far)
+{
+  if(c->gt_key.ensure(2 * (size_t)nt) || c->gt_acc.ensure(3 * (size_t)nt) || c->gt_nint.ensure((size_t)nt))
+    return NGRAVS_ERR_NOMEM;
+  const bool latt = c->cfg.periodic && !c->cfg.pmgrid, pm = c->cfg.pmgrid != 0;
+  int rc;
+  if(latt && (rc = ensure_lattice(c)))
+    return rc;
+  // a tree-only walk without periodic boundaries evaluates a law out to its farthest target, which may lie outside the cube
+  if((rc = user_tables_ensure(c, latt ? lattice_reach(c) : fmax(user_reach(c), pm ? 0.0 : 1.25 * (far + 0.5 * sqrt(3.0) * c->dom[6])))))
+    return rc;
+  WalkParams wp;
+  make_walk_params(c, &wp);
+  LawIds li;
+  make_law_ids(c, &li);
+  const unsigned int *ord = c->gt_ord.p;   // 0 .. nt-1 (k_grav_tg_prep)
+  if(c->tune.walk_tg_sort)
+    {
+      const double fac21 = c->dom[7] * (double)(1 << (TREE_BITS - NGRAVS_BITS_PER_DIMENSION));
+      if((rc = dom_keys_only(c, c->gt_in.p + 5 * nt, nt, c->dom, fac21, TREE_BITS, reinterpret_cast<long long *>(c->gt_key.p))))
+        return rc;
+      size_t bytes = 0;
+      HIP_TRY(c, hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, c->gt_key.p, c->gt_key.p + nt, c->gt_ord.p, c->gt_ord.p + nt, (int)nt, 0,
+                                                    3 * TREE_BITS, c->stream));
+      if(c->gt_tmp.ensure(bytes))
+        return NGRAVS_ERR_NOMEM;
+      HIP_TRY(c, hipcub::DeviceRadixSort::SortPairs(c->gt_tmp.p, bytes, c->gt_key.p, c->gt_key.p + nt, c->gt_ord.p, c->gt_ord.p + nt, (int)nt, 0,
+                                                    3 * TREE_BITS, c->stream));
+      ord = c->gt_ord.p + nt;
+    }
+  const int key[] = {c->cfg.n_gravs, pm, latt, wp.user != 0, 0};
+  if((rc = dispatch(c, StrictRows{}, key, [&](auto row) { return launch_strict_targets(row, c, wp, li, nt, ord); })))
+    return rc;
   HIP_TRY(c, hipGetLastError());
   return NGRAVS_OK;
 }

@@ -40,6 +40,15 @@ __device__ __forceinline__ double exp_neg_fast(double x, const double *__restric
   return ldexp(t * pz, -(mi >> 5));
 }
 
+// What the strict walk knows of its target (the reference's walk reads the same of P[target] or of GravDataGet[target],
+// forcetree.c:1284-1313 / :1668-1695): position, ErrTolForceAcc * OldAcc, the softening length of its type (ADA: its own), its mass
+// (read by the BAM laws alone) and its species
+struct StrictTarget
+{
+  double x, y, z, aold, h, mass;
+  int tg;
+};
+
 // wave-level "any lane": the condition's lane mask is compared on the scalar unit (no vector select / compare round trip)
 __device__ __forceinline__ bool wave_any(bool p) { return __builtin_amdgcn_ballot_w64(p) != 0ull; }
 __device__ __forceinline__ void wave_sync()

@@ -266,6 +266,7 @@ int ngravs_get_config(ngravs_ctx *ctx, ngravs_config_t *out);
  *   "sort_full" 1: Peano order by one radix sort on all key bits (default: top 28 to 42 bits + fix-up of the ties, the same order)
  *   "dd_keep" f: decompositions are kept over several steps (ngravs_host_kept_step): leaves are imported for ALL own particles as
  *       targets, whose cells may have grown by f x the domain's side (0 <= f <= 0.25; default 0: import for this step's active targets)
+ *   "walk_tg_sort" 0: ngravs_gravity_tree_targets walks its targets in the caller's order, not along the Peano curve (same results)
  *   "sph_verbose" 1: the SPH density call prints one line of iteration statistics (targets, rounds, candidates, neighbours) to stdout,
  *       the SPH hydro call one line (targets, candidates tested, pairs evaluated)
  * Returns NGRAVS_ERR_ARG for an unknown name or a value out of range. */
@@ -387,6 +388,47 @@ int ngravs_direct_sum(ngravs_ctx *ctx, const int32_t *idx, int64_t nt, double *a
  * this task OWNS (not its imported copies).  Every task calls it with the test particles of ALL tasks and the host adds the
  * partial sums up (MPI_Allreduce / ncclAllReduce).  xG, lattice correction included when PERIODIC. */
 int ngravs_direct_sum_targets(ngravs_ctx *ctx, const double *pos, const double *mass, const int32_t *type, int64_t nt, double *acc);
+
+/* ---- gravity for targets that are not the engine's own particles ----------------------------------------
+ * The reference walks its tree for particles imported from other tasks (force_treeevaluate(j, 1), force_treeevaluate_shortrange(j, 1),
+ * force_treeevaluate_lattice_correction(j, 1), gravtree.c:133-285): a target is given by value -- position, type,
+ * OldAcc and mass (forcetree.c:1299-1313, :1683-1695) -- and need not be a particle of the tree.  The same here for one task: test
+ * particles, tracers, map pixels, or the particles of another engine (the force on a set split over engines is the sum of every
+ * engine's force at the targets).  The targets are no sources, the tree, the engine's own accelerations, costs and walk statistics
+ * are not modified: ngravs_get_accel() returns afterwards what it returned before. */
+typedef struct
+{
+  const double *pos;
+  int64_t pos_stride;          /* 3 doubles per target; strides in bytes                                */
+  const int32_t *type;
+  int64_t type_stride;         /* 0..5                                                                  */
+  const double *old_acc;
+  int64_t old_acc_stride;      /* P[].OldAcc of the target; may be NULL: 0 for every target             */
+  const double *mass;
+  int64_t mass_stride;         /* may be NULL: 1.0; only the BAM laws read it (ngravs.c:495-668)        */
+  int32_t on_device;           /* all pointers, results included, are device pointers (else host)       */
+} ngravs_grav_targets_t;
+/* The strict walk (the reference's semantics per target, whatever walk mode the engine is in) of the built tree for nt targets in
+ * any order: every node the target's own criterion accepts is used, every opened node is followed, counts as
+ * forcetree.c:1244-1610 / :1623-2052 / :2077-2455.  TreePM configurations give the short-range force, periodic tree-only ones add
+ * the lattice-correction walk.  The criterion is the context's current one (ngravs_set_opening): Barnes-Hut when err_tol_theta != 0,
+ * else the relative criterion with the target's old_acc -- with old_acc = 0 it opens every node that has mass.  A source at the
+ * target's position contributes no force and counts as an interaction.  acc[3*nt] xG and nint[nt] (may be NULL), contiguous, in
+ * the caller's order; kernel_ms (may be NULL): device time of ordering the targets along the Peano curve and walking them.
+ * NGRAVS_ERR_ARG for a NULL ctx.  Refused with a message in ngravs_last_error() and nothing written: NGRAVS_ERR_ARG for a NULL
+ * targets, pos, type or acc, nt < 0, a type outside 0..5, a position that is not finite or, in a periodic configuration, has a
+ * coordinate outside [0, BoxSize] (elsewhere any finite position is served, also outside the domain cube); NGRAVS_ERR_STATE "single
+ * task only" with world_size > 1 or a multi-task working set (the reference's short-cuts for top-level nodes, forcetree.c:1424-1434,
+ * :1522-1526, are not implemented), with adaptive gas softening on (as ngravs_direct_sum_targets), and without a built tree of the
+ * current particle set (after ngravs_update_particles the tree is refit first).  nt = 0 is NGRAVS_OK. */
+int ngravs_gravity_tree_targets(ngravs_ctx *ctx, const ngravs_grav_targets_t *targets, int64_t nt, double *acc, int32_t *nint,
+                                double *kernel_ms);
+/* GravPM at nt targets: the 4-point gradient and CIC read-back (pm_periodic.c:681-763) of the potential meshes the last
+ * ngravs_pmforce_periodic() of this task left, each target reading the mesh of its species; grav_pm[3*nt], G included, exactly as
+ * GravPM is delivered.  old_acc and mass are not read.  The mesh stays valid across steps without PM, as P[].GravPM does, until the
+ * next PM step rewrites it.  Refusals as above; NGRAVS_ERR_STATE also for PMGRID = 0 and without a valid mesh (no PM step yet, or
+ * the last one ran over the slab-decomposed mesh). */
+int ngravs_pm_targets(ngravs_ctx *ctx, const ngravs_grav_targets_t *targets, int64_t nt, double *grav_pm);
 
 /* ---- multi-task domain decomposition ------------------------------------------------------------------
  * The role of domain_decompose()/domain_exchangeParticles() (domain.c:164-330, 554-760) and of the target export of
