@@ -44,6 +44,8 @@ EXPORTS = [
     "ngravs_sph_density", "ngravs_sph_kernel", "ngravs_sph_hydro", "ngravs_sph_accelerations",
     "ngravs_sph_hsml_guess", "ngravs_sph_density_sums", "ngravs_sph_hydro_sums", "ngravs_sph_density_update",
     "ngravs_gravity_tree_targets", "ngravs_pm_targets",
+    "ngravs_time_tables", "ngravs_time_factors", "ngravs_next_sync_point", "ngravs_move_particles", "ngravs_displacement_sums",
+    "ngravs_dt_displacement", "ngravs_advance_and_find_timesteps",
 ]
 # include/ngravs_host.h (plain-C multi-task drivers over a communicator vtable, linked into the same library)
 HOST_EXPORTS = ["ngravs_host_comm_selftest", "ngravs_host_kept_step", "ngravs_host_toptree_borrow", "ngravs_host_domain_decomposition", "ngravs_host_domain_owners", "ngravs_host_domain_halo",
@@ -142,6 +144,13 @@ def lib():
         L.ngravs_sph_density_update.restype = C.c_int64
         L.ngravs_gravity_tree_targets.argtypes = abi.GRAVITY_TREE_TARGETS_ARGTYPES
         L.ngravs_pm_targets.argtypes = abi.PM_TARGETS_ARGTYPES
+        L.ngravs_time_tables.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ngravs_time_factors.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+        L.ngravs_next_sync_point.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+        L.ngravs_move_particles.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
+        L.ngravs_displacement_sums.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ngravs_dt_displacement.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p]
+        L.ngravs_advance_and_find_timesteps.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -233,6 +242,39 @@ def hydro_factors(time, omega0, omega_lambda, hubble, gamma=5.0 / 3):
     fac_mu = np.power(time, 3 * (gamma - 1) / 2) / time
     fac_vsic_fix = hubble_a * np.power(time, 3 * (gamma - 1))
     return float(hubble_a2), float(fac_mu), float(fac_vsic_fix)
+
+
+def time_tables(par, rule=0):
+    """init_drift_table() of the reference (driftfac.c:26-60) for the cosmology and the time span of par
+    (abi.make_time_params): (drift, gravkick, hydrokick), abi.DRIFT_TABLE_LENGTH float64 each.  rule 0: the library's rule,
+    1: its finer check rule.  No GPU needed."""
+    t = [np.zeros(abi.DRIFT_TABLE_LENGTH) for _ in range(3)]
+    rc = lib().ngravs_time_tables(C.byref(par), int(rule), *(x.ctypes.data for x in t))
+    if rc != 0:
+        raise NgravsError("ngravs_time_tables: %d" % rc)
+    return tuple(t)
+
+
+def time_factors(par, ti0, ti1):
+    """(get_drift_factor, get_gravkick_factor, get_hydrokick_factor)(ti0, ti1) (driftfac.c:67-174) from the tables in par; no
+    GPU needed"""
+    out = np.zeros(3)
+    rc = lib().ngravs_time_factors(C.byref(par), int(ti0), int(ti1), out.ctypes.data)
+    if rc != 0:
+        raise NgravsError("ngravs_time_factors: %d" % rc)
+    return tuple(float(x) for x in out)
+
+
+def dt_displacement(par, sums, G, asmth, time):
+    """find_dt_displacement_constraint() after its sums (timestep.c:595-659); asmth = All.Asmth[0], 0 without a mesh; time =
+    All.Time.  No GPU needed."""
+    sums = np.ascontiguousarray(sums, dtype=np.float64)
+    assert sums.shape == (18,)
+    out = C.c_double(0)
+    rc = lib().ngravs_dt_displacement(C.byref(par), sums.ctypes.data, float(G), float(asmth), float(time), C.byref(out))
+    if rc != 0:
+        raise NgravsError("ngravs_dt_displacement: %d" % rc)
+    return float(out.value)
 
 
 def _ptr(a):
@@ -780,6 +822,74 @@ class Engine:
         del keep
         return pm
 
+    # -- time integration: the stations of run.c:32-65 around the forces ------------------------------------------------------
+    @staticmethod
+    def _time_cols(cols):
+        """abi.TimeCols for a dict of columns by the names of abi.TIME_COL_NAMES: numpy arrays (C-contiguous, float64 / int32:
+        they are written through) or contiguous torch tensors on the device, all of one kind; [n,3] for the vectors, [n] else"""
+        given = {k: a for k, a in cols.items() if a is not None}
+        unknown = set(given) - set(abi.TIME_COL_NAMES)
+        if unknown:
+            raise TypeError("unknown columns %s" % sorted(unknown))
+        first = next(iter(given.values()))
+        on_device, n = _is_device(first), int(first.shape[0])
+        shapes = {k: (n, 3) if k in abi.TIME_VEC_COLS else (n,) for k in given}
+        chk, addr = _columns(given, shapes, on_device, int_keys=abi.TIME_INT_COLS, own=tuple(given))
+        tc = abi.TimeCols()
+        _set_columns(tc, chk, addr)
+        tc.n, tc.on_device = n, int(on_device)
+        return tc, chk
+
+    def time_tables(self, par, rule=0):
+        return time_tables(par, rule)
+
+    def asmth(self):
+        """All.Asmth[0] of the configuration (pm_periodic.c:59), 0 without a mesh"""
+        if self.cfg.pmgrid <= 0:
+            return 0.0
+        return self.cfg.asmth if self.cfg.asmth > 0 else abi.ASMTH * self.cfg.box_size / self.cfg.pmgrid
+
+    def next_sync_point(self, ti_endstep, pm_ti_endstep=None):
+        """run.c:161-191: (ti_next, full_step, n_active) from the Ti_endstep column (int32 [n]; numpy or a device tensor);
+        pm_ti_endstep: All.PM_Ti_endstep, or None without a mesh"""
+        tc, keep = self._time_cols(dict(ti_endstep=ti_endstep))
+        out = abi.SyncPoint()
+        self._check(lib().ngravs_next_sync_point(self._h, C.byref(tc), -1 if pm_ti_endstep is None else int(pm_ti_endstep), C.byref(out)),
+                    "ngravs_next_sync_point")
+        return int(out.ti_next), bool(out.full_step), int(out.n_active)
+
+    def move_particles(self, cols, par, time0, time1, wrap=False):
+        """move_particles(time0, time1) of the reference (predict.c:31-76) on the caller's columns, IN PLACE: cols is a dict by
+        the names of abi.TIME_COL_NAMES -- type, pos, vel, and for gas vel_pred, grav_accel, grav_pm (with a mesh), hydro_accel,
+        density, hsml, pressure, div_vel, entropy, dt_entropy, ti_begstep, ti_endstep.  wrap: do_box_wrapping() afterwards."""
+        tc, keep = self._time_cols(cols)
+        self._check(lib().ngravs_move_particles(self._h, C.byref(tc), C.byref(par), int(time0), int(time1), int(bool(wrap))),
+                    "ngravs_move_particles")
+
+    def displacement_sums(self, ptype, vel, mass):
+        """the 18 local sums of find_dt_displacement_constraint (timestep.c:606-612): per type the sum of |v|^2, the smallest
+        mass, the count"""
+        tc, keep = self._time_cols(dict(type=ptype, vel=vel, mass=mass))
+        sums = np.zeros(18)
+        self._check(lib().ngravs_displacement_sums(self._h, C.byref(tc), sums.ctypes.data), "ngravs_displacement_sums")
+        return sums
+
+    def dt_displacement(self, par, sums, time):
+        """the displacement constraint from the (all-reduced) sums, with the configuration's G and Asmth"""
+        return dt_displacement(par, sums, self.cfg.G, self.asmth(), time)
+
+    def advance_and_find_timesteps(self, cols, par, ti_current, dt_displacement, pm_ti=None):
+        """advance_and_find_timesteps() of the reference (timestep.c:24-413) on the caller's columns, IN PLACE, for the rows with
+        ti_endstep == ti_current: cols holds type, vel, ti_begstep, ti_endstep, grav_accel, grav_pm (with a mesh), and for gas
+        vel_pred, hydro_accel, entropy, dt_entropy, density, hsml, max_signal_vel.  pm_ti: [PM_Ti_begstep, PM_Ti_endstep] with a
+        mesh.  Returns (rows advanced, the new pm_ti or None)."""
+        tc, keep = self._time_cols(cols)
+        pm = (C.c_int32 * 2)(*[int(x) for x in pm_ti]) if pm_ti is not None else None
+        kicked = C.c_int64(0)
+        self._check(lib().ngravs_advance_and_find_timesteps(self._h, C.byref(tc), C.byref(par), int(ti_current), float(dt_displacement), pm,
+                                                            C.byref(kicked)), "ngravs_advance_and_find_timesteps")
+        return int(kicked.value), (None if pm is None else [int(pm[0]), int(pm[1])])
+
     def direct_sum(self, idx):
         idx = np.ascontiguousarray(idx, dtype=np.int32)
         out = np.zeros((len(idx), 3))
@@ -787,3 +897,4 @@ class Engine:
         return out
 
 from . import sph_split  # noqa: E402,F401  (uses NgravsError and sph_density_update above)
+from . import timeline  # noqa: E402,F401

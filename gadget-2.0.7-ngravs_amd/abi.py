@@ -207,6 +207,55 @@ SPH_DENSITY_UPDATE_ARGTYPES = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.
 
 GRAV_TARGET_NAMES = ("pos", "type", "old_acc", "mass")
 
+# ---- time integration (ngravs_next_sync_point ... ngravs_advance_and_find_timesteps) ----
+TIMEBASE = 1 << 28
+DRIFT_TABLE_LENGTH = 1000
+TIME_COL_NAMES = ("type", "pos", "vel", "mass", "ti_begstep", "ti_endstep", "grav_accel", "grav_pm", "vel_pred", "hydro_accel", "entropy",
+                  "dt_entropy", "density", "hsml", "pressure", "div_vel", "max_signal_vel")
+TIME_INT_COLS = ("type", "ti_begstep", "ti_endstep")
+TIME_VEC_COLS = ("pos", "vel", "grav_accel", "grav_pm", "vel_pred", "hydro_accel")
+TIME_PARAM_DOUBLES = ("timebase_interval", "time_begin", "time_max", "omega0", "omega_lambda", "omega_baryon", "hubble", "gamma",
+                      "min_gas_hsml", "err_tol_int_accuracy", "courant_fac", "max_size_timestep", "min_size_timestep",
+                      "max_rms_displacement_fac", "min_egy_spec", "timestep_scale")
+TIME_PARAM_TABLES = ("drift_table", "gravkick_table", "hydrokick_table")
+TIME_PARAM_INTS = ("comoving", "adaptive_gravsoft", "synchronization", "stop_below_min_timestep")
+
+
+class TimeCols(C.Structure):
+    """ngravs_time_cols_t"""
+    _fields_ = [f for k in TIME_COL_NAMES for f in ((k, C.c_void_p), (k + "_stride", C.c_int64))] + [
+        ("n", C.c_int64), ("on_device", C.c_int32), ("reserved", C.c_int32)]
+
+
+class TimeParams(C.Structure):
+    """ngravs_time_params_t"""
+    _fields_ = [(k, C.c_double) for k in TIME_PARAM_DOUBLES] + [(k, C.c_void_p) for k in TIME_PARAM_TABLES] + [
+        (k, C.c_int32) for k in TIME_PARAM_INTS]
+
+
+class SyncPoint(C.Structure):
+    """ngravs_sync_t"""
+    _fields_ = [("ti_next", C.c_int32), ("full_step", C.c_int32), ("n_active", C.c_int64)]
+
+
+def make_time_params(tables=None, **kw):
+    """ngravs_time_params_t: gamma 5/3, timestep_scale 1, synchronization and stop_below_min_timestep on (the reference's
+    Makefile), everything else 0 unless given by field name.  tables: (drift, gravkick, hydrokick) float64 numpy arrays of
+    DRIFT_TABLE_LENGTH from Engine.time_tables / time_tables(); they are kept alive with the struct."""
+    par = TimeParams()
+    par.gamma, par.timestep_scale, par.synchronization, par.stop_below_min_timestep = 5.0 / 3, 1.0, 1, 1
+    for k, v in kw.items():
+        if k not in TIME_PARAM_DOUBLES + TIME_PARAM_INTS:
+            raise TypeError("ngravs_time_params_t has no field %r" % k)
+        setattr(par, k, int(v) if k in TIME_PARAM_INTS else float(v))
+    if tables is not None:
+        import numpy as np
+        keep = [np.ascontiguousarray(t, dtype=np.float64) for t in tables]
+        assert len(keep) == 3 and all(t.shape == (DRIFT_TABLE_LENGTH,) for t in keep)
+        par.drift_table, par.gravkick_table, par.hydrokick_table = (t.ctypes.data for t in keep)
+        par._tables = keep
+    return par
+
 
 class GravTargets(C.Structure):
     """ngravs_grav_targets_t"""

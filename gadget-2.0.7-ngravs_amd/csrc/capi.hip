@@ -463,6 +463,7 @@ extern "C" void ngravs_destroy(ngravs_ctx *c)
       (void)hipStreamDestroy(c->walk_stream);
     }
   c->probe_out.release();
+  c->time_buf.release();
   (void)hipStreamDestroy(c->stream);
   delete c;
 }
@@ -2757,4 +2758,39 @@ extern "C" int ngravs_pm_targets(ngravs_ctx *c, const ngravs_grav_targets_t *t, 
   if((rc = pm_targets_run(c, nt, c->gt_acc.p)))
     return rc;
   return grav_targets_deliver(c, c->gt_acc.p, sizeof(double) * 3 * (size_t)nt, grav_pm, t->on_device);
+}
+
+// ---- time integration: drift, kick and timestep assignment (run.c:32-65 around the forces; kernels_time.hip) ------------------------
+static_assert(sizeof(ngravs_time_cols_t) == 288 && sizeof(ngravs_time_params_t) == 168 && sizeof(ngravs_sync_t) == 16,
+              "the Python mirror (abi.TimeCols / TimeParams / SyncPoint) assumes this layout");
+extern "C" int ngravs_time_tables(const ngravs_time_params_t *par, int32_t rule, double *drift, double *gravkick, double *hydrokick)
+{
+  return par && drift && gravkick && hydrokick ? time_tables(par, rule, drift, gravkick, hydrokick) : NGRAVS_ERR_ARG;
+}
+extern "C" int ngravs_time_factors(const ngravs_time_params_t *par, int32_t ti0, int32_t ti1, double out[3])
+{
+  return par && out ? time_factors(par, ti0, ti1, out) : NGRAVS_ERR_ARG;
+}
+extern "C" int ngravs_dt_displacement(const ngravs_time_params_t *par, const double sums[18], double G, double asmth, double time,
+                                      double *dt_displacement)
+{
+  return par && sums && dt_displacement ? time_dt_displacement(par, sums, G, asmth, time, dt_displacement) : NGRAVS_ERR_ARG;
+}
+extern "C" int ngravs_next_sync_point(ngravs_ctx *c, const ngravs_time_cols_t *cols, int32_t pm_ti_endstep, ngravs_sync_t *out)
+{
+  return c ? time_next_sync_point(c, cols, pm_ti_endstep, out) : NGRAVS_ERR_ARG;
+}
+extern "C" int ngravs_move_particles(ngravs_ctx *c, const ngravs_time_cols_t *cols, const ngravs_time_params_t *par, int32_t time0,
+                                     int32_t time1, int32_t wrap)
+{
+  return c ? time_move_particles(c, cols, par, time0, time1, wrap) : NGRAVS_ERR_ARG;
+}
+extern "C" int ngravs_displacement_sums(ngravs_ctx *c, const ngravs_time_cols_t *cols, double sums[18])
+{
+  return c ? time_displacement_sums(c, cols, sums) : NGRAVS_ERR_ARG;
+}
+extern "C" int ngravs_advance_and_find_timesteps(ngravs_ctx *c, const ngravs_time_cols_t *cols, const ngravs_time_params_t *par,
+                                                 int32_t ti_current, double dt_displacement, int32_t *pm_ti, int64_t *n_kicked)
+{
+  return c ? time_advance(c, cols, par, ti_current, dt_displacement, pm_ti, n_kicked) : NGRAVS_ERR_ARG;
 }

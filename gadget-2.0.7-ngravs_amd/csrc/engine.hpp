@@ -418,6 +418,9 @@ struct ngravs_ctx
   // pm_phi holds the complete potentials of the last single-mesh PM step (pm_finish); false before one, while they are being
   // rewritten, and when the last PM step went through the slab path, which has no whole mesh
   bool pm_mesh_valid = false;
+  // time integration (kernels_time.hip): counters, the decided steps of one advance call, the look-up tables, and the device
+  // copies of host columns; nothing in it outlives a call
+  DevBuf<unsigned char> time_buf;
 };
 
 // Routes the context's launches to stream `s`, whose CU mask leaves them `cus` CUs, until the end of the scope (the kernels
@@ -685,3 +688,13 @@ void pmslab_release(ngravs_ctx *c);
 void host_shortrange_table(const ngravs_config_t *cfg, double *force, double *pot, const ngravs_user_fn_t *fns = nullptr, int nfns = 0);
 double cfg_asmth(const ngravs_config_t *c);
 double cfg_rcut(const ngravs_config_t *c);
+
+// ---- time integration (kernels_time.hip; the entry points of capi.hip check for NULL and forward) -------------------------------
+int time_tables(const ngravs_time_params_t *par, int rule, double *drift, double *gravkick, double *hydrokick);
+int time_factors(const ngravs_time_params_t *par, int ti0, int ti1, double out[3]);
+int time_dt_displacement(const ngravs_time_params_t *par, const double sums[18], double G, double asmth, double time, double *out);
+int time_next_sync_point(ngravs_ctx *c, const ngravs_time_cols_t *cols, int pm_ti_endstep, ngravs_sync_t *out);
+int time_move_particles(ngravs_ctx *c, const ngravs_time_cols_t *cols, const ngravs_time_params_t *par, int time0, int time1, int wrap);
+int time_displacement_sums(ngravs_ctx *c, const ngravs_time_cols_t *cols, double sums[18]);
+int time_advance(ngravs_ctx *c, const ngravs_time_cols_t *cols, const ngravs_time_params_t *par, int ti_current, double dt_displacement,
+                 int32_t *pm_ti, int64_t *n_kicked);

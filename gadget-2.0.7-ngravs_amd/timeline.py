@@ -1,0 +1,164 @@
+"""The reference's main loop (run.c:32-65) for ONE task on an Engine: sync point, drift, hand-over, accelerations, gas,
+displacement constraint, advance -- every station a call of the library, on columns that stay where they are.
+
+    tl = Timeline(engine, cols, par, sph=dict(des_num_ngb=..., max_num_ngb_deviation=..., art_bulk_visc_const=...))
+    while tl.ti_current < abi.TIMEBASE:
+        tl.step()
+
+cols is the host's P[] and SphP[] as a dict of columns, numpy arrays or contiguous torch tensors on the device (float64; int32
+for type and the two Ti columns): type, pos, vel, mass, ti_begstep, ti_endstep, grav_accel, grav_pm, old_acc, and with gas
+vel_pred, hydro_accel, entropy, dt_entropy, density, hsml, pressure, div_vel, curl_vel, dhsml_factor, max_signal_vel.  All are
+updated in place.  With device tensors no column crosses to the host: the loop reads back the scalars of the sync point and,
+on full steps, the 18 displacement sums.
+"""
+import ctypes as C
+import math
+
+import numpy as np
+
+from . import abi
+
+TIME_COLS = abi.TIME_COL_NAMES
+GAS_COLS = ("vel_pred", "hydro_accel", "entropy", "dt_entropy", "density", "hsml", "pressure", "div_vel", "curl_vel", "dhsml_factor",
+            "max_signal_vel")
+
+
+def _addr(a):
+    return a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data
+
+
+class Timeline:
+    """ti_current, time, pm_ti ([PM_Ti_begstep, PM_Ti_endstep], None without a mesh), dt_displacement, full_step and n_active
+    are the reference's globals of the same names after the last step()."""
+
+    def __init__(self, engine, cols, par, sph=None, tree_domain_update_frequency=0.0, softening=None, on_station=None):
+        """par: abi.make_time_params(...).  sph: the keyword arguments of Engine.sph_accelerations that are not columns or times
+        (des_num_ngb, max_num_ngb_deviation, art_bulk_visc_const, ...), required with gas.  tree_domain_update_frequency:
+        All.TreeDomainUpdateFrequency (domain.c:66-76); 0 decomposes and builds on every step.  softening: None, or a function
+        of All.Time that returns All.ForceSoftening[6] (set_softenings(), gravtree.c:468-518, for comoving runs).  on_station:
+        None, or a function called as on_station(name, timeline) in front of the stations "drift" and "advance", when the particles
+        have "moved", and at the "end" of a step.  The reference's start (init.c): Ti_begstep = Ti_endstep = 0 for every row, Ti_Current = 0."""
+        from . import lib
+        self._lib = lib()
+        self.eng, self.cols, self.par = engine, cols, par
+        self.sph = dict(sph or {})
+        self.freq = float(tree_domain_update_frequency)
+        self.softening, self.on_station = softening, on_station
+        self.n = int(cols["pos"].shape[0])
+        self.device = hasattr(cols["pos"], "data_ptr")
+        self.mesh = engine.cfg.pmgrid > 0
+        self.n_gas = int((cols["type"] == 0).sum())
+        if self.n_gas and not all(k in cols for k in GAS_COLS):
+            raise ValueError("gas needs the columns %s" % (GAS_COLS,))
+        cols["ti_begstep"][:] = 0
+        cols["ti_endstep"][:] = 0
+        self.ti_current, self.pm_ti = 0, [0, 0] if self.mesh else None
+        self.time = par.time_begin
+        self.dt_displacement, self.full_step, self.n_active = 0.0, True, 0
+        self.num_forces_since_decomp = 1 + self.n * self.freq   # (begrun: the first step decomposes)
+        self.have_tree = False
+        self.steps = 0
+
+    def _station(self, name):
+        if self.on_station:
+            self.on_station(name, self)
+
+    def _time_cols(self, names):
+        return {k: self.cols[k] for k in names if k in self.cols}
+
+    def _hand_over(self, rebuild):
+        """P[] to the engine: a new particle set in front of a decomposition, else the drifted rows of the kept tree"""
+        c = self.cols
+        if self.device:
+            import torch
+            act = (c["ti_endstep"] == self.ti_current).to(torch.uint8)
+            torch.cuda.synchronize()   # the library works on a stream of its own
+        else:
+            act = (c["ti_endstep"] == self.ti_current).astype(np.uint8)
+        p = abi.Particles()
+        p.n = self.n
+        p.pos, p.pos_stride = _addr(c["pos"]), 24
+        p.mass, p.mass_stride = _addr(c["mass"]), 8
+        p.type, p.type_stride = _addr(c["type"]), 4
+        p.old_acc, p.old_acc_stride = _addr(c["old_acc"]), 8
+        p.active, p.active_stride = _addr(act), 1
+        if self.mesh and rebuild:
+            p.grav_pm, p.grav_pm_stride = _addr(c["grav_pm"]), 24
+        p.on_device = int(self.device)
+        eng = self.eng
+        if rebuild:
+            eng.n = self.n
+            eng._check(self._lib.ngravs_set_particles(eng._h, C.byref(p)), "ngravs_set_particles")
+        else:
+            eng._check(self._lib.ngravs_update_particles(eng._h, C.byref(p)), "ngravs_update_particles")
+            eng.force_update_tree()
+        if self.par.adaptive_gravsoft and self.n_gas:
+            eng.set_gas_softening(c["hsml"])
+        self._active = act
+
+    def _fetch_accel(self):
+        """GravAccel and OldAcc of the active rows, GravPM of all rows, into the caller's columns (gravtree.c:318-341)"""
+        c, eng = self.cols, self.eng
+        eng._check(self._lib.ngravs_get_accel(eng._h, _addr(c["grav_accel"]), 24, _addr(c["grav_pm"]) if self.mesh else None, 24,
+                                              _addr(c["old_acc"]), 8, None, 0, int(self.device), 1), "ngravs_get_accel")
+
+    def step(self):
+        """one pass of the main loop (run.c:36-61); returns ti_current"""
+        eng, c, par = self.eng, self.cols, self.par
+        # 1. find_next_sync_point_and_drift (run.c:151-234)
+        ti_next, self.full_step, self.n_active = eng.next_sync_point(c["ti_endstep"], self.pm_ti[1] if self.mesh else None)
+        self.num_forces_since_decomp += self.n_active
+        pm_step = self.mesh and self.pm_ti[1] == ti_next
+        if pm_step:   # domain.c:66-73
+            self.num_forces_since_decomp = 1 + self.n * self.freq
+        rebuild = not self.have_tree or self.num_forces_since_decomp > self.n * self.freq   # domain.c:76
+        self._station("drift")
+        # 2. the drift; in front of a decomposition the particles are mapped back onto the box (domain.c:80-82)
+        self.wrapped = bool(rebuild and eng.cfg.periodic)
+        eng.move_particles(self._time_cols(TIME_COLS), par, self.ti_current, ti_next, wrap=rebuild)
+        self.ti_previous, self.ti_current = self.ti_current, ti_next
+        self._station("moved")
+        if par.comoving:
+            self.time = par.time_begin * math.exp(ti_next * par.timebase_interval)
+        else:
+            self.time = par.time_begin + ti_next * par.timebase_interval
+        if self.softening:
+            eng.set_softening(self.softening(self.time))
+        # 3. domain_Decomposition, or the kept tree
+        self._hand_over(rebuild)
+        if rebuild:
+            self.num_forces_since_decomp = 0
+        # 4. compute_accelerations (accel.c:24-58); at the start twice, the second time with the OldAcc of the first
+        eng.compute_accelerations(pm_step)
+        self.have_tree = True
+        self._fetch_accel()
+        if self.ti_current == 0 and eng.cfg.err_tol_theta == 0:
+            eng._check(self._lib.ngravs_set_old_acc(eng._h, _addr(c["old_acc"]), 8, int(self.device)), "ngravs_set_old_acc")
+            eng.gravity_tree()
+            self._fetch_accel()
+        # 5. density, pressure and hydro forces of the active gas (accel.c:60-89)
+        if self.n_gas:
+            comoving = None
+            if par.comoving:
+                from . import hydro_factors
+                comoving = hydro_factors(self.time, par.omega0, par.omega_lambda, par.hubble, par.gamma)
+            out = dict(hydro_accel=c["hydro_accel"], dt_entropy_out=c["dt_entropy"], max_signal_vel=c["max_signal_vel"])
+            self.sph_result = eng.sph_accelerations(
+                c["vel_pred"], c["entropy"], c["hsml"], c["density"], c["pressure"], c["dhsml_factor"], c["div_vel"], c["curl_vel"],
+                dt_entropy=c["dt_entropy"], ti_begstep=c["ti_begstep"], ti_endstep=c["ti_endstep"], ti_current=self.ti_current,
+                timebase_interval=par.timebase_interval, gamma=par.gamma, min_gas_hsml=par.min_gas_hsml, comoving=comoving, out=out,
+                **self.sph)
+        # 6. the displacement constraint, on full steps (timestep.c:63-68)
+        if self.full_step or self.dt_displacement == 0:
+            self.disp_sums = eng.displacement_sums(c["type"], c["vel"], c["mass"])
+            self.dt_displacement = eng.dt_displacement(par, self.disp_sums, self.time)
+        # 7. advance_and_find_timesteps
+        self._station("advance")
+        self.n_kicked, pm_ti = eng.advance_and_find_timesteps(self._time_cols(TIME_COLS), par, self.ti_current, self.dt_displacement,
+                                                              self.pm_ti)
+        if pm_step:
+            self.pm_ti = pm_ti
+            self.num_forces_since_decomp = 1 + self.n * self.freq   # timestep.c:77-81: the nodes were not kicked
+        self.steps += 1
+        self._station("end")
+        return self.ti_current

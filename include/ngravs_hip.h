@@ -734,6 +734,113 @@ int64_t ngravs_sph_density_update(int64_t n, const double *sums, double *hsml, d
                                   double des_num_ngb, double max_num_ngb_deviation, double min_gas_hsml,
                                   const ngravs_sph_update_out_t *out, int32_t on_device);
 
+/* ---- Time integration for ONE task: the stations of run.c:32-65 around the force computation -------------------------------------
+ * find_next_sync_point_and_drift (run.c:151-234), move_particles (predict.c:31-76), do_box_wrapping (predict.c:106-133),
+ * find_dt_displacement_constraint (timestep.c:587-665), advance_and_find_timesteps with get_timestep (timestep.c:24-576) and the
+ * look-up tables of driftfac.c, so that a host whose particles live on the device runs the whole loop without a column leaving it.
+ * Every call is STATELESS over the caller's columns: ngravs_time_cols_t is a view of the host's P[] and SphP[] (pointer + stride in
+ * bytes per field; any layout, SoA or interleaved), n its number of rows.  on_device != 0: device pointers, used in place;
+ * otherwise host pointers, staged by the library.  The context supplies only G, BoxSize, PERIODIC, PMGRID ("a mesh": PMGRID > 0),
+ * Asmth and All.SofteningTable[type] = force_softening[type] / 2.8 of the last softening set.  No call touches the engine's
+ * particles, its tree, the walk's state or the stored accelerations.  One task: the calls are local; a host with several tasks
+ * all-reduces the scalars of the sync point and the 18 displacement sums itself.
+ * Which columns a call reads (R) and writes (W), rows of type != 0 never touching a gas column:
+ *   sync point        R ti_endstep
+ *   move              R type vel, W pos; gas rows: R grav_accel [grav_pm with a mesh] hydro_accel div_vel entropy dt_entropy ti_begstep
+ *                     ti_endstep, W vel_pred density hsml pressure
+ *   displacement sums R type vel mass
+ *   advance           active rows: R type grav_accel [grav_pm with a mesh], W vel ti_begstep ti_endstep; active gas rows: R hydro_accel
+ *                     density hsml max_signal_vel, W vel_pred entropy dt_entropy; on a long-range kick ALL rows: R grav_pm, W vel, and
+ *                     all gas rows: R grav_accel hydro_accel, W vel_pred
+ * Refusals (NGRAVS_ERR_ARG with a message, nothing written): NULL ctx, cols or params, n < 0, NULL where a column is required, a gas
+ * column missing while a type-0 row exists, a type outside 0..5, timebase_interval <= 0, gamma < 1, time1 < time0, a comoving
+ * call without tables.
+ * Not provided: FLEXSTEPS, PSEUDOSYMMETRIC, MAKEGLASS, CONDUCTION, NOPMSTEPADJUSTMENT, PLACEHIGHRESREGION, snapshot times
+ * (run.c:206-225), the node drift and node kicks (predict.c:79-91, timestep.c:331-344: the library refits its tree instead). */
+#define NGRAVS_TIMEBASE (1 << 28)          /* allvars.h: TIMEBASE                                     */
+#define NGRAVS_DRIFT_TABLE_LENGTH 1000     /* allvars.h: DRIFT_TABLE_LENGTH                           */
+typedef struct {   /* strides in bytes; n rows */
+  int32_t *type;           int64_t type_stride;            /* P[].Type                                   */
+  double *pos;             int64_t pos_stride;             /* P[].Pos[3]                                 */
+  double *vel;             int64_t vel_stride;             /* P[].Vel[3]                                 */
+  double *mass;            int64_t mass_stride;            /* P[].Mass                                   */
+  int32_t *ti_begstep;     int64_t ti_begstep_stride;      /* P[].Ti_begstep                             */
+  int32_t *ti_endstep;     int64_t ti_endstep_stride;      /* P[].Ti_endstep                             */
+  double *grav_accel;      int64_t grav_accel_stride;      /* P[].GravAccel[3]                           */
+  double *grav_pm;         int64_t grav_pm_stride;         /* P[].GravPM[3]; read only with a mesh       */
+  double *vel_pred;        int64_t vel_pred_stride;        /* SphP[].VelPred[3]                          */
+  double *hydro_accel;     int64_t hydro_accel_stride;     /* SphP[].HydroAccel[3]                       */
+  double *entropy;         int64_t entropy_stride;         /* SphP[].Entropy                             */
+  double *dt_entropy;      int64_t dt_entropy_stride;      /* SphP[].DtEntropy                           */
+  double *density;         int64_t density_stride;         /* SphP[].Density                             */
+  double *hsml;            int64_t hsml_stride;            /* SphP[].Hsml                                */
+  double *pressure;        int64_t pressure_stride;        /* SphP[].Pressure                            */
+  double *div_vel;         int64_t div_vel_stride;         /* SphP[].DivVel                              */
+  double *max_signal_vel;  int64_t max_signal_vel_stride;  /* SphP[].MaxSignalVel                        */
+  int64_t n;                                               /* NumPart                                    */
+  int32_t on_device, reserved;
+} ngravs_time_cols_t;
+typedef struct {
+  double timebase_interval;         /* All.Timebase_interval                                                                   */
+  double time_begin, time_max;      /* All.TimeBegin, All.TimeMax: the span of the integer time line (and of the tables)       */
+  double omega0, omega_lambda, omega_baryon, hubble;   /* All.Omega0, OmegaLambda, OmegaBaryon, Hubble; read when comoving     */
+  double gamma;                     /* GAMMA (5/3; 1 is ISOTHERM_EQS)                                                          */
+  double min_gas_hsml;              /* All.MinGasHsml                                                                          */
+  double err_tol_int_accuracy, courant_fac;            /* All.ErrTolIntAccuracy, All.CourantFac                                */
+  double max_size_timestep, min_size_timestep;         /* All.MaxSizeTimestep, All.MinSizeTimestep                             */
+  double max_rms_displacement_fac;  /* All.MaxRMSDisplacementFac                                                               */
+  double min_egy_spec;              /* All.MinEgySpec (0: no floor)                                                            */
+  double timestep_scale;            /* NGRAVS_TIMESTEP_SCALE (timestep.c:484-493); 0 => 1                                      */
+  const double *drift_table, *gravkick_table, *hydrokick_table;   /* HOST arrays of NGRAVS_DRIFT_TABLE_LENGTH (driftfac.c);
+                                                                     required when comoving != 0                               */
+  int32_t comoving;                 /* All.ComovingIntegrationOn                                                               */
+  int32_t adaptive_gravsoft;        /* ADAPTIVE_GRAVSOFT_FORGAS: a gas row's softening in the step criterion is Hsml / 2.8      */
+  int32_t synchronization;          /* SYNCHRONIZATION (timestep.c:240-246); 1 in the reference's Makefile                     */
+  int32_t stop_below_min_timestep;  /* 1: a step below MinSizeTimestep is fatal (888), the reference's default; 0: the step
+                                       becomes MinSizeTimestep (NOSTOP_WHEN_BELOW_MINTIMESTEP)                                 */
+} ngravs_time_params_t;
+typedef struct {
+  int32_t ti_next;       /* the next sync point: min Ti_endstep, or PM_Ti_endstep when the minimum is not below it (run.c:175-181) */
+  int32_t full_step;     /* Flag_FullStep: every row sits on the minimum, or the PM rule applied                                  */
+  int64_t n_active;      /* NumForceUpdate: rows with Ti_endstep == ti_next                                                        */
+} ngravs_sync_t;
+/* init_drift_table (driftfac.c:26-60), host, no GPU: drift[i], gravkick[i], hydrokick[i] = the integrals of driftfac.c:179-212 from
+ * time_begin to exp(log time_begin + (log time_max - log time_begin) / LENGTH * (i + 1)), LENGTH entries each.  Reads omega0,
+ * omega_lambda, hubble, gamma, time_begin, time_max of par.  A fixed rule instead of the reference's adaptive one at 1e-8: every
+ * table cell is integrated in log a by Gauss-Legendre, rule 0 with 12 nodes on one panel, rule 1 (the check) with 12 nodes on each
+ * of two panels, and the cells are added up.  NGRAVS_ERR_ARG: a NULL argument, time_begin <= 0, time_max <= time_begin, hubble <= 0,
+ * gamma < 1, another rule. */
+int ngravs_time_tables(const ngravs_time_params_t *par, int32_t rule, double *drift, double *gravkick, double *hydrokick);
+/* get_drift_factor, get_gravkick_factor, get_hydrokick_factor (driftfac.c:67-174) for the integer times ti0, ti1 from the tables
+ * in par -> out[3]; the branch for the first two cells and the clamp at the table's end included.  Host, no GPU; the device code
+ * evaluates the same function. */
+int ngravs_time_factors(const ngravs_time_params_t *par, int32_t ti0, int32_t ti1, double out[3]);
+/* run.c:161-191.  pm_ti_endstep < 0: no PM time (tree-only).  NGRAVS_ERR_ARG also for n = 0 (the minimum of nothing). */
+int ngravs_next_sync_point(ngravs_ctx *ctx, const ngravs_time_cols_t *cols, int32_t pm_ti_endstep, ngravs_sync_t *out);
+/* move_particles from the integer time time0 to time1 (predict.c:31-76) over ALL rows; the three factors come from the tables,
+ * once per call, when comoving.  wrap != 0: afterwards do_box_wrapping (predict.c:124-132) when the configuration is periodic --
+ * the reference wraps only in front of a decomposition, the caller decides. */
+int ngravs_move_particles(ngravs_ctx *ctx, const ngravs_time_cols_t *cols, const ngravs_time_params_t *par, int32_t time0,
+                          int32_t time1, int32_t wrap);
+/* The local sums of timestep.c:606-612: sums[0..5] = sum of |Vel|^2 per type, [6..11] the smallest mass per type (1.0e30 for a
+ * type without rows), [12..17] the number of rows per type.  The same sums bit for bit on every call with the same columns. */
+int ngravs_displacement_sums(ngravs_ctx *ctx, const ngravs_time_cols_t *cols, double sums[18]);
+/* The rest of find_dt_displacement_constraint (timestep.c:595-659) from the (all-reduced) sums, host, no GPU: MaxSizeTimestep
+ * without comoving integration; else per populated type the dmean rule (OmegaBaryon for type 0) and, when asmth > 0 (a mesh:
+ * All.Asmth[0]) and asmth < dmean, the Asmth rule, with hfac = a^2 H(a) at the expansion factor `time`. */
+int ngravs_dt_displacement(const ngravs_time_params_t *par, const double sums[18], double G, double asmth, double time,
+                           double *dt_displacement);
+/* advance_and_find_timesteps at All.Ti_Current = ti_current (timestep.c:24-413) for the rows with Ti_endstep == ti_current, with
+ * the caller's dt_displacement; All.Time is time_begin * exp(ti_current * timebase_interval) when comoving.  With a mesh pm_ti[2] =
+ * {All.PM_Ti_begstep, All.PM_Ti_endstep} is required, in/out, and when pm_ti[1] == ti_current the long-range kick of
+ * timestep.c:351-408 runs over ALL rows.  The steps are decided in one pass and applied in a second: NOTHING is written unless the
+ * whole call succeeds.  The two fatal cases call the fatal handler with the reference's code and the lowest failing row, and
+ * return NGRAVS_ERR_STATE: 888, a step below MinSizeTimestep (with stop_below_min_timestep); 818, a step on the integer line that
+ * is not in (0, TIMEBASE) -- a quotient dt / timebase_interval that no int holds is this case.  n_kicked (may be NULL): the rows
+ * advanced. */
+int ngravs_advance_and_find_timesteps(ngravs_ctx *ctx, const ngravs_time_cols_t *cols, const ngravs_time_params_t *par,
+                                      int32_t ti_current, double dt_displacement, int32_t *pm_ti, int64_t *n_kicked);
+
 #ifdef __cplusplus
 }
 #endif
