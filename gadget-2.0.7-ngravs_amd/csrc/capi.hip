@@ -4,6 +4,7 @@
 // pmforce_periodic (longrange.c:56, pm_periodic.c:204), domain_Decomposition (domain.c:62-154),
 // compute_accelerations (accel.c:24-96), init_grav_maps (ngravs_core.c:201-425).
 #include "engine.hpp"
+#include "columns.hpp"
 #include "../../include/ngravs_peano.h"
 #include <chrono>
 #include <cmath>
@@ -23,65 +24,6 @@ void ngravs_report(ngravs_ctx *ctx, int code, const std::string &msg)
 }
 
 // ---- small device helpers ---------------------------------------------------------------------
-__global__ void k_pack_strided_f64(const unsigned char *src, long long stride, int ncomp, long long n, double *dst)
-{
-  long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-  if(i >= n)
-    return;
-  const double *s = reinterpret_cast<const double *>(src + i * stride);
-  for(int k = 0; k < ncomp; k++)
-    dst[i * ncomp + k] = s[k];
-}
-// Type column: values outside 0..5 would index fsoft[] / t2g[] out of bounds; they are counted (the host path
-// rejects them before the upload) and clamped
-__global__ void k_pack_type(const unsigned char *src, long long stride, long long n, int *dst, int *nbad)
-{
-  long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-  if(i >= n)
-    return;
-  int t = *reinterpret_cast<const int *>(src + i * stride);
-  if(t < 0 || t >= NGRAVS_NTYPES)
-    {
-      atomicAdd(nbad, 1);
-      t = t < 0 ? 0 : NGRAVS_NTYPES - 1;
-    }
-  dst[i] = t;
-}
-// active flag: only bit 0 is the caller's (bit 1 marks halo copies inside the engine)
-__global__ void k_pack_active(const unsigned char *src, long long stride, long long n, unsigned char *dst)
-{
-  long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-  if(i < n)
-    dst[i] = src[i * stride] ? 1 : 0;
-}
-// rows of the caller-order result that belong to active particles only (gravtree.c:318-341 touch nothing else)
-__global__ void k_copy_masked_f64(const unsigned char *__restrict__ act, long long n, int ncomp, const double *__restrict__ src,
-                                  double *__restrict__ dst)
-{
-  long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-  if(i >= n || !(act[i] & 1))
-    return;
-  for(int k = 0; k < ncomp; k++)
-    dst[i * ncomp + k] = src[i * ncomp + k];
-}
-__global__ void k_copy_masked_f32(const unsigned char *__restrict__ act, long long n, const float *__restrict__ src, float *__restrict__ dst)
-{
-  long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-  if(i < n && (act[i] & 1))
-    dst[i] = src[i];
-}
-__global__ void k_pack_strided_i32(const unsigned char *src, long long stride, long long n, int *dst)
-{
-  long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-  if(i < n)
-    dst[i] = *reinterpret_cast<const int *>(src + i * stride);
-}
-__global__ void k_pack_strided_f32_to_f64(const unsigned char *src, long long stride, long long n, double *dst)
-{
-  long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-  if(i < n)
-    dst[i] = (double)*reinterpret_cast<const float *>(src + i * stride);
-}
 // GravCost of the walked particles -> the work-weight column (caller order); other rows keep theirs (gravtree.c:387-392 updates
 // P[].GravCost of active particles only)
 __global__ void k_cost_update(const unsigned int *__restrict__ idx, const unsigned char *__restrict__ act, const int *__restrict__ nint,
@@ -93,64 +35,6 @@ __global__ void k_cost_update(const unsigned int *__restrict__ idx, const unsign
   const long long i = first + k;
   if(act[i] & 1)
     cost[idx[i]] = (double)nint[i];
-}
-__global__ void k_fill_f64(double *p, long long n, double v)
-{
-  long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-  if(i < n)
-    p[i] = v;
-}
-__global__ void k_fill_u8(unsigned char *p, long long n, unsigned char v)
-{
-  long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-  if(i < n)
-    p[i] = v;
-}
-// Peano order -> caller order
-__global__ void k_unpermute_f64(const unsigned int *idx, long long n, int ncomp, const double *src, double *dst)
-{
-  long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-  if(i >= n)
-    return;
-  long long j = idx[i];
-  for(int k = 0; k < ncomp; k++)
-    dst[j * ncomp + k] = src[i * ncomp + k];
-}
-__global__ void k_unpermute_i2f(const unsigned int *idx, long long n, const int *src, float *dst)
-{
-  long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-  if(i < n)
-    dst[idx[i]] = (float)src[i];
-}
-__global__ void k_permute_f64(const unsigned int *idx, long long n, int ncomp, const double *src, double *dst)
-{
-  long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-  if(i >= n)
-    return;
-  long long j = idx[i];
-  for(int k = 0; k < ncomp; k++)
-    dst[i * ncomp + k] = src[j * ncomp + k];
-}
-// Peano order <- caller order for a column that only exists for the first `lim` (own) rows: imported copies read 0
-__global__ void k_permute_f64_lim(const unsigned int *idx, long long n, long long lim, int ncomp, const double *src, double *dst)
-{
-  long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-  if(i >= n)
-    return;
-  long long j = idx[i];
-  for(int k = 0; k < ncomp; k++)
-    dst[i * ncomp + k] = j < lim ? src[j * ncomp + k] : 0.0;
-}
-// Peano order -> caller order, own rows only
-__global__ void k_unpermute_f64_lim(const unsigned int *idx, long long n, long long lim, int ncomp, const double *src, double *dst)
-{
-  long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-  if(i >= n)
-    return;
-  long long j = idx[i];
-  if(j < lim)
-    for(int k = 0; k < ncomp; k++)
-      dst[j * ncomp + k] = src[i * ncomp + k];
 }
 __global__ void k_key18(const unsigned long long *k21, long long n, long long *out)
 {
@@ -170,7 +54,6 @@ __global__ void k_map_idx(const int *inv, const int *in, long long n, int *out)
   if(i < n)
     out[i] = inv[in[i]];
 }
-#define GRID1(n) dim3((unsigned)(((n) + 255) / 256)), dim3(256)
 
 // ---- lifecycle --------------------------------------------------------------------------------
 extern "C" int ngravs_abi_version(void) { return NGRAVS_ABI_VERSION; }
@@ -612,33 +495,25 @@ extern "C" int ngravs_device_free(ngravs_ctx *c, void *ptr)
 }
 
 // ---- data hand-over -----------------------------------------------------------------------------
-static int upload_column_f64(ngravs_ctx *c, const void *src, int64_t stride, int ncomp, int64_t n, int on_device, double *dst)
-{
-  if(on_device)
-    {
-      if(stride == (int64_t)sizeof(double) * ncomp)
-        HIP_TRY(c, hipMemcpyAsync(dst, src, sizeof(double) * ncomp * n, hipMemcpyDeviceToDevice, c->stream));
-      else
-        hipLaunchKernelGGL(k_pack_strided_f64, GRID1(n), 0, c->stream, (const unsigned char *)src, (long long)stride, ncomp,
-                           (long long)n, dst);
-      return NGRAVS_OK;
-    }
-  if(stride == (int64_t)sizeof(double) * ncomp)
-    {
-      HIP_TRY(c, hipMemcpyAsync(dst, src, sizeof(double) * ncomp * n, hipMemcpyHostToDevice, c->stream));
-      HIP_TRY(c, hipStreamSynchronize(c->stream));
-      return NGRAVS_OK;
-    }
-  c->host_stage.resize(sizeof(double) * ncomp * (size_t)n);
-  double *h = reinterpret_cast<double *>(c->host_stage.data());
-  for(int64_t i = 0; i < n; i++)
-    memcpy(h + i * ncomp, (const unsigned char *)src + i * stride, sizeof(double) * ncomp);
-  HIP_TRY(c, hipMemcpyAsync(dst, h, sizeof(double) * ncomp * n, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return NGRAVS_OK;
-}
-
 static double ev_ms(ngravs_ctx *c);
+
+// the state after a hand-over: what every one resets, and what only a new particle set (not a kept tree's update) resets
+static void handed_over(ngravs_ctx *c, bool keep_tree)
+{
+  c->walk_ia_ratio = 0;   // (a new particle set: the walk's unit is chosen afresh)
+  c->pm_solo_steps = 0, c->pm_auto_cus = -1;   // ... and so are the CUs reserved for PM
+  c->walk_unit_state = 4;
+  c->have_particles = true;
+  if(keep_tree)
+    {
+      c->tree_stale = true;    // same order and topology; columns and moments are refreshed by ngravs_force_update_tree
+      return;
+    }
+  c->have_order = c->have_tree = c->have_pm = c->have_acc = false;   // new P[]: nothing carries over ...
+  c->gsoft_on = false;     // ... a new set has no gas softening lengths
+  c->top.on = false;   // (the top tree itself is kept: it is the first guess of the next decomposition)
+  c->pm_parked = false;
+}
 
 static int set_particles_impl(ngravs_ctx *c, const ngravs_particles_t *p, bool keep_tree)
 {
@@ -661,14 +536,7 @@ static int set_particles_impl(ngravs_ctx *c, const ngravs_particles_t *p, bool k
       c->own_order_nlocal = -1;
       c->sort_low = 35;
       c->all_active = true;
-      c->walk_ia_ratio = 0;   // (a new particle set: the walk's unit is chosen afresh)
-      c->pm_solo_steps = 0, c->pm_auto_cus = -1;   // ... and so are the CUs reserved for PM
-      c->walk_unit_state = 4;
-      c->have_particles = true;
-      c->have_order = c->have_tree = c->have_pm = c->have_acc = false;
-      c->gsoft_on = false;
-      c->top.on = false;
-      c->pm_parked = false;
+      handed_over(c, false);
       return NGRAVS_OK;
     }
   // (a multi-task working set: the caller's rows are its own particles; the imported copies behind them are refreshed by their
@@ -707,13 +575,13 @@ static int set_particles_impl(ngravs_ctx *c, const ngravs_particles_t *p, bool k
   int rc;
   if(!keep_tree && (rc = dd_fill_ids(c)))
     return rc;
-  if((rc = upload_column_f64(c, p->pos, p->pos_stride, 3, n, p->on_device, c->in_pos.p)))
+  if((rc = col_upload(c, p->pos, p->pos_stride, sizeof(double), 3, n, p->on_device, c->in_pos.p)))
     return rc;
-  if((rc = upload_column_f64(c, p->mass, p->mass_stride, 1, n, p->on_device, c->in_mass.p)))
+  if((rc = col_upload(c, p->mass, p->mass_stride, sizeof(double), 1, n, p->on_device, c->in_mass.p)))
     return rc;
   if(p->old_acc)
     {
-      if((rc = upload_column_f64(c, p->old_acc, p->old_acc_stride, 1, n, p->on_device, c->in_oldacc.p)))
+      if((rc = col_upload(c, p->old_acc, p->old_acc_stride, sizeof(double), 1, n, p->on_device, c->in_oldacc.p)))
         return rc;
     }
   else
@@ -725,16 +593,15 @@ static int set_particles_impl(ngravs_ctx *c, const ngravs_particles_t *p, bool k
                            (long long)p->grav_cost_stride, (long long)n, c->in_cost.p);
       else if(p->grav_cost)
         {
-          c->host_stage.resize(sizeof(double) * (size_t)n);
-          double *h = reinterpret_cast<double *>(c->host_stage.data());
+          // the floats at the front of the staging buffer, their doubles behind them
+          const size_t at = (sizeof(float) * (size_t)n + 7) & ~(size_t)7;
+          unsigned char *st = col_stage_rows(c, p->grav_cost, p->grav_cost_stride, sizeof(float), n, at + sizeof(double) * (size_t)n);
+          const float *f = reinterpret_cast<const float *>(st);
+          double *h = reinterpret_cast<double *>(st + at);
           for(int64_t i = 0; i < n; i++)
-            {
-              float f;
-              memcpy(&f, (const unsigned char *)p->grav_cost + i * p->grav_cost_stride, sizeof(float));
-              h[i] = f;
-            }
-          HIP_TRY(c, hipMemcpyAsync(c->in_cost.p, h, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
-          HIP_TRY(c, hipStreamSynchronize(c->stream));
+            h[i] = f[i];
+          if((rc = col_upload(c, h, sizeof(double), sizeof(double), 1, n, 0, c->in_cost.p)))
+            return rc;
         }
       else
         hipLaunchKernelGGL(k_fill_f64, GRID1(n), 0, c->stream, c->in_cost.p, (long long)n, 0.0);
@@ -758,19 +625,15 @@ static int set_particles_impl(ngravs_ctx *c, const ngravs_particles_t *p, bool k
     }
   else
     {
-      c->host_stage.resize(sizeof(int) * (size_t)n);
-      int *h = reinterpret_cast<int *>(c->host_stage.data());
+      const int *h = reinterpret_cast<const int *>(col_stage_rows(c, p->type, p->type_stride, sizeof(int), n, sizeof(int) * (size_t)n));
       for(int64_t i = 0; i < n; i++)
-        {
-          memcpy(h + i, (const unsigned char *)p->type + i * p->type_stride, sizeof(int));
-          if(h[i] < 0 || h[i] >= NGRAVS_NTYPES)
-            {
-              ngravs_report(c, NGRAVS_ERR_ARG, "particle Type outside 0..5");
-              return NGRAVS_ERR_ARG;
-            }
-        }
-      HIP_TRY(c, hipMemcpyAsync(c->in_type.p, h, sizeof(int) * n, hipMemcpyHostToDevice, c->stream));
-      HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if(h[i] < 0 || h[i] >= NGRAVS_NTYPES)
+          {
+            ngravs_report(c, NGRAVS_ERR_ARG, "particle Type outside 0..5");
+            return NGRAVS_ERR_ARG;
+          }
+      if((rc = col_upload(c, h, sizeof(int), sizeof(int), 1, n, 0, c->in_type.p)))
+        return rc;
     }
   c->all_active = p->active == nullptr;
   if(p->active)
@@ -780,38 +643,26 @@ static int set_particles_impl(ngravs_ctx *c, const ngravs_particles_t *p, bool k
                            (long long)p->active_stride, (long long)n, c->in_active.p);
       else
         {
-          c->host_stage.resize((size_t)n);
+          unsigned char *h = col_stage_rows(c, p->active, p->active_stride, 1, n, (size_t)n);
           for(int64_t i = 0; i < n; i++)
-            c->host_stage[i] = ((const unsigned char *)p->active)[i * p->active_stride] ? 1 : 0;
-          HIP_TRY(c, hipMemcpyAsync(c->in_active.p, c->host_stage.data(), (size_t)n, hipMemcpyHostToDevice, c->stream));
-          HIP_TRY(c, hipStreamSynchronize(c->stream));
+            h[i] = h[i] ? 1 : 0;
+          if((rc = col_upload(c, h, 1, 1, 1, n, 0, c->in_active.p)))
+            return rc;
         }
     }
   else
     hipLaunchKernelGGL(k_fill_u8, GRID1(n), 0, c->stream, c->in_active.p, (long long)n, (unsigned char)1);
   HIP_TRY(c, hipGetLastError());
-  c->walk_ia_ratio = 0;   // (a new particle set: the walk's unit is chosen afresh)
-  c->pm_solo_steps = 0, c->pm_auto_cus = -1;   // ... and so are the CUs reserved for PM
-  c->walk_unit_state = 4;
-  c->have_particles = true;
-  if(keep_tree)
-    c->tree_stale = true;    // same order and topology; columns and moments are refreshed by ngravs_force_update_tree
-  else
+  handed_over(c, keep_tree);
+  if(!keep_tree && p->grav_pm && c->cfg.pmgrid)
     {
-      c->have_order = c->have_tree = c->have_pm = c->have_acc = false;   // new P[]: nothing carries over ...
-      c->gsoft_on = false;     // ... a new set has no gas softening lengths
-      c->top.on = false;   // (the top tree itself is kept: it is the first guess of the next decomposition)
-      c->pm_parked = false;
-      if(p->grav_pm && c->cfg.pmgrid)
-        {
-          // ... except P[].GravPM, which the host keeps between PM steps: parked in caller order, permuted into the Peano
-          // order by the next ngravs_domain_decomposition (OldAcc on non-PM steps needs it, gravtree.c:318-330)
-          if(c->pm_orig.ensure(3 * n))
-            return NGRAVS_ERR_NOMEM;
-          if((rc = upload_column_f64(c, p->grav_pm, p->grav_pm_stride, 3, n, p->on_device, c->pm_orig.p)))
-            return rc;
-          c->pm_parked = true;
-        }
+      // nothing carries over except P[].GravPM, which the host keeps between PM steps: parked in caller order, permuted into the
+      // Peano order by the next ngravs_domain_decomposition (OldAcc on non-PM steps needs it, gravtree.c:318-330)
+      if(c->pm_orig.ensure(3 * n))
+        return NGRAVS_ERR_NOMEM;
+      if((rc = col_upload(c, p->grav_pm, p->grav_pm_stride, sizeof(double), 3, n, p->on_device, c->pm_orig.p)))
+        return rc;
+      c->pm_parked = true;
     }
   return NGRAVS_OK;
 }
@@ -856,7 +707,7 @@ extern "C" int ngravs_set_old_acc(ngravs_ctx *c, const double *old_acc, int64_t 
     return NGRAVS_OK;
   // the caller's rows are its OWN particles (NumPart = ngravs_dd_num_local()); imported copies of a multi-task working set are
   // sources only, their OldAcc is never read
-  int rc = upload_column_f64(c, old_acc, stride, 1, c->n_local, on_device, c->in_oldacc.p);
+  int rc = col_upload(c, old_acc, stride, sizeof(double), 1, c->n_local, on_device, c->in_oldacc.p);
   if(rc)
     return rc;
   if(c->have_order)
@@ -865,9 +716,8 @@ extern "C" int ngravs_set_old_acc(ngravs_ctx *c, const double *old_acc, int64_t 
   return NGRAVS_OK;
 }
 
-// type-0 rows whose length is negative or not finite are counted; rows of other types are not read and staged as 0
-__global__ void k_gsoft_stage(const unsigned char *__restrict__ src, long long stride, int strided_src, const int *__restrict__ type,
-                              long long n, double *__restrict__ dst, int *__restrict__ nbad)
+// the staged column checked in place: type-0 rows whose length is negative or not finite are counted; rows of other types become 0
+__global__ void k_gsoft_stage(const int *__restrict__ type, long long n, double *__restrict__ col, int *__restrict__ nbad)
 {
   const long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
   if(i >= n)
@@ -875,11 +725,11 @@ __global__ void k_gsoft_stage(const unsigned char *__restrict__ src, long long s
   double h = 0.0;
   if(type[i] == 0)
     {
-      h = strided_src ? *reinterpret_cast<const double *>(src + i * stride) : dst[i];
+      h = col[i];
       if(!(h >= 0.0) || isinf(h))
         atomicAdd(nbad, 1);
     }
-  dst[i] = h;
+  col[i] = h;
 }
 
 // ADAPTIVE_GRAVSOFT_FORGAS (forcetree.c:1398-1413): the caller-order copy of the gas lengths; the sorted column and the node
@@ -915,15 +765,13 @@ extern "C" int ngravs_set_gas_softening(ngravs_ctx *c, const double *hsml, int64
   DevBuf<double> &stage = c->gsoft_stage;   // checked here, swapped in when the call succeeds: a refused call changes nothing
   if(stage.ensure(n) || c->d_counters.ensure(16))
     return NGRAVS_ERR_NOMEM;
-  // host columns are packed on the host (only type-0 rows would have to be read, but the packed copy is checked on the device
-  // against the types there); device columns are read in place, type-0 rows only
+  // the whole column is staged (only type-0 rows would have to be read) and checked on the device against the types there
   int nbad = 0, rc = NGRAVS_OK;
-  if(!on_device && (rc = upload_column_f64(c, hsml, stride, 1, n, 0, stage.p)))
+  if((rc = col_upload(c, hsml, stride, sizeof(double), 1, n, on_device, stage.p)))
     return rc;
   if(hipMemsetAsync(c->d_counters.p + 15, 0, sizeof(int), c->stream) != hipSuccess)
     rc = NGRAVS_ERR_NO_DEVICE;
-  hipLaunchKernelGGL(k_gsoft_stage, GRID1(n), 0, c->stream, (const unsigned char *)hsml, (long long)stride, on_device ? 1 : 0, c->in_type.p,
-                     (long long)n, stage.p, c->d_counters.p + 15);
+  hipLaunchKernelGGL(k_gsoft_stage, GRID1(n), 0, c->stream, c->in_type.p, (long long)n, stage.p, c->d_counters.p + 15);
   if(!rc && (hipMemcpyAsync(&nbad, c->d_counters.p + 15, sizeof(int), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
              hipStreamSynchronize(c->stream) != hipSuccess || hipGetLastError() != hipSuccess))
     rc = NGRAVS_ERR_NO_DEVICE;
@@ -1394,67 +1242,6 @@ extern "C" int ngravs_compute_accelerations(ngravs_ctx *c, int pm_step)
 }
 
 // ---- results ----------------------------------------------------------------------------------------
-static int download_strided(ngravs_ctx *c, const void *dsrc, size_t elem, int ncomp, int64_t n, void *dst, int64_t stride,
-                            int on_device)
-{
-  const size_t row = elem * ncomp;
-  if(on_device)
-    {
-      if((size_t)stride != row)
-        {
-          ngravs_report(c, NGRAVS_ERR_ARG, "device outputs must be contiguous");
-          return NGRAVS_ERR_ARG;
-        }
-      HIP_TRY(c, hipMemcpyAsync(dst, dsrc, row * n, hipMemcpyDeviceToDevice, c->stream));
-      HIP_TRY(c, hipStreamSynchronize(c->stream));
-      return NGRAVS_OK;
-    }
-  if((size_t)stride == row)
-    {
-      HIP_TRY(c, hipMemcpyAsync(dst, dsrc, row * n, hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(c, hipStreamSynchronize(c->stream));
-      return NGRAVS_OK;
-    }
-  c->host_stage.resize(row * (size_t)n);
-  HIP_TRY(c, hipMemcpyAsync(c->host_stage.data(), dsrc, row * n, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  for(int64_t i = 0; i < n; i++)
-    memcpy((unsigned char *)dst + i * stride, c->host_stage.data() + i * row, row);
-  return NGRAVS_OK;
-}
-
-// device result column (caller order, contiguous) -> the caller's array; with a mask only the rows of active particles
-static int deliver(ngravs_ctx *c, const void *dsrc, size_t elem, int ncomp, int64_t n, void *dst, int64_t stride, int on_device,
-                   const unsigned char *d_mask)
-{
-  if(!d_mask)
-    return download_strided(c, dsrc, elem, ncomp, n, dst, stride, on_device);
-  const size_t row = elem * ncomp;
-  if(on_device)
-    {
-      if((size_t)stride != row)
-        {
-          ngravs_report(c, NGRAVS_ERR_ARG, "device outputs must be contiguous");
-          return NGRAVS_ERR_ARG;
-        }
-      if(elem == sizeof(double))
-        hipLaunchKernelGGL(k_copy_masked_f64, GRID1(n), 0, c->stream, d_mask, (long long)n, ncomp, (const double *)dsrc, (double *)dst);
-      else
-        hipLaunchKernelGGL(k_copy_masked_f32, GRID1(n), 0, c->stream, d_mask, (long long)n, (const float *)dsrc, (float *)dst);
-      HIP_TRY(c, hipStreamSynchronize(c->stream));
-      return NGRAVS_OK;
-    }
-  c->host_stage.resize(row * (size_t)n + (size_t)n);
-  unsigned char *hm = c->host_stage.data() + row * (size_t)n;
-  HIP_TRY(c, hipMemcpyAsync(c->host_stage.data(), dsrc, row * n, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(hm, d_mask, (size_t)n, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  for(int64_t i = 0; i < n; i++)
-    if(hm[i] & 1)
-      memcpy((unsigned char *)dst + i * stride, c->host_stage.data() + i * row, row);
-  return NGRAVS_OK;
-}
-
 extern "C" int ngravs_get_accel(ngravs_ctx *c, double *grav_accel, int64_t accel_stride, double *grav_pm, int64_t pm_stride,
                                 double *old_acc, int64_t old_acc_stride, float *grav_cost, int64_t cost_stride, int on_device,
                                 int only_active)
@@ -1478,7 +1265,7 @@ extern "C" int ngravs_get_accel(ngravs_ctx *c, double *grav_accel, int64_t accel
         return NGRAVS_ERR_STATE;
       HIP_TRY(c, hipMemsetAsync(c->out_tmp.p, 0, sizeof(double) * 3 * n, c->stream));
       hipLaunchKernelGGL(k_unpermute_f64, GRID1(n), 0, c->stream, c->s_idx.p, (long long)n, 3, c->r_acc.p, c->out_tmp.p);
-      if((rc = deliver(c, c->out_tmp.p, sizeof(double), 3, nl, grav_accel, accel_stride, on_device, mask)))
+      if((rc = col_download(c, c->out_tmp.p, sizeof(double), 3, nl, grav_accel, accel_stride, on_device, mask)))
         return rc;
     }
   if(grav_pm)
@@ -1486,7 +1273,7 @@ extern "C" int ngravs_get_accel(ngravs_ctx *c, double *grav_accel, int64_t accel
       if(!c->have_pm)
         return NGRAVS_ERR_STATE;
       hipLaunchKernelGGL(k_unpermute_f64, GRID1(n), 0, c->stream, c->s_idx.p, (long long)n, 3, c->r_pm.p, c->out_tmp.p);
-      if((rc = deliver(c, c->out_tmp.p, sizeof(double), 3, nl, grav_pm, pm_stride, on_device, nullptr)))
+      if((rc = col_download(c, c->out_tmp.p, sizeof(double), 3, nl, grav_pm, pm_stride, on_device, nullptr)))
         return rc;
     }
   if(old_acc)
@@ -1494,7 +1281,7 @@ extern "C" int ngravs_get_accel(ngravs_ctx *c, double *grav_accel, int64_t accel
       if(!c->have_acc)
         return NGRAVS_ERR_STATE;
       hipLaunchKernelGGL(k_unpermute_f64, GRID1(n), 0, c->stream, c->s_idx.p, (long long)n, 1, c->r_oldacc.p, c->out_tmp.p);
-      if((rc = deliver(c, c->out_tmp.p, sizeof(double), 1, nl, old_acc, old_acc_stride, on_device, mask)))
+      if((rc = col_download(c, c->out_tmp.p, sizeof(double), 1, nl, old_acc, old_acc_stride, on_device, mask)))
         return rc;
     }
   if(grav_cost)
@@ -1502,7 +1289,7 @@ extern "C" int ngravs_get_accel(ngravs_ctx *c, double *grav_accel, int64_t accel
       if(!c->have_acc)
         return NGRAVS_ERR_STATE;
       hipLaunchKernelGGL(k_unpermute_i2f, GRID1(n), 0, c->stream, c->s_idx.p, (long long)n, c->r_nint.p, c->out_tmpf.p);
-      if((rc = deliver(c, c->out_tmpf.p, sizeof(float), 1, nl, grav_cost, cost_stride, on_device, mask)))
+      if((rc = col_download(c, c->out_tmpf.p, sizeof(float), 1, nl, grav_cost, cost_stride, on_device, mask)))
         return rc;
     }
   return NGRAVS_OK;
@@ -1615,7 +1402,7 @@ extern "C" int ngravs_get_keys(ngravs_ctx *c, int64_t *keys, int on_device)
     return NGRAVS_ERR_NOMEM;
   long long *tmp = reinterpret_cast<long long *>(c->out_tmp.p);
   hipLaunchKernelGGL(k_key18, GRID1(n), 0, c->stream, c->in_key.p, (long long)n, tmp);
-  return download_strided(c, tmp, sizeof(long long), 1, c->n_local, keys, sizeof(long long), on_device);   // own rows
+  return col_download(c, tmp, sizeof(long long), 1, c->n_local, keys, sizeof(long long), on_device, nullptr);   // own rows
 }
 
 extern "C" int ngravs_get_order(ngravs_ctx *c, int32_t *order, int on_device)
@@ -1623,7 +1410,7 @@ extern "C" int ngravs_get_order(ngravs_ctx *c, int32_t *order, int on_device)
   if(!c || !c->have_order || !order)
     return NGRAVS_ERR_STATE;
   (void)hipSetDevice(c->cfg.device);
-  return download_strided(c, c->s_idx.p, sizeof(int), 1, c->n, order, sizeof(int), on_device);
+  return col_download(c, c->s_idx.p, sizeof(int), 1, c->n, order, sizeof(int), on_device, nullptr);
 }
 
 extern "C" int ngravs_get_shard(ngravs_ctx *c, int64_t *first, int64_t *count)
@@ -1988,7 +1775,7 @@ extern "C" int ngravs_dd_get_ids(ngravs_ctx *c, int64_t *ids, int on_device)
   (void)hipSetDevice(c->cfg.device);
   if(c->n_local == 0)
     return NGRAVS_OK;
-  return download_strided(c, c->in_id.p, sizeof(long long), 1, c->n_local, ids, sizeof(long long), on_device);
+  return col_download(c, c->in_id.p, sizeof(long long), 1, c->n_local, ids, sizeof(long long), on_device, nullptr);
 }
 
 // ---- slab-decomposed pmforce_periodic (kernels_pmslab.hip) ------------------------------------------------------------------
@@ -2052,41 +1839,10 @@ extern "C" int ngravs_pm_slab_bytes(ngravs_ctx *c, double bytes[4])
 }
 
 // ---- SPH: what ngravs_sph_density and ngravs_sph_hydro share ------------------------------------------------------------------
-static int upload_column_i32(ngravs_ctx *c, const void *src, int64_t stride, int64_t n, int on_device, int *dst)
-{
-  if(on_device)
-    {
-      if(stride == (int64_t)sizeof(int))
-        HIP_TRY(c, hipMemcpyAsync(dst, src, sizeof(int) * n, hipMemcpyDeviceToDevice, c->stream));
-      else
-        hipLaunchKernelGGL(k_pack_strided_i32, GRID1(n), 0, c->stream, (const unsigned char *)src, (long long)stride, (long long)n, dst);
-      return NGRAVS_OK;
-    }
-  c->host_stage.resize(sizeof(int) * (size_t)n);
-  int *h = reinterpret_cast<int *>(c->host_stage.data());
-  for(int64_t i = 0; i < n; i++)
-    memcpy(h + i, (const unsigned char *)src + i * stride, sizeof(int));
-  HIP_TRY(c, hipMemcpyAsync(dst, h, sizeof(int) * n, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return NGRAVS_OK;
-}
-
-// a refusal of the entry point who: reported as "<who>: <why>", nothing is written
-struct SphRefuse
-{
-  ngravs_ctx *c;
-  const char *who;
-  int operator()(int code, const char *why) const
-  {
-    ngravs_report(c, code, std::string(who) + ": " + why);
-    return code;
-  }
-};
-
 // What every SPH call does once its arguments are checked: one task, a built tree of the current particle set (refit first when
 // the particles drifted, as ngravs_gravity_tree does); then max_rounds (may be NULL) and the nms values of kernel_ms (may be NULL)
 // read 0 for a call that ends early.
-static int sph_begin(ngravs_ctx *c, const SphRefuse &refuse, int32_t *max_rounds, double *kernel_ms, int nms)
+static int sph_begin(ngravs_ctx *c, const Refuse &refuse, int32_t *max_rounds, double *kernel_ms, int nms)
 {
   if(c->cfg.world_size > 1 || c->top.on || c->n_local != c->n)
     return refuse(NGRAVS_ERR_STATE, "single task only (the neighbour search does not cross task boundaries yet)");
@@ -2107,7 +1863,7 @@ static int sph_begin(ngravs_ctx *c, const SphRefuse &refuse, int32_t *max_rounds
 static bool sph_empty(const ngravs_ctx *c) { return c->n_local == 0 || c->nnodes <= 0; }
 
 // what a density walk's statistics mean for the call: the log line, then the three ways it can have gone wrong
-static int sph_density_outcome(ngravs_ctx *c, const SphStats &st, const SphRefuse &refuse)
+static int sph_density_outcome(ngravs_ctx *c, const SphStats &st, const Refuse &refuse)
 {
   if(c->tune.sph_verbose && st.targets > 0)   // the reference logs every round of its iteration (density.c:409-414); here one line per call
     printf("ngravs_sph_density: %lld targets, rounds mean %.3f max %lld, %lld candidates tested, %lld neighbours\n", st.targets,
@@ -2125,7 +1881,7 @@ static int sph_density_outcome(ngravs_ctx *c, const SphStats &st, const SphRefus
 }
 
 // the own rows' columns that k_sph_hydro_prep / k_sph_gas_prep counted as bad
-static int sph_hydro_rows_outcome(const SphHydroStats &st, const SphRefuse &refuse)
+static int sph_hydro_rows_outcome(const SphHydroStats &st, const Refuse &refuse)
 {
   if(st.bad_hsml)
     return refuse(NGRAVS_ERR_ARG, "a type-0 row's hsml is <= 0 or not finite");
@@ -2144,7 +1900,7 @@ template <class In> static bool sph_hydro_cols_given(const In *in)
   return in && in->vel_pred && in->hsml && in->density && in->pressure && in->dhsml_factor && in->div_vel && in->curl_vel;
 }
 // the switches,
-template <class In> static int sph_hydro_switches(const In *in, const SphRefuse &refuse)
+template <class In> static int sph_hydro_switches(const In *in, const Refuse &refuse)
 {
   if(!(in->gamma >= 1) || !(in->art_bulk_visc_const >= 0) || !(in->timebase_interval >= 0))
     return refuse(NGRAVS_ERR_ARG, "gamma must be >= 1, art_bulk_visc_const and timebase_interval >= 0");
@@ -2154,20 +1910,20 @@ template <class In> static int sph_hydro_switches(const In *in, const SphRefuse 
 }
 // and, after sph_begin, the upload of the seven columns to sph_vel_in, sph_h_in and sph_col_in with SphHydroParams from the switches
 // (have_ts and the timestep columns stay with the caller)
-template <class In> static int sph_hydro_own(ngravs_ctx *c, const In *in, const SphRefuse &refuse, SphHydroParams *hp)
+template <class In> static int sph_hydro_own(ngravs_ctx *c, const In *in, const Refuse &refuse, SphHydroParams *hp)
 {
   const int64_t n = c->n_local;
   int rc;
   if(c->sph_vel_in.ensure(3 * n) || c->sph_h_in.ensure(n) || c->sph_col_in.ensure(5 * n))
     return refuse(NGRAVS_ERR_NOMEM, "device allocation failed");
-  if((rc = upload_column_f64(c, in->vel_pred, in->vel_pred_stride, 3, n, in->on_device, c->sph_vel_in.p)))
+  if((rc = col_upload(c, in->vel_pred, in->vel_pred_stride, sizeof(double), 3, n, in->on_device, c->sph_vel_in.p)))
     return rc;
-  if((rc = upload_column_f64(c, in->hsml, in->hsml_stride, 1, n, in->on_device, c->sph_h_in.p)))
+  if((rc = col_upload(c, in->hsml, in->hsml_stride, sizeof(double), 1, n, in->on_device, c->sph_h_in.p)))
     return rc;
   const double *col[5] = {in->density, in->pressure, in->dhsml_factor, in->div_vel, in->curl_vel};
   const int64_t cstride[5] = {in->density_stride, in->pressure_stride, in->dhsml_factor_stride, in->div_vel_stride, in->curl_vel_stride};
   for(int k = 0; k < 5; k++)
-    if((rc = upload_column_f64(c, col[k], cstride[k], 1, n, in->on_device, c->sph_col_in.p + k * n)))
+    if((rc = col_upload(c, col[k], cstride[k], sizeof(double), 1, n, in->on_device, c->sph_col_in.p + k * n)))
       return rc;
   hp->periodic = c->cfg.periodic;
   hp->box = c->cfg.box_size;
@@ -2214,7 +1970,7 @@ extern "C" int ngravs_sph_density(ngravs_ctx *c, const ngravs_sph_in_t *in, cons
 {
   if(!c)
     return NGRAVS_ERR_ARG;
-  const SphRefuse refuse = {c, "ngravs_sph_density"};
+  const Refuse refuse = {c, "ngravs_sph_density"};
   if(!in || !in->hsml || !in->vel_pred)
     return refuse(NGRAVS_ERR_ARG, "in, in->hsml and in->vel_pred must not be NULL");
   if(!(in->des_num_ngb > 0) || !(in->max_num_ngb_deviation >= 0) || !(in->min_gas_hsml >= 0))
@@ -2225,9 +1981,9 @@ extern "C" int ngravs_sph_density(ngravs_ctx *c, const ngravs_sph_in_t *in, cons
   const int64_t n = c->n_local;
   if(c->sph_vel_in.ensure(3 * n) || c->sph_h_in.ensure(n) || c->sph_vel.ensure(3 * n))
     return refuse(NGRAVS_ERR_NOMEM, "device allocation failed");
-  if((rc = upload_column_f64(c, in->vel_pred, in->vel_stride, 3, n, in->on_device, c->sph_vel_in.p)))
+  if((rc = col_upload(c, in->vel_pred, in->vel_stride, sizeof(double), 3, n, in->on_device, c->sph_vel_in.p)))
     return rc;
-  if((rc = upload_column_f64(c, in->hsml, in->hsml_stride, 1, n, in->on_device, c->sph_h_in.p)))
+  if((rc = col_upload(c, in->hsml, in->hsml_stride, sizeof(double), 1, n, in->on_device, c->sph_h_in.p)))
     return rc;
   HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
   hipLaunchKernelGGL(k_permute_f64, GRID1(n), 0, c->stream, c->s_idx.p, (long long)n, 3, c->sph_vel_in.p, c->sph_vel.p);
@@ -2264,7 +2020,7 @@ extern "C" int ngravs_sph_hsml_guess(ngravs_ctx *c, double des_num_ngb, double *
 {
   if(!c)
     return NGRAVS_ERR_ARG;
-  const SphRefuse refuse = {c, "ngravs_sph_hsml_guess"};
+  const Refuse refuse = {c, "ngravs_sph_hsml_guess"};
   if(!hsml || !(des_num_ngb > 0))
     return refuse(NGRAVS_ERR_ARG, "hsml must not be NULL and des_num_ngb must be > 0");
   int rc;
@@ -2275,7 +2031,7 @@ extern "C" int ngravs_sph_hsml_guess(ngravs_ctx *c, double des_num_ngb, double *
     {
       if(c->sph_h_in.ensure(n))
         return refuse(NGRAVS_ERR_NOMEM, "device allocation failed");
-      if((rc = upload_column_f64(c, hsml, hsml_stride, 1, n, on_device, c->sph_h_in.p)))
+      if((rc = col_upload(c, hsml, hsml_stride, sizeof(double), 1, n, on_device, c->sph_h_in.p)))
         return rc;
     }
   HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
@@ -2300,7 +2056,7 @@ extern "C" int ngravs_sph_hydro(ngravs_ctx *c, const ngravs_hydro_in_t *in, cons
 {
   if(!c)
     return NGRAVS_ERR_ARG;
-  const SphRefuse refuse = {c, "ngravs_sph_hydro"};
+  const Refuse refuse = {c, "ngravs_sph_hydro"};
   if(!sph_hydro_cols_given(in))
     return refuse(NGRAVS_ERR_ARG, "in and its vel_pred, hsml, density, pressure, dhsml_factor, div_vel, curl_vel must not be NULL");
   int rc;
@@ -2314,7 +2070,7 @@ extern "C" int ngravs_sph_hydro(ngravs_ctx *c, const ngravs_hydro_in_t *in, cons
     return rc;
   if(c->sph_ts_in.ensure(n))
     return refuse(NGRAVS_ERR_NOMEM, "device allocation failed");
-  if(in->timestep && (rc = upload_column_i32(c, in->timestep, in->timestep_stride, n, in->on_device, c->sph_ts_in.p)))
+  if(in->timestep && (rc = col_upload(c, in->timestep, in->timestep_stride, sizeof(int), 1, n, in->on_device, c->sph_ts_in.p)))
     return rc;
   hp.have_ts = in->timestep != nullptr;
   HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
@@ -2348,7 +2104,7 @@ extern "C" int ngravs_sph_accelerations(ngravs_ctx *c, const ngravs_gas_in_t *in
 {
   if(!c)
     return NGRAVS_ERR_ARG;
-  const SphRefuse refuse = {c, "ngravs_sph_accelerations"};
+  const Refuse refuse = {c, "ngravs_sph_accelerations"};
   if(!sph_hydro_cols_given(in) || !in->entropy)
     return refuse(NGRAVS_ERR_ARG, "in and its vel_pred, entropy, hsml, density, pressure, dhsml_factor, div_vel, curl_vel must not be NULL");
   if(!in->ti_begstep != !in->ti_endstep)
@@ -2366,12 +2122,12 @@ extern "C" int ngravs_sph_accelerations(ngravs_ctx *c, const ngravs_gas_in_t *in
     return rc;
   if(c->sph_vel.ensure(3 * n) || c->sph_gas_in.ensure(2 * n) || c->sph_ti_in.ensure(2 * n))
     return refuse(NGRAVS_ERR_NOMEM, "device allocation failed");
-  if((rc = upload_column_f64(c, in->entropy, in->entropy_stride, 1, n, in->on_device, c->sph_gas_in.p)))
+  if((rc = col_upload(c, in->entropy, in->entropy_stride, sizeof(double), 1, n, in->on_device, c->sph_gas_in.p)))
     return rc;
-  if(in->dt_entropy && (rc = upload_column_f64(c, in->dt_entropy, in->dt_entropy_stride, 1, n, in->on_device, c->sph_gas_in.p + n)))
+  if(in->dt_entropy && (rc = col_upload(c, in->dt_entropy, in->dt_entropy_stride, sizeof(double), 1, n, in->on_device, c->sph_gas_in.p + n)))
     return rc;
-  if(in->ti_begstep && ((rc = upload_column_i32(c, in->ti_begstep, in->ti_begstep_stride, n, in->on_device, c->sph_ti_in.p)) ||
-                        (rc = upload_column_i32(c, in->ti_endstep, in->ti_endstep_stride, n, in->on_device, c->sph_ti_in.p + n))))
+  if(in->ti_begstep && ((rc = col_upload(c, in->ti_begstep, in->ti_begstep_stride, sizeof(int), 1, n, in->on_device, c->sph_ti_in.p)) ||
+                        (rc = col_upload(c, in->ti_endstep, in->ti_endstep_stride, sizeof(int), 1, n, in->on_device, c->sph_ti_in.p + n))))
     return rc;
   SphGasParams gp;
   gp.des = in->des_num_ngb;
@@ -2445,32 +2201,12 @@ extern "C" int ngravs_sph_accelerations(ngravs_ctx *c, const ngravs_gas_in_t *in
 // ---- SPH sums for targets that are not own rows: density_evaluate(j, 1) / hydro_evaluate(j, 1) (kernels_sph.hip) ---------------------
 static_assert(sizeof(ngravs_sph_targets_t) == 48 && sizeof(ngravs_hydro_targets_t) == 144 && sizeof(ngravs_sph_update_out_t) == 56,
               "the Python mirror (abi.SphTargets / HydroTargets / SphUpdateOut) assumes this layout");
-// sph_tg_res [nt][ncomp] (caller order; NULL: zeros) -> the caller's contiguous array
-static int sph_write_sums(ngravs_ctx *c, const double *res, int ncomp, int64_t nt, double *out, int on_device)
-{
-  const size_t bytes = sizeof(double) * ncomp * (size_t)nt;
-  if(!res)
-    {
-      if(on_device)
-        {
-          HIP_TRY(c, hipMemsetAsync(out, 0, bytes, c->stream));
-          HIP_TRY(c, hipStreamSynchronize(c->stream));
-        }
-      else
-        memset(out, 0, bytes);
-      return NGRAVS_OK;
-    }
-  HIP_TRY(c, hipMemcpyAsync(out, res, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return NGRAVS_OK;
-}
-
 extern "C" int ngravs_sph_density_sums(ngravs_ctx *c, const double *own_vel_pred, int64_t own_vel_stride, const ngravs_sph_targets_t *tg, int64_t nt,
                                        double *sums, int32_t on_device, double *kernel_ms)
 {
   if(!c)
     return NGRAVS_ERR_ARG;
-  const SphRefuse refuse = {c, "ngravs_sph_density_sums"};
+  const Refuse refuse = {c, "ngravs_sph_density_sums"};
   if(nt < 0 || nt > 0x7fffffff)
     return refuse(NGRAVS_ERR_ARG, "nt must be >= 0 (and below 2^31)");
   if(!own_vel_pred || !tg || (nt > 0 && (!tg->pos || !tg->vel || !tg->hsml || !sums)))
@@ -2480,14 +2216,14 @@ extern "C" int ngravs_sph_density_sums(ngravs_ctx *c, const double *own_vel_pred
     return rc;
   const int64_t n = c->n_local;
   if(sph_empty(c))
-    return sph_write_sums(c, nullptr, SPH_NSUMS, nt, sums, on_device);
+    return col_deliver_or_zeros(c, nullptr, sizeof(double) * SPH_NSUMS * (size_t)nt, sums, on_device);
   if(c->sph_vel_in.ensure(3 * n) || c->sph_vel.ensure(3 * n) || c->sph_tg_in.ensure((size_t)(SPH_TG_H + 1 + 3) * nt))
     return refuse(NGRAVS_ERR_NOMEM, "device allocation failed");
-  if((rc = upload_column_f64(c, own_vel_pred, own_vel_stride, 3, n, on_device, c->sph_vel_in.p)))
+  if((rc = col_upload(c, own_vel_pred, own_vel_stride, sizeof(double), 3, n, on_device, c->sph_vel_in.p)))
     return rc;
-  if((rc = upload_column_f64(c, tg->pos, tg->pos_stride, 3, nt, on_device, c->sph_tg_in.p)) ||
-     (rc = upload_column_f64(c, tg->vel, tg->vel_stride, 3, nt, on_device, c->sph_tg_in.p + 3 * nt)) ||
-     (rc = upload_column_f64(c, tg->hsml, tg->hsml_stride, 1, nt, on_device, c->sph_tg_in.p + SPH_TG_H * nt)))
+  if((rc = col_upload(c, tg->pos, tg->pos_stride, sizeof(double), 3, nt, on_device, c->sph_tg_in.p)) ||
+     (rc = col_upload(c, tg->vel, tg->vel_stride, sizeof(double), 3, nt, on_device, c->sph_tg_in.p + 3 * nt)) ||
+     (rc = col_upload(c, tg->hsml, tg->hsml_stride, sizeof(double), 1, nt, on_device, c->sph_tg_in.p + SPH_TG_H * nt)))
     return rc;
   HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
   hipLaunchKernelGGL(k_permute_f64, GRID1(n), 0, c->stream, c->s_idx.p, (long long)n, 3, c->sph_vel_in.p, c->sph_vel.p);
@@ -2505,7 +2241,7 @@ extern "C" int ngravs_sph_density_sums(ngravs_ctx *c, const double *own_vel_pred
     printf("ngravs_sph_density_sums: %lld targets, %lld candidates tested, %lld neighbours\n", (long long)nt, st.candidates, st.pairs);
   if(st.stack_ovf)
     return refuse(NGRAVS_ERR_TREE, "the tree is deeper than the walk's stack");
-  return sph_write_sums(c, c->sph_tg_res.p, SPH_NSUMS, nt, sums, on_device);
+  return col_deliver_or_zeros(c, c->sph_tg_res.p, sizeof(double) * SPH_NSUMS * (size_t)nt, sums, on_device);
 }
 
 extern "C" int ngravs_sph_hydro_sums(ngravs_ctx *c, const ngravs_hydro_in_t *in, const ngravs_hydro_targets_t *tg, int64_t nt, double *sums,
@@ -2513,7 +2249,7 @@ extern "C" int ngravs_sph_hydro_sums(ngravs_ctx *c, const ngravs_hydro_in_t *in,
 {
   if(!c)
     return NGRAVS_ERR_ARG;
-  const SphRefuse refuse = {c, "ngravs_sph_hydro_sums"};
+  const Refuse refuse = {c, "ngravs_sph_hydro_sums"};
   if(nt < 0 || nt > 0x7fffffff)
     return refuse(NGRAVS_ERR_ARG, "nt must be >= 0 (and below 2^31)");
   if(!sph_hydro_cols_given(in))
@@ -2527,23 +2263,23 @@ extern "C" int ngravs_sph_hydro_sums(ngravs_ctx *c, const ngravs_hydro_in_t *in,
     return rc;
   const int64_t n = c->n_local;
   if(sph_empty(c))
-    return sph_write_sums(c, nullptr, SPH_HY_NRES, nt, sums, on_device);
+    return col_deliver_or_zeros(c, nullptr, sizeof(double) * SPH_HY_NRES * (size_t)nt, sums, on_device);
   SphHydroParams hp;
   if((rc = sph_hydro_own(c, in, refuse, &hp)))
     return rc;
   if(c->sph_ts_in.ensure(n) || c->sph_tg_in.ensure((size_t)(SPH_TG_NCOL + 3) * nt) || c->sph_tg_ts.ensure((size_t)nt))
     return refuse(NGRAVS_ERR_NOMEM, "device allocation failed");
-  if(in->timestep && (rc = upload_column_i32(c, in->timestep, in->timestep_stride, n, in->on_device, c->sph_ts_in.p)))
+  if(in->timestep && (rc = col_upload(c, in->timestep, in->timestep_stride, sizeof(int), 1, n, in->on_device, c->sph_ts_in.p)))
     return rc;
-  if((rc = upload_column_f64(c, tg->pos, tg->pos_stride, 3, nt, on_device, c->sph_tg_in.p)) ||
-     (rc = upload_column_f64(c, tg->vel, tg->vel_stride, 3, nt, on_device, c->sph_tg_in.p + 3 * nt)))
+  if((rc = col_upload(c, tg->pos, tg->pos_stride, sizeof(double), 3, nt, on_device, c->sph_tg_in.p)) ||
+     (rc = col_upload(c, tg->vel, tg->vel_stride, sizeof(double), 3, nt, on_device, c->sph_tg_in.p + 3 * nt)))
     return rc;
   const double *tcol[6] = {tg->hsml, tg->mass, tg->density, tg->pressure, tg->dhsml_factor, tg->f1};
   const int64_t tstride[6] = {tg->hsml_stride, tg->mass_stride, tg->density_stride, tg->pressure_stride, tg->dhsml_factor_stride, tg->f1_stride};
   for(int k = 0; k < 6; k++)
-    if((rc = upload_column_f64(c, tcol[k], tstride[k], 1, nt, on_device, c->sph_tg_in.p + (SPH_TG_H + k) * nt)))
+    if((rc = col_upload(c, tcol[k], tstride[k], sizeof(double), 1, nt, on_device, c->sph_tg_in.p + (SPH_TG_H + k) * nt)))
       return rc;
-  if(tg->timestep && (rc = upload_column_i32(c, tg->timestep, tg->timestep_stride, nt, on_device, c->sph_tg_ts.p)))
+  if(tg->timestep && (rc = col_upload(c, tg->timestep, tg->timestep_stride, sizeof(int), 1, nt, on_device, c->sph_tg_ts.p)))
     return rc;
   hp.have_ts = in->timestep != nullptr;
   HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
@@ -2568,7 +2304,7 @@ extern "C" int ngravs_sph_hydro_sums(ngravs_ctx *c, const ngravs_hydro_in_t *in,
     printf("ngravs_sph_hydro_sums: %lld targets, %lld candidates tested, %lld pairs evaluated\n", (long long)nt, st.candidates, st.pairs);
   if(st.stack_ovf)
     return refuse(NGRAVS_ERR_TREE, "the tree is deeper than the walk's stack");
-  return sph_write_sums(c, c->sph_tg_res.p, SPH_HY_NRES, nt, sums, on_device);
+  return col_deliver_or_zeros(c, c->sph_tg_res.p, sizeof(double) * SPH_HY_NRES * (size_t)nt, sums, on_device);
 }
 
 extern "C" int64_t ngravs_sph_density_update(int64_t n, const double *sums, double *hsml, double *left, double *right, int32_t *rounds,
@@ -2630,7 +2366,7 @@ extern "C" int ngravs_sph_kernel(double h, const double *r, int64_t n, double *w
 static_assert(sizeof(ngravs_grav_targets_t) == 72, "the Python mirror (abi.GravTargets) assumes this layout");
 
 // What both calls refuse before anything is staged: NULL arguments and nt < 0, several tasks, adaptive gas softening
-static int grav_targets_refusals(ngravs_ctx *c, const SphRefuse &refuse, const ngravs_grav_targets_t *t, int64_t nt, const void *result,
+static int grav_targets_refusals(ngravs_ctx *c, const Refuse &refuse, const ngravs_grav_targets_t *t, int64_t nt, const void *result,
                                  const char *result_name)
 {
   if(!t)
@@ -2640,7 +2376,7 @@ static int grav_targets_refusals(ngravs_ctx *c, const SphRefuse &refuse, const n
   if(!t->type)
     return refuse(NGRAVS_ERR_ARG, "targets->type is NULL");
   if(!result)
-    return refuse(NGRAVS_ERR_ARG, (std::string(result_name) + " is NULL").c_str());
+    return refuse(NGRAVS_ERR_ARG, std::string(result_name) + " is NULL");
   if(nt < 0 || nt > 0x7fffffff)
     return refuse(NGRAVS_ERR_ARG, "nt must be >= 0 (and below 2^31)");
   if(c->cfg.world_size > 1 || c->top.on || c->n_local != c->n)
@@ -2654,22 +2390,22 @@ static int grav_targets_refusals(ngravs_ctx *c, const SphRefuse &refuse, const n
 
 // The records into gt_in (pos[nt][3], old_acc[nt], mass[nt]) and gt_type; refused, with nothing written: a type outside 0..5, a
 // position that is not finite, or outside [0, BoxSize] in a periodic configuration.  *far: grav_targets_check
-static int grav_targets_stage(ngravs_ctx *c, const SphRefuse &refuse, const ngravs_grav_targets_t *t, int64_t nt, double *far)
+static int grav_targets_stage(ngravs_ctx *c, const Refuse &refuse, const ngravs_grav_targets_t *t, int64_t nt, double *far)
 {
   if(c->gt_in.ensure(8 * (size_t)nt) || c->gt_type.ensure((size_t)nt))
     return refuse(NGRAVS_ERR_NOMEM, "device allocation failed");
   int rc;
-  if((rc = upload_column_f64(c, t->pos, t->pos_stride, 3, nt, t->on_device, c->gt_in.p)) ||
-     (rc = upload_column_i32(c, t->type, t->type_stride, nt, t->on_device, c->gt_type.p)))
+  if((rc = col_upload(c, t->pos, t->pos_stride, sizeof(double), 3, nt, t->on_device, c->gt_in.p)) ||
+     (rc = col_upload(c, t->type, t->type_stride, sizeof(int), 1, nt, t->on_device, c->gt_type.p)))
     return rc;
   if(t->old_acc)
-    rc = upload_column_f64(c, t->old_acc, t->old_acc_stride, 1, nt, t->on_device, c->gt_in.p + 3 * nt);
+    rc = col_upload(c, t->old_acc, t->old_acc_stride, sizeof(double), 1, nt, t->on_device, c->gt_in.p + 3 * nt);
   else
     hipLaunchKernelGGL(k_fill_f64, GRID1(nt), 0, c->stream, c->gt_in.p + 3 * nt, (long long)nt, 0.0);
   if(rc)
     return rc;
   if(t->mass)
-    rc = upload_column_f64(c, t->mass, t->mass_stride, 1, nt, t->on_device, c->gt_in.p + 4 * nt);
+    rc = col_upload(c, t->mass, t->mass_stride, sizeof(double), 1, nt, t->on_device, c->gt_in.p + 4 * nt);
   else
     hipLaunchKernelGGL(k_fill_f64, GRID1(nt), 0, c->stream, c->gt_in.p + 4 * nt, (long long)nt, 1.0);
   if(rc)
@@ -2685,25 +2421,12 @@ static int grav_targets_stage(ngravs_ctx *c, const SphRefuse &refuse, const ngra
   return NGRAVS_OK;
 }
 
-// a device result column (NULL: zeros) -> the caller's contiguous array
-static int grav_targets_deliver(ngravs_ctx *c, const void *res, size_t bytes, void *out, int on_device)
-{
-  if(res)
-    HIP_TRY(c, hipMemcpyAsync(out, res, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
-  else if(on_device)
-    HIP_TRY(c, hipMemsetAsync(out, 0, bytes, c->stream));
-  else
-    memset(out, 0, bytes);
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return NGRAVS_OK;
-}
-
 extern "C" int ngravs_gravity_tree_targets(ngravs_ctx *c, const ngravs_grav_targets_t *t, int64_t nt, double *acc, int32_t *nint,
                                            double *kernel_ms)
 {
   if(!c)
     return NGRAVS_ERR_ARG;
-  const SphRefuse refuse = {c, "ngravs_gravity_tree_targets"};
+  const Refuse refuse = {c, "ngravs_gravity_tree_targets"};
   int rc;
   if((rc = grav_targets_refusals(c, refuse, t, nt, acc, "acc")))
     return rc;
@@ -2730,16 +2453,16 @@ extern "C" int ngravs_gravity_tree_targets(ngravs_ctx *c, const ngravs_grav_targ
       if(kernel_ms)
         *kernel_ms = ev_ms(c);
     }
-  if((rc = grav_targets_deliver(c, empty ? nullptr : c->gt_acc.p, sizeof(double) * 3 * (size_t)nt, acc, t->on_device)))
+  if((rc = col_deliver_or_zeros(c, empty ? nullptr : c->gt_acc.p, sizeof(double) * 3 * (size_t)nt, acc, t->on_device)))
     return rc;
-  return nint ? grav_targets_deliver(c, empty ? nullptr : c->gt_nint.p, sizeof(int) * (size_t)nt, nint, t->on_device) : NGRAVS_OK;
+  return nint ? col_deliver_or_zeros(c, empty ? nullptr : c->gt_nint.p, sizeof(int) * (size_t)nt, nint, t->on_device) : NGRAVS_OK;
 }
 
 extern "C" int ngravs_pm_targets(ngravs_ctx *c, const ngravs_grav_targets_t *t, int64_t nt, double *grav_pm)
 {
   if(!c)
     return NGRAVS_ERR_ARG;
-  const SphRefuse refuse = {c, "ngravs_pm_targets"};
+  const Refuse refuse = {c, "ngravs_pm_targets"};
   int rc;
   if((rc = grav_targets_refusals(c, refuse, t, nt, grav_pm, "grav_pm")))
     return rc;
@@ -2757,7 +2480,7 @@ extern "C" int ngravs_pm_targets(ngravs_ctx *c, const ngravs_grav_targets_t *t, 
     return refuse(NGRAVS_ERR_NOMEM, "device allocation failed");
   if((rc = pm_targets_run(c, nt, c->gt_acc.p)))
     return rc;
-  return grav_targets_deliver(c, c->gt_acc.p, sizeof(double) * 3 * (size_t)nt, grav_pm, t->on_device);
+  return col_deliver_or_zeros(c, c->gt_acc.p, sizeof(double) * 3 * (size_t)nt, grav_pm, t->on_device);
 }
 
 // ---- time integration: drift, kick and timestep assignment (run.c:32-65 around the forces; kernels_time.hip) ------------------------

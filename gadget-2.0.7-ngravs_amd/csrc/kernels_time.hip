@@ -11,6 +11,7 @@
 // once per call, no intermediate column.  The calls keep no state: the context lends its stream, its fatal handler and one scratch
 // buffer (counters, the decided steps, the tables, device copies of host columns).
 #include "engine.hpp"
+#include "columns.hpp"
 #include <cmath>
 
 #define TI_BASE NGRAVS_TIMEBASE
@@ -538,17 +539,6 @@ __global__ __launch_bounds__(TIME_BLOCK) void k_advance_apply(TCols c, AdvParams
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------------
-struct TimeRefuse
-{
-  ngravs_ctx *c;
-  const char *who;
-  int operator()(int code, const std::string &why) const
-  {
-    ngravs_report(c, code, std::string(who) + ": " + why);
-    return code;
-  }
-};
-
 static size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // The columns of one call on the device.  need: columns that must be given; gas: columns that must be given if a type-0 row exists
@@ -563,7 +553,7 @@ struct TimeStage
   int gas_ok = 1;
   unsigned staged = 0;
 
-  int begin(const TimeRefuse &refuse, unsigned need, unsigned gas, size_t scratch_bytes)
+  int begin(const Refuse &refuse, unsigned need, unsigned gas, size_t scratch_bytes)
   {
     const TCol *src = reinterpret_cast<const TCol *>(in);
     const long long n = in->n;
@@ -598,18 +588,10 @@ struct TimeStage
     for(int k = 0; k < TC_COUNT; k++)
       if(staged & TB(k))
         {
-          const size_t eb = tc_bytes[k];
-          const unsigned char *h = src[k].p;
-          if(src[k].stride != (long long)eb)
-            {
-              c->host_stage.resize(eb * (size_t)n);
-              for(long long i = 0; i < n; i++)
-                memcpy(c->host_stage.data() + i * eb, src[k].p + i * src[k].stride, eb);
-              h = c->host_stage.data();
-            }
-          HIP_TRY(c, hipMemcpy(c->time_buf.p + off[k], h, eb * (size_t)n, hipMemcpyHostToDevice));
+          if(int rc = col_upload(c, src[k].p, src[k].stride, tc_bytes[k], 1, n, 0, c->time_buf.p + off[k]))
+            return rc;
           d.c[k].p = c->time_buf.p + off[k];
-          d.c[k].stride = eb;
+          d.c[k].stride = tc_bytes[k];
         }
     return NGRAVS_OK;
   }
@@ -621,18 +603,8 @@ struct TimeStage
     const long long n = in->n;
     for(int k = 0; k < TC_COUNT; k++)
       if(staged & write & TB(k))
-        {
-          const size_t eb = tc_bytes[k];
-          if(src[k].stride == (long long)eb)
-            {
-              HIP_TRY(c, hipMemcpy(src[k].p, d.c[k].p, eb * (size_t)n, hipMemcpyDeviceToHost));
-              continue;
-            }
-          c->host_stage.resize(eb * (size_t)n);
-          HIP_TRY(c, hipMemcpy(c->host_stage.data(), d.c[k].p, eb * (size_t)n, hipMemcpyDeviceToHost));
-          for(long long i = 0; i < n; i++)
-            memcpy(src[k].p + i * src[k].stride, c->host_stage.data() + i * eb, eb);
-        }
+        if(int rc = col_download(c, d.c[k].p, tc_bytes[k], 1, n, src[k].p, src[k].stride, 0, nullptr))
+          return rc;
     return NGRAVS_OK;
   }
 };
@@ -654,7 +626,7 @@ static int time_clear_counters(ngravs_ctx *c, TimeCounters *dev)
   HIP_TRY(c, hipStreamSynchronize(c->stream));   // (z is on the stack)
   return NGRAVS_OK;
 }
-static int time_flags_outcome(const TimeRefuse &refuse, unsigned flags)
+static int time_flags_outcome(const Refuse &refuse, unsigned flags)
 {
   if(flags & TF_BAD_TYPE)
     return refuse(NGRAVS_ERR_ARG, "a type outside 0..5");
@@ -662,7 +634,7 @@ static int time_flags_outcome(const TimeRefuse &refuse, unsigned flags)
     return refuse(NGRAVS_ERR_ARG, "there is a type-0 row, but not every gas column of this call was given");
   return NGRAVS_OK;
 }
-static int time_params_check(const TimeRefuse &refuse, const ngravs_time_params_t *par)
+static int time_params_check(const Refuse &refuse, const ngravs_time_params_t *par)
 {
   if(!par)
     return refuse(NGRAVS_ERR_ARG, "params must not be NULL");
@@ -796,7 +768,7 @@ int time_dt_displacement(const ngravs_time_params_t *par, const double sums[18],
 
 int time_next_sync_point(ngravs_ctx *c, const ngravs_time_cols_t *cols, int pm_ti_endstep, ngravs_sync_t *out)
 {
-  const TimeRefuse refuse = {c, "ngravs_next_sync_point"};
+  const Refuse refuse = {c, "ngravs_next_sync_point"};
   if(!cols || !out)
     return refuse(NGRAVS_ERR_ARG, "cols and out must not be NULL");
   if(cols->n <= 0)
@@ -823,7 +795,7 @@ int time_next_sync_point(ngravs_ctx *c, const ngravs_time_cols_t *cols, int pm_t
 
 int time_displacement_sums(ngravs_ctx *c, const ngravs_time_cols_t *cols, double sums[18])
 {
-  const TimeRefuse refuse = {c, "ngravs_displacement_sums"};
+  const Refuse refuse = {c, "ngravs_displacement_sums"};
   if(!cols || !sums)
     return refuse(NGRAVS_ERR_ARG, "cols and sums must not be NULL");
   const size_t off_part = up256(sizeof(TimeCounters)), off_out = off_part + up256(sizeof(double) * 18 * TIME_MAX_GRID);
@@ -854,7 +826,7 @@ static const unsigned TIME_GAS_ADVANCE = TB(TC_VP) | TB(TC_HA) | TB(TC_ENT) | TB
 
 int time_move_particles(ngravs_ctx *c, const ngravs_time_cols_t *cols, const ngravs_time_params_t *par, int time0, int time1, int wrap)
 {
-  const TimeRefuse refuse = {c, "ngravs_move_particles"};
+  const Refuse refuse = {c, "ngravs_move_particles"};
   if(!cols)
     return refuse(NGRAVS_ERR_ARG, "cols must not be NULL");
   int rc;
@@ -909,7 +881,7 @@ int time_move_particles(ngravs_ctx *c, const ngravs_time_cols_t *cols, const ngr
 int time_advance(ngravs_ctx *c, const ngravs_time_cols_t *cols, const ngravs_time_params_t *par, int ti_current, double dt_displacement,
                  int32_t *pm_ti, int64_t *n_kicked)
 {
-  const TimeRefuse refuse = {c, "ngravs_advance_and_find_timesteps"};
+  const Refuse refuse = {c, "ngravs_advance_and_find_timesteps"};
   if(!cols)
     return refuse(NGRAVS_ERR_ARG, "cols must not be NULL");
   int rc;
@@ -939,9 +911,10 @@ int time_advance(ngravs_ctx *c, const ngravs_time_cols_t *cols, const ngravs_tim
   p.tabs = time_host_tabs(par, dtab);
   if(par->comoving)
     {
-      HIP_TRY(c, hipMemcpy(dtab, par->drift_table, sizeof(double) * TT_LEN, hipMemcpyHostToDevice));
-      HIP_TRY(c, hipMemcpy(dtab + TT_LEN, par->gravkick_table, sizeof(double) * TT_LEN, hipMemcpyHostToDevice));
-      HIP_TRY(c, hipMemcpy(dtab + 2 * TT_LEN, par->hydrokick_table, sizeof(double) * TT_LEN, hipMemcpyHostToDevice));
+      const double *tab[3] = {par->drift_table, par->gravkick_table, par->hydrokick_table};
+      for(int k = 0; k < 3; k++)
+        if((rc = col_upload(c, tab[k], sizeof(double), sizeof(double), 1, TT_LEN, 0, dtab + k * TT_LEN)))
+          return rc;
       const double time = par->time_begin * exp(ti_current * par->timebase_interval);   // All.Time (run.c:231-234)
       p.fac1 = 1 / (time * time);
       p.fac2 = 1 / pow(time, 3 * par->gamma - 2);
