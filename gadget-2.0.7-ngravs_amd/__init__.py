@@ -46,6 +46,7 @@ EXPORTS = [
     "ngravs_gravity_tree_targets", "ngravs_pm_targets",
     "ngravs_time_tables", "ngravs_time_factors", "ngravs_next_sync_point", "ngravs_move_particles", "ngravs_displacement_sums",
     "ngravs_dt_displacement", "ngravs_advance_and_find_timesteps",
+    "ngravs_global_sums", "ngravs_global_finish", "ngravs_energy_line",
 ]
 # include/ngravs_host.h (plain-C multi-task drivers over a communicator vtable, linked into the same library)
 HOST_EXPORTS = ["ngravs_host_comm_selftest", "ngravs_host_kept_step", "ngravs_host_toptree_borrow", "ngravs_host_domain_decomposition", "ngravs_host_domain_owners", "ngravs_host_domain_halo",
@@ -151,6 +152,9 @@ def lib():
         L.ngravs_displacement_sums.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.ngravs_dt_displacement.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p]
         L.ngravs_advance_and_find_timesteps.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p]
+        L.ngravs_global_sums.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        L.ngravs_global_finish.argtypes = [C.c_void_p, C.c_void_p]
+        L.ngravs_energy_line.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_int64]
         _LIB = L
     return _LIB
 
@@ -275,6 +279,27 @@ def dt_displacement(par, sums, G, asmth, time):
     if rc != 0:
         raise NgravsError("ngravs_dt_displacement: %d" % rc)
     return float(out.value)
+
+
+def global_finish(sums):
+    """compute_global_quantities_of_system() after its MPI_Reduce (global.c:130-194) from the (all-reduced) 78 sums of
+    Engine.global_sums: abi.SysState, the reference's struct state_of_system.  No GPU needed."""
+    sums = np.ascontiguousarray(sums, dtype=np.float64)
+    assert sums.shape == (abi.GLOBAL_NSUMS,)
+    out = abi.SysState()
+    rc = lib().ngravs_global_finish(sums.ctypes.data, C.byref(out))
+    if rc != 0:
+        raise NgravsError("ngravs_global_finish: %d" % rc)
+    return out
+
+
+def energy_line(state, time):
+    """the line energy_statistics() appends to energy.txt (run.c:419-429) for an abi.SysState at All.Time = time.  No GPU needed."""
+    buf = C.create_string_buffer(1024)
+    rc = lib().ngravs_energy_line(C.byref(state), float(time), buf, len(buf))
+    if rc < 0:
+        raise NgravsError("ngravs_energy_line: %d" % rc)
+    return buf.raw[:rc].decode()
 
 
 def _ptr(a):
@@ -889,6 +914,28 @@ class Engine:
         self._check(lib().ngravs_advance_and_find_timesteps(self._h, C.byref(tc), C.byref(par), int(ti_current), float(dt_displacement), pm,
                                                             C.byref(kicked)), "ngravs_advance_and_find_timesteps")
         return int(kicked.value), (None if pm is None else [int(pm[0]), int(pm[1])])
+
+    def global_sums(self, cols, par, ti_current, pm_ti=None, potential=None):
+        """the task's 78 sums of compute_global_quantities_of_system() (global.c:52-114) at All.Ti_Current = ti_current: float64
+        [78], [13 * type + k] with k = mass, kinetic, internal and potential energy, m vel [3], m pos x vel [3], m pos [3].  cols
+        holds type, pos, vel, mass, ti_begstep, ti_endstep, grav_accel, grav_pm (with a mesh), and for gas hydro_accel, entropy,
+        dt_entropy, density; nothing is written.  pm_ti: [PM_Ti_begstep, PM_Ti_endstep] with a mesh.  potential: None (EnergyPot
+        is 0 then), or P[].Potential, float64 [n] of the kind of the columns.  A host with several tasks adds the sums of its
+        tasks before global_finish()."""
+        tc, keep = self._time_cols(cols)
+        pot = None
+        if potential is not None:
+            pcol, addr = _columns(dict(potential=potential), dict(potential=(int(tc.n),)), bool(tc.on_device))
+            pot = addr(pcol["potential"])
+        pm = (C.c_int32 * 2)(*[int(x) for x in pm_ti]) if pm_ti is not None else None
+        sums = np.zeros(abi.GLOBAL_NSUMS)
+        self._check(lib().ngravs_global_sums(self._h, C.byref(tc), C.byref(par), int(ti_current), pm, pot, 8, sums.ctypes.data),
+                    "ngravs_global_sums")
+        return sums
+
+    def global_quantities(self, cols, par, ti_current, pm_ti=None, potential=None):
+        """compute_global_quantities_of_system() for one task: global_finish(global_sums(...)), an abi.SysState"""
+        return global_finish(self.global_sums(cols, par, ti_current, pm_ti, potential))
 
     def direct_sum(self, idx):
         idx = np.ascontiguousarray(idx, dtype=np.int32)

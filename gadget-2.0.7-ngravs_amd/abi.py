@@ -257,6 +257,17 @@ def make_time_params(tables=None, **kw):
     return par
 
 
+GLOBAL_NSUMS = 78   # NGRAVS_GLOBAL_NSUMS: 13 sums for each of the 6 types
+
+
+class SysState(C.Structure):
+    """ngravs_sysstate_t: struct state_of_system of the reference (allvars.h), 119 doubles"""
+    _fields_ = [(k, C.c_double) for k in ("Mass", "EnergyKin", "EnergyPot", "EnergyInt", "EnergyTot")] + [
+        (k, C.c_double * 4) for k in ("Momentum", "AngMomentum", "CenterOfMass")] + [
+        (k, C.c_double * 6) for k in ("MassComp", "EnergyKinComp", "EnergyPotComp", "EnergyIntComp", "EnergyTotComp")] + [
+        (k, C.c_double * 4 * 6) for k in ("MomentumComp", "AngMomentumComp", "CenterOfMassComp")]
+
+
 class GravTargets(C.Structure):
     """ngravs_grav_targets_t"""
     _fields_ = [f for k in GRAV_TARGET_NAMES for f in ((k, C.c_void_p), (k + "_stride", C.c_int64))] + [("on_device", C.c_int32)]

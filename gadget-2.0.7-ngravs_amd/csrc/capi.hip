@@ -2517,3 +2517,17 @@ extern "C" int ngravs_advance_and_find_timesteps(ngravs_ctx *c, const ngravs_tim
 {
   return c ? time_advance(c, cols, par, ti_current, dt_displacement, pm_ti, n_kicked) : NGRAVS_ERR_ARG;
 }
+static_assert(sizeof(ngravs_sysstate_t) == 952, "struct state_of_system (allvars.h): 119 doubles; the Python mirror is abi.SysState");
+extern "C" int ngravs_global_sums(ngravs_ctx *c, const ngravs_time_cols_t *cols, const ngravs_time_params_t *par, int32_t ti_current,
+                                  const int32_t *pm_ti, const double *potential, int64_t potential_stride, double sums[NGRAVS_GLOBAL_NSUMS])
+{
+  return c ? time_global_sums(c, cols, par, ti_current, pm_ti, potential, potential_stride, sums) : NGRAVS_ERR_ARG;
+}
+extern "C" int ngravs_global_finish(const double sums[NGRAVS_GLOBAL_NSUMS], ngravs_sysstate_t *out)
+{
+  return sums && out ? time_global_finish(sums, out) : NGRAVS_ERR_ARG;
+}
+extern "C" int ngravs_energy_line(const ngravs_sysstate_t *s, double time, char *buf, int64_t len)
+{
+  return s && buf ? time_energy_line(s, time, buf, len) : NGRAVS_ERR_ARG;
+}

@@ -698,3 +698,7 @@ int time_move_particles(ngravs_ctx *c, const ngravs_time_cols_t *cols, const ngr
 int time_displacement_sums(ngravs_ctx *c, const ngravs_time_cols_t *cols, double sums[18]);
 int time_advance(ngravs_ctx *c, const ngravs_time_cols_t *cols, const ngravs_time_params_t *par, int ti_current, double dt_displacement,
                  int32_t *pm_ti, int64_t *n_kicked);
+int time_global_sums(ngravs_ctx *c, const ngravs_time_cols_t *cols, const ngravs_time_params_t *par, int ti_current, const int32_t *pm_ti,
+                     const double *potential, int64_t potential_stride, double sums[NGRAVS_GLOBAL_NSUMS]);
+int time_global_finish(const double sums[NGRAVS_GLOBAL_NSUMS], ngravs_sysstate_t *out);
+int time_energy_line(const ngravs_sysstate_t *s, double time, char *buf, int64_t len);

@@ -6,6 +6,8 @@
 //   advance_and_find_timesteps       timestep.c:24-413   k_advance_decide, k_advance_apply
 //   get_timestep                     timestep.c:427-576  k_advance_decide
 //   init_drift_table, get_*_factor   driftfac.c:26-212   time_tables (host), time_factor (host and device)
+//   compute_global_quantities_of_system  global.c:22-198 k_global_sums + k_global_final, time_global_finish (host)
+//   energy_statistics                run.c:413-433       time_energy_line (host)
 //
 // Streaming kernels over the caller's own columns (pointer + byte stride per field, any layout): every byte is read once and written
 // once per call, no intermediate column.  The calls keep no state: the context lends its stream, its fatal handler and one scratch
@@ -239,6 +241,134 @@ __global__ void k_disp_final(const double *partial, int nblocks, double *out)
       v = (k >= 6 && k < 12) ? (w < v ? w : v) : v + w;
     }
   out[k] = v;
+}
+
+// ---- compute_global_quantities_of_system (global.c:52-114): 13 sums per type, one partial of 78 numbers per block ------------------
+#define GQ_NK 13                        // mass, kinetic, internal, potential, momentum[3], angular momentum[3], mass x position[3]
+#define GQ_NSUMS NGRAVS_GLOBAL_NSUMS    // GQ_NK per type
+#define GQ_SPLIT 8                      // k_global_final: runs of TIME_MAX_GRID / GQ_SPLIT blocks
+static_assert(GQ_NSUMS == GQ_NK * NGRAVS_NTYPES && TIME_MAX_GRID % GQ_SPLIT == 0 && GQ_NSUMS * GQ_SPLIT <= 1024, "k_global_final is one block");
+struct GlobalParams
+{
+  TimeTabs tabs;
+  double tbi, dt_pm, a1, a2, a3, gm1;   // dt_pm: the long-range half-step prediction (global.c:79-84), once per call on the host
+  int ti_current, comoving, mesh, isotherm;
+};
+// A row's type is data, and 78 accumulators per lane are not to live in registers: they live in LDS as acc[k][type][lane], 64 lanes
+// wide, 39 KiB for the block.  The block's four waves share the 64 lane columns and take turns on them with a barrier between the
+// turns, so a cell is only ever touched by the one thread whose turn it is, and it sees its rows in the order (trip, wave) that the
+// grid alone fixes.  Adding a row's terms is a read-add-write of 13 cells without a bank conflict (consecutive lanes, consecutive
+// cells).  At the end each cell column is added up over the lanes by the shuffle tree, and the block stores its 78 numbers: no
+// floating-point atomic anywhere, the same bits on every call with the same columns.  (Four blocks fill a CU's LDS: the launch bound
+// asks for the four waves per SIMD that go with them.)
+__global__ __launch_bounds__(TIME_BLOCK, 4) void k_global_sums(TCols c, TCol pot, GlobalParams p, int gas_ok, double *__restrict__ partial,
+                                                            TimeCounters *cnt)
+{
+  __shared__ double acc[GQ_NSUMS * 64];
+  __shared__ unsigned ldsf[4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for(int e = threadIdx.x; e < GQ_NSUMS * 64; e += TIME_BLOCK)
+    acc[e] = 0;
+  unsigned f = 0;
+  const long long n = c.n;
+  // (the trip count is the block's, not the thread's: there are barriers inside)
+  for(long long base = blockIdx.x * (long long)TIME_BLOCK; base < n; base += (long long)gridDim.x * TIME_BLOCK)
+    {
+      const long long i = base + threadIdx.x;
+      int ty = -1;   // no row, or a row that is refused
+      double t[GQ_NK];
+      if(i < n)
+        {
+          const int ty0 = ldi(c.c[TC_TYPE], i);
+          if(ty0 < 0 || ty0 >= NGRAVS_NTYPES)
+            f |= TF_BAD_TYPE;
+          else if(ty0 == 0 && !gas_ok)
+            f |= TF_GAS_MISSING;
+          else
+            {
+              ty = ty0;
+              const bool gas = ty == 0;
+              const double m = ldd(c.c[TC_MASS], i);
+              const int beg = ldi(c.c[TC_TIB], i), mid = (beg + ldi(c.c[TC_TIE], i)) / 2;
+              const double dt_entr = (p.ti_current - mid) * p.tbi;   // global.c:58-68
+              double dt_gravkick = dt_entr, dt_hydrokick = dt_entr;
+              if(p.comoving)
+                {
+                  dt_gravkick = p.tabs.gravkick(beg, p.ti_current) - p.tabs.gravkick(beg, mid);
+                  if(gas)
+                    dt_hydrokick = p.tabs.hydrokick(beg, p.ti_current) - p.tabs.hydrokick(beg, mid);
+                }
+              double pos[3], vel[3];
+              for(int j = 0; j < 3; j++)   // global.c:70-88
+                {
+                  pos[j] = ldd(c.c[TC_POS], i, j);
+                  vel[j] = ldd(c.c[TC_VEL], i, j) + ldd(c.c[TC_GA], i, j) * dt_gravkick;
+                  if(gas)
+                    vel[j] += ldd(c.c[TC_HA], i, j) * dt_hydrokick;
+                  if(p.mesh)
+                    vel[j] += ldd(c.c[TC_GPM], i, j) * p.dt_pm;
+                }
+              t[0] = m;
+              t[1] = 0.5 * m * (vel[0] * vel[0] + vel[1] * vel[1] + vel[2] * vel[2]) / p.a2;
+              t[2] = 0;
+              if(gas)   // global.c:76-77, 93-101
+                {
+                  const double entr = ldd(c.c[TC_ENT], i) + ldd(c.c[TC_DTE], i) * dt_entr;
+                  t[2] = m * (p.isotherm ? entr : entr / p.gm1 * pow(ldd(c.c[TC_RHO], i) / p.a3, p.gm1));
+                }
+              t[3] = pot.p ? 0.5 * m * ldd(pot, i) / p.a1 : 0.0;
+              for(int j = 0; j < 3; j++)
+                {
+                  t[4 + j] = m * vel[j];
+                  t[10 + j] = m * pos[j];
+                }
+              t[7] = m * (pos[1] * vel[2] - pos[2] * vel[1]);
+              t[8] = m * (pos[2] * vel[0] - pos[0] * vel[2]);
+              t[9] = m * (pos[0] * vel[1] - pos[1] * vel[0]);
+            }
+        }
+      for(int w = 0; w < TIME_BLOCK / 64; w++)
+        {
+          __syncthreads();
+          if(w == wave && ty >= 0)
+            {
+              double *cell = acc + ty * 64 + lane;
+#pragma unroll
+              for(int k = 0; k < GQ_NK; k++)
+                cell[k * NGRAVS_NTYPES * 64] += t[k];
+            }
+        }
+    }
+  __syncthreads();
+  for(int e = wave; e < GQ_NSUMS; e += TIME_BLOCK / 64)
+    {
+      const double v = wave_reduce(acc[e * 64 + lane], OpAdd());
+      if(lane == 0)
+        partial[blockIdx.x * (long long)GQ_NSUMS + (e % NGRAVS_NTYPES) * GQ_NK + e / NGRAVS_NTYPES] = v;   // [type][k], as the caller gets it
+    }
+  f = block_reduce(f, OpOr(), ldsf);
+  if(threadIdx.x == 0 && f)
+    atomicOr(&cnt->flags, f);
+}
+// One block.  Thread (run, e) adds entry e of the blocks of its run in block order, then thread (0, e) adds the runs in their order:
+// for up to TIME_MAX_GRID / GQ_SPLIT blocks that is the plain sum in block order, and always an order that the grid alone fixes.
+__global__ __launch_bounds__(GQ_NSUMS *GQ_SPLIT) void k_global_final(const double *__restrict__ partial, int nblocks, double *__restrict__ out)
+{
+  __shared__ double runs[GQ_SPLIT * GQ_NSUMS];
+  const int e = threadIdx.x % GQ_NSUMS, run = threadIdx.x / GQ_NSUMS;
+  const int b0 = run * (TIME_MAX_GRID / GQ_SPLIT);
+  const int b1 = b0 + TIME_MAX_GRID / GQ_SPLIT < nblocks ? b0 + TIME_MAX_GRID / GQ_SPLIT : nblocks;
+  double v = 0;
+  for(int b = b0; b < b1; b++)
+    v += partial[b * GQ_NSUMS + e];
+  runs[run * GQ_NSUMS + e] = v;
+  __syncthreads();
+  if(run == 0)
+    {
+      for(int r = 1; r < GQ_SPLIT; r++)
+        v += runs[r * GQ_NSUMS + e];
+      out[e] = v;
+    }
 }
 
 // ---- move_particles (predict.c:31-76) and do_box_wrapping (predict.c:124-132) -------------------------------------------------------
@@ -820,7 +950,175 @@ int time_displacement_sums(ngravs_ctx *c, const ngravs_time_cols_t *cols, double
   return NGRAVS_OK;
 }
 
-static const unsigned TIME_GAS_MOVE = TB(TC_GA) | TB(TC_VP) | TB(TC_HA) | TB(TC_ENT) | TB(TC_DTE) | TB(TC_RHO) | TB(TC_H) | TB(TC_PRES) | TB(TC_DIV) |
+// compute_global_quantities_of_system up to its MPI_Reduce (global.c:32-114): the task's 78 sums
+int time_global_sums(ngravs_ctx *c, const ngravs_time_cols_t *cols, const ngravs_time_params_t *par, int ti_current, const int32_t *pm_ti,
+                     const double *potential, int64_t potential_stride, double sums[GQ_NSUMS])
+{
+  const Refuse refuse = {c, "ngravs_global_sums"};
+  if(!cols || !sums)
+    return refuse(NGRAVS_ERR_ARG, "cols and sums must not be NULL");
+  int rc;
+  if((rc = time_params_check(refuse, par)))
+    return rc;
+  const int mesh = c->cfg.pmgrid > 0;
+  if(mesh && !pm_ti)
+    return refuse(NGRAVS_ERR_ARG, "a configuration with a mesh needs pm_ti");
+  if(ti_current < 0 || ti_current > TI_BASE)
+    return refuse(NGRAVS_ERR_ARG, "ti_current outside the integer time line");
+  if(mesh && (pm_ti[0] < 0 || pm_ti[1] < pm_ti[0] || pm_ti[1] > TI_BASE))
+    return refuse(NGRAVS_ERR_ARG, "pm_ti is not a step on the integer time line");
+  const long long n = cols->n;
+  if(potential && potential_stride < (int64_t)sizeof(double) && n > 1)
+    return refuse(NGRAVS_ERR_ARG, "potential_stride is smaller than the field");
+  const bool pot_staged = potential && !cols->on_device;
+  const size_t off_tab = up256(sizeof(TimeCounters)), off_part = off_tab + up256(sizeof(double) * 3 * TT_LEN),
+               off_out = off_part + up256(sizeof(double) * GQ_NSUMS * TIME_MAX_GRID), off_pot = off_out + up256(sizeof(double) * GQ_NSUMS);
+  TimeStage st = {c, cols};
+  if((rc = st.begin(refuse, TB(TC_TYPE) | TB(TC_POS) | TB(TC_VEL) | TB(TC_MASS) | TB(TC_TIB) | TB(TC_TIE) | TB(TC_GA) | (mesh ? TB(TC_GPM) : 0),
+                    TB(TC_HA) | TB(TC_ENT) | TB(TC_DTE) | TB(TC_RHO), off_pot + (pot_staged ? sizeof(double) * (size_t)n : 0))))
+    return rc;
+  if(n == 0)   // a task that owns no rows
+    {
+      memset(sums, 0, sizeof(double) * GQ_NSUMS);
+      return NGRAVS_OK;
+    }
+  TimeCounters *cnt = reinterpret_cast<TimeCounters *>(st.scratch), h;
+  double *dtab = reinterpret_cast<double *>(st.scratch + off_tab), *partial = reinterpret_cast<double *>(st.scratch + off_part),
+         *dout = reinterpret_cast<double *>(st.scratch + off_out);
+  TCol pot = {nullptr, 0};
+  if(pot_staged)
+    {
+      if((rc = col_upload(c, potential, potential_stride, sizeof(double), 1, n, 0, st.scratch + off_pot)))
+        return rc;
+      pot.p = st.scratch + off_pot, pot.stride = sizeof(double);
+    }
+  else if(potential)
+    pot.p = reinterpret_cast<unsigned char *>(const_cast<double *>(potential)), pot.stride = potential_stride;
+
+  GlobalParams p;
+  memset(&p, 0, sizeof p);
+  p.tabs = time_host_tabs(par, dtab);
+  p.tbi = par->timebase_interval;
+  p.a1 = p.a2 = p.a3 = 1;
+  p.gm1 = par->gamma - 1;
+  p.isotherm = par->gamma == 1;
+  p.ti_current = ti_current;
+  p.comoving = par->comoving != 0;
+  p.mesh = mesh;
+  if(par->comoving)
+    {
+      const double *tab[3] = {par->drift_table, par->gravkick_table, par->hydrokick_table};
+      for(int k = 0; k < 3; k++)
+        if((rc = col_upload(c, tab[k], sizeof(double), sizeof(double), 1, TT_LEN, 0, dtab + k * TT_LEN)))
+          return rc;
+      const double time = par->time_begin * exp(ti_current * par->timebase_interval);   // All.Time (run.c:231-234)
+      p.a1 = time, p.a2 = time * time, p.a3 = time * time * time;
+    }
+  if(mesh)   // global.c:79-84
+    {
+      const TimeTabs hg = time_host_tabs(par, par->gravkick_table);
+      const int pmb = pm_ti[0], mid = (pm_ti[0] + pm_ti[1]) / 2;
+      if(par->comoving)
+        p.dt_pm = time_factor(hg.t, hg.ltb, hg.ltm, hg.tbi, pmb, ti_current) - time_factor(hg.t, hg.ltb, hg.ltm, hg.tbi, pmb, mid);
+      else
+        p.dt_pm = (ti_current - mid) * par->timebase_interval;
+    }
+  if((rc = time_clear_counters(c, cnt)))
+    return rc;
+  const unsigned grid = time_grid(n);
+  hipLaunchKernelGGL(k_global_sums, dim3(grid), dim3(TIME_BLOCK), 0, c->stream, st.d, pot, p, st.gas_ok, partial, cnt);
+  hipLaunchKernelGGL(k_global_final, dim3(1), dim3(GQ_NSUMS * GQ_SPLIT), 0, c->stream, partial, (int)grid, dout);
+  HIP_TRY(c, hipGetLastError());
+  double hs[GQ_NSUMS];
+  HIP_TRY(c, hipMemcpyAsync(hs, dout, sizeof hs, hipMemcpyDeviceToHost, c->stream));
+  if((rc = time_read_counters(c, cnt, &h)) || (rc = time_flags_outcome(refuse, h.flags)))
+    return rc;
+  memcpy(sums, hs, sizeof hs);
+  return NGRAVS_OK;
+}
+
+// compute_global_quantities_of_system after its MPI_Reduce (global.c:130-194), in the reference's order of operations
+int time_global_finish(const double sums[GQ_NSUMS], ngravs_sysstate_t *out)
+{
+#pragma clang fp contract(off)
+  ngravs_sysstate_t s;
+  memset(&s, 0, sizeof s);
+  for(int i = 0; i < 6; i++)
+    {
+      const double *t = sums + GQ_NK * i;
+      s.MassComp[i] = t[0], s.EnergyKinComp[i] = t[1], s.EnergyIntComp[i] = t[2], s.EnergyPotComp[i] = t[3];
+      for(int j = 0; j < 3; j++)
+        s.MomentumComp[i][j] = t[4 + j], s.AngMomentumComp[i][j] = t[7 + j], s.CenterOfMassComp[i][j] = t[10 + j];
+      s.EnergyTotComp[i] = s.EnergyKinComp[i] + s.EnergyPotComp[i] + s.EnergyIntComp[i];
+    }
+  for(int i = 0; i < 6; i++)
+    {
+      s.Mass += s.MassComp[i];
+      s.EnergyKin += s.EnergyKinComp[i];
+      s.EnergyPot += s.EnergyPotComp[i];
+      s.EnergyInt += s.EnergyIntComp[i];
+      s.EnergyTot += s.EnergyTotComp[i];
+      for(int j = 0; j < 3; j++)
+        {
+          s.Momentum[j] += s.MomentumComp[i][j];
+          s.AngMomentum[j] += s.AngMomentumComp[i][j];
+          s.CenterOfMass[j] += s.CenterOfMassComp[i][j];
+        }
+    }
+  for(int i = 0; i < 6; i++)
+    for(int j = 0; j < 3; j++)
+      if(s.MassComp[i] > 0)
+        s.CenterOfMassComp[i][j] /= s.MassComp[i];
+  for(int j = 0; j < 3; j++)
+    if(s.Mass > 0)
+      s.CenterOfMass[j] /= s.Mass;
+  for(int i = 0; i < 6; i++)
+    {
+      for(int j = 0; j < 3; j++)
+        {
+          s.CenterOfMassComp[i][3] += s.CenterOfMassComp[i][j] * s.CenterOfMassComp[i][j];
+          s.MomentumComp[i][3] += s.MomentumComp[i][j] * s.MomentumComp[i][j];
+          s.AngMomentumComp[i][3] += s.AngMomentumComp[i][j] * s.AngMomentumComp[i][j];
+        }
+      s.CenterOfMassComp[i][3] = sqrt(s.CenterOfMassComp[i][3]);
+      s.MomentumComp[i][3] = sqrt(s.MomentumComp[i][3]);
+      s.AngMomentumComp[i][3] = sqrt(s.AngMomentumComp[i][3]);
+    }
+  for(int j = 0; j < 3; j++)
+    {
+      s.CenterOfMass[3] += s.CenterOfMass[j] * s.CenterOfMass[j];
+      s.Momentum[3] += s.Momentum[j] * s.Momentum[j];
+      s.AngMomentum[3] += s.AngMomentum[j] * s.AngMomentum[j];
+    }
+  s.CenterOfMass[3] = sqrt(s.CenterOfMass[3]);
+  s.Momentum[3] = sqrt(s.Momentum[3]);
+  s.AngMomentum[3] = sqrt(s.AngMomentum[3]);
+  *out = s;
+  return NGRAVS_OK;
+}
+
+// the energy.txt line of energy_statistics (run.c:419-429): 28 fields and a newline; the length, or NGRAVS_ERR_ARG for a short buffer
+int time_energy_line(const ngravs_sysstate_t *s, double time, char *buf, int64_t len)
+{
+  double v[28] = {time, s->EnergyInt, s->EnergyPot, s->EnergyKin};
+  for(int i = 0; i < 6; i++)
+    {
+      v[4 + 3 * i] = s->EnergyIntComp[i], v[5 + 3 * i] = s->EnergyPotComp[i], v[6 + 3 * i] = s->EnergyKinComp[i];
+      v[22 + i] = s->MassComp[i];
+    }
+  char line[28 * 32];
+  int at = 0;
+  for(int k = 0; k < 28; k++)
+    at += snprintf(line + at, sizeof line - at, k ? " %g" : "%g", v[k]);
+  line[at++] = '\n';
+  if(len < at + 1)
+    return NGRAVS_ERR_ARG;
+  memcpy(buf, line, at);
+  buf[at] = 0;
+  return at;
+}
+
+static const unsigned TIME_GAS_MOVE =TB(TC_GA) | TB(TC_VP) | TB(TC_HA) | TB(TC_ENT) | TB(TC_DTE) | TB(TC_RHO) | TB(TC_H) | TB(TC_PRES) | TB(TC_DIV) |
                                       TB(TC_TIB) | TB(TC_TIE);
 static const unsigned TIME_GAS_ADVANCE = TB(TC_VP) | TB(TC_HA) | TB(TC_ENT) | TB(TC_DTE) | TB(TC_RHO) | TB(TC_H) | TB(TC_MSV);
 

@@ -9,7 +9,7 @@ cols is the host's P[] and SphP[] as a dict of columns, numpy arrays or contiguo
 for type and the two Ti columns): type, pos, vel, mass, ti_begstep, ti_endstep, grav_accel, grav_pm, old_acc, and with gas
 vel_pred, hydro_accel, entropy, dt_entropy, density, hsml, pressure, div_vel, curl_vel, dhsml_factor, max_signal_vel.  All are
 updated in place.  With device tensors no column crosses to the host: the loop reads back the scalars of the sync point and,
-on full steps, the 18 displacement sums.
+on full steps, the 18 displacement sums, and with time_bet_statistics the 78 sums of the energy statistics (run.c:52-59) when due.
 """
 import ctypes as C
 import math
@@ -31,13 +31,19 @@ class Timeline:
     """ti_current, time, pm_ti ([PM_Ti_begstep, PM_Ti_endstep], None without a mesh), dt_displacement, full_step and n_active
     are the reference's globals of the same names after the last step()."""
 
-    def __init__(self, engine, cols, par, sph=None, tree_domain_update_frequency=0.0, softening=None, on_station=None):
+    def __init__(self, engine, cols, par, sph=None, tree_domain_update_frequency=0.0, softening=None, on_station=None,
+                 time_bet_statistics=None, energy_file=None, potential=None):
         """par: abi.make_time_params(...).  sph: the keyword arguments of Engine.sph_accelerations that are not columns or times
         (des_num_ngb, max_num_ngb_deviation, art_bulk_visc_const, ...), required with gas.  tree_domain_update_frequency:
         All.TreeDomainUpdateFrequency (domain.c:66-76); 0 decomposes and builds on every step.  softening: None, or a function
         of All.Time that returns All.ForceSoftening[6] (set_softenings(), gravtree.c:468-518, for comoving runs).  on_station:
         None, or a function called as on_station(name, timeline) in front of the stations "drift" and "advance", when the particles
-        have "moved", and at the "end" of a step.  The reference's start (init.c): Ti_begstep = Ti_endstep = 0 for every row, Ti_Current = 0."""
+        have "moved", and at the "end" of a step.  The reference's start (init.c): Ti_begstep = Ti_endstep = 0 for every row, Ti_Current = 0.
+        time_bet_statistics: None (no energy statistics), or All.TimeBetStatistics: whenever All.Time has passed the last
+        statistics by that much (run.c:52-59), on_station("statistics", timeline) is called in front of the "advance" station,
+        sys_state becomes the abi.SysState of compute_global_quantities_of_system(), and the line of energy.txt is appended to
+        energy_lines and to energy_file (a path opened for append, or an object with write).  potential: None, or a function of
+        the timeline that returns the P[].Potential column (of the kind of the columns) or None; the loop computes no potentials."""
         from . import lib
         self._lib = lib()
         self.eng, self.cols, self.par = engine, cols, par
@@ -58,6 +64,11 @@ class Timeline:
         self.num_forces_since_decomp = 1 + self.n * self.freq   # (begrun: the first step decomposes)
         self.have_tree = False
         self.steps = 0
+        self.time_bet_statistics = None if time_bet_statistics is None else float(time_bet_statistics)
+        if self.time_bet_statistics is not None:
+            self.time_last_statistics = par.time_begin - self.time_bet_statistics   # init.c:94
+        self.potential, self.sys_state, self.energy_lines = potential, None, []
+        self._energy_file = open(energy_file, "a") if isinstance(energy_file, (str, bytes)) or hasattr(energy_file, "__fspath__") else energy_file
 
     def _station(self, name):
         if self.on_station:
@@ -101,6 +112,19 @@ class Timeline:
         c, eng = self.cols, self.eng
         eng._check(self._lib.ngravs_get_accel(eng._h, _addr(c["grav_accel"]), 24, _addr(c["grav_pm"]) if self.mesh else None, 24,
                                               _addr(c["old_acc"]), 8, None, 0, int(self.device), 1), "ngravs_get_accel")
+
+    def _statistics(self):
+        """energy_statistics() (run.c:413-433) on the columns as they are, without the potential computation"""
+        from . import energy_line
+        self._station("statistics")
+        pot = self.potential(self) if self.potential else None
+        self.sys_state = self.eng.global_quantities(self._time_cols(TIME_COLS), self.par, self.ti_current, self.pm_ti, pot)
+        line = energy_line(self.sys_state, self.time)
+        self.energy_lines.append(line)
+        if self._energy_file is not None:
+            self._energy_file.write(line)
+            self._energy_file.flush()
+        self.time_last_statistics += self.time_bet_statistics
 
     def step(self):
         """one pass of the main loop (run.c:36-61); returns ti_current"""
@@ -152,7 +176,10 @@ class Timeline:
         if self.full_step or self.dt_displacement == 0:
             self.disp_sums = eng.displacement_sums(c["type"], c["vel"], c["mass"])
             self.dt_displacement = eng.dt_displacement(par, self.disp_sums, self.time)
-        # 7. advance_and_find_timesteps
+        # 7. energy_statistics, when due (run.c:52-59)
+        if self.time_bet_statistics is not None and self.time - self.time_last_statistics >= self.time_bet_statistics:
+            self._statistics()
+        # 8. advance_and_find_timesteps
         self._station("advance")
         self.n_kicked, pm_ti = eng.advance_and_find_timesteps(self._time_cols(TIME_COLS), par, self.ti_current, self.dt_displacement,
                                                               self.pm_ti)

@@ -752,6 +752,8 @@ int64_t ngravs_sph_density_update(int64_t n, const double *sums, double *hsml, d
  *   advance           active rows: R type grav_accel [grav_pm with a mesh], W vel ti_begstep ti_endstep; active gas rows: R hydro_accel
  *                     density hsml max_signal_vel, W vel_pred entropy dt_entropy; on a long-range kick ALL rows: R grav_pm, W vel, and
  *                     all gas rows: R grav_accel hydro_accel, W vel_pred
+ *   global sums       R type pos vel mass ti_begstep ti_endstep grav_accel [grav_pm with a mesh] [the potential argument, if given];
+ *                     gas rows: R hydro_accel entropy dt_entropy density; writes no column
  * Refusals (NGRAVS_ERR_ARG with a message, nothing written): NULL ctx, cols or params, n < 0, NULL where a column is required, a gas
  * column missing while a type-0 row exists, a type outside 0..5, timebase_interval <= 0, gamma < 1, time1 < time0, a comoving
  * call without tables.
@@ -840,6 +842,38 @@ int ngravs_dt_displacement(const ngravs_time_params_t *par, const double sums[18
  * advanced. */
 int ngravs_advance_and_find_timesteps(ngravs_ctx *ctx, const ngravs_time_cols_t *cols, const ngravs_time_params_t *par,
                                       int32_t ti_current, double dt_displacement, int32_t *pm_ti, int64_t *n_kicked);
+
+/* ---- Energy statistics: compute_global_quantities_of_system (global.c:22-198) and the energy.txt line of energy_statistics
+ * (run.c:413-433), the station of the main loop between compute_accelerations() and advance_and_find_timesteps() (run.c:52-59).
+ * Split like the displacement constraint: the local sums on the device, then a host rule on the (all-reduced) sums, so that a host
+ * with several tasks adds the 78 numbers of its tasks in between (the reference's MPI_Reduce, global.c:118-127).
+ * The potential is NOT computed: P[].Potential is a column the caller may hand in; without it EnergyPot is 0, as in the reference
+ * built without COMPUTE_POTENTIAL_ENERGY. */
+#define NGRAVS_GLOBAL_NSUMS 78
+typedef struct {   /* struct state_of_system, allvars.h, field for field: 119 doubles, 952 bytes; [3] of a vector is its norm */
+  double Mass, EnergyKin, EnergyPot, EnergyInt, EnergyTot, Momentum[4], AngMomentum[4], CenterOfMass[4];
+  double MassComp[6], EnergyKinComp[6], EnergyPotComp[6], EnergyIntComp[6], EnergyTotComp[6];
+  double MomentumComp[6][4], AngMomentumComp[6][4], CenterOfMassComp[6][4];
+} ngravs_sysstate_t;
+/* The local sums of global.c:52-114 at All.Ti_Current = ti_current over ALL rows: sums[13 * type + k], k = 0 mass, 1 kinetic
+ * energy 0.5 m |vel|^2 / a^2, 2 internal energy (type 0 only), 3 potential energy 0.5 m Potential / a (0 without the column),
+ * 4..6 m vel, 7..9 m (pos x vel), 10..12 m pos.  vel is the velocity predicted to ti_current from the middle of the row's step:
+ * Vel + GravAccel dt_gravkick [+ HydroAccel dt_hydrokick for type 0] [+ GravPM dt_pm with a mesh], and the entropy of a gas row is
+ * Entropy + DtEntropy dt; when comoving the two kick factors come from the tables and a = time_begin * exp(ti_current *
+ * timebase_interval), else a = 1.  The internal energy is m entr / (gamma - 1) (Density / a^3)^(gamma - 1), and m entr for gamma = 1
+ * (ISOTHERM_EQS).  potential: NULL, or P[].Potential with its stride in bytes, a device or host pointer as cols->on_device says.
+ * With a mesh pm_ti[2] = {All.PM_Ti_begstep, All.PM_Ti_endstep} is required (read only).  n = 0 gives 78 zeros.  The same sums bit
+ * for bit on every call with the same columns: no floating-point atomic, one partial per block, added in an order the number of
+ * rows alone fixes.  Refusals as for the other time calls, and a mesh without pm_ti; nothing is written then. */
+int ngravs_global_sums(ngravs_ctx *ctx, const ngravs_time_cols_t *cols, const ngravs_time_params_t *par, int32_t ti_current,
+                       const int32_t *pm_ti, const double *potential, int64_t potential_stride, double sums[NGRAVS_GLOBAL_NSUMS]);
+/* global.c:130-194 from the (all-reduced) sums, host, no GPU, in the reference's order of operations: EnergyTotComp, the totals,
+ * the centres of mass divided by the mass where that is > 0, and the norms in [3]. */
+int ngravs_global_finish(const double sums[NGRAVS_GLOBAL_NSUMS], ngravs_sysstate_t *out);
+/* The line energy_statistics() appends to energy.txt (run.c:419-429), host, no GPU: time, EnergyInt, EnergyPot, EnergyKin, the same
+ * three per type, MassComp[6] -- 28 %g fields separated by blanks, a newline, a terminating 0.  Returns the length without the
+ * 0, or NGRAVS_ERR_ARG for a NULL argument or a buffer shorter than length + 1. */
+int ngravs_energy_line(const ngravs_sysstate_t *s, double time, char *buf, int64_t len);
 
 #ifdef __cplusplus
 }
