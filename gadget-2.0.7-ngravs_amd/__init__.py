@@ -47,6 +47,8 @@ EXPORTS = [
     "ngravs_time_tables", "ngravs_time_factors", "ngravs_next_sync_point", "ngravs_move_particles", "ngravs_displacement_sums",
     "ngravs_dt_displacement", "ngravs_advance_and_find_timesteps",
     "ngravs_global_sums", "ngravs_global_finish", "ngravs_energy_line",
+    "ngravs_snapshot_plan", "ngravs_snapshot_block_count", "ngravs_snapshot_block", "ngravs_snapshot_header", "ngravs_snapshot_write",
+    "ngravs_find_next_outputtime",
 ]
 # include/ngravs_host.h (plain-C multi-task drivers over a communicator vtable, linked into the same library)
 HOST_EXPORTS = ["ngravs_host_comm_selftest", "ngravs_host_kept_step", "ngravs_host_toptree_borrow", "ngravs_host_domain_decomposition", "ngravs_host_domain_owners", "ngravs_host_domain_halo",
@@ -155,6 +157,12 @@ def lib():
         L.ngravs_global_sums.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         L.ngravs_global_finish.argtypes = [C.c_void_p, C.c_void_p]
         L.ngravs_energy_line.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_int64]
+        L.ngravs_snapshot_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ngravs_snapshot_block_count.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+        L.ngravs_snapshot_block.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_int32]
+        L.ngravs_snapshot_header.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_void_p]
+        L.ngravs_snapshot_write.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_int64, C.c_char_p]
+        L.ngravs_find_next_outputtime.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -300,6 +308,33 @@ def energy_line(state, time):
     if rc < 0:
         raise NgravsError("ngravs_energy_line: %d" % rc)
     return buf.raw[:rc].decode()
+
+
+def find_next_outputtime(par, rule, ti_curr):
+    """find_next_outputtime(ti_curr) of the reference (run.c:244-361) for an abi.OutputRule (abi.make_output_rule): the first
+    output time >= ti_curr on the integer time line, 2 * abi.TIMEBASE when there is none.  Raises NgravsError where the reference
+    ends with 13123, 110 or 111.  No GPU needed."""
+    out = C.c_int32(0)
+    rc = lib().ngravs_find_next_outputtime(C.byref(par), C.byref(rule), int(ti_curr), C.byref(out))
+    if rc != 0:
+        msg = lib().ngravs_last_error(None)
+        raise NgravsError("ngravs_find_next_outputtime failed: status %d (%s)" % (rc, msg.decode() if msg else ""))
+    return int(out.value)
+
+
+def snapshot_header(par, npart, time, mass_table=None, npart_total=None, num_files=1, hubble_param=0.0, box_size=0.0):
+    """struct io_header as write_file fills it (io.c:720-761): 256 bytes.  No GPU needed."""
+    s = abi.Snapshot()
+    s.mass_table = (C.c_double * 6)(*([0.0] * 6 if mass_table is None else [float(x) for x in mass_table]))
+    s.box_size, s.hubble_param = float(box_size), float(hubble_param)
+    npart = np.ascontiguousarray(npart, dtype=np.int64)
+    total = npart if npart_total is None else np.ascontiguousarray(npart_total, dtype=np.int64)
+    assert npart.shape == (6,) and total.shape == (6,)
+    out = C.create_string_buffer(256)
+    rc = lib().ngravs_snapshot_header(C.byref(par), C.byref(s), npart.ctypes.data, total.ctypes.data, int(num_files), float(time), out)
+    if rc != 0:
+        raise NgravsError("ngravs_snapshot_header: %d" % rc)
+    return out.raw
 
 
 def _ptr(a):
@@ -937,6 +972,93 @@ class Engine:
         """compute_global_quantities_of_system() for one task: global_finish(global_sums(...)), an abi.SysState"""
         return global_finish(self.global_sums(cols, par, ti_current, pm_ti, potential))
 
+    # -- snapshot files: savepositions() (io.c:33-989) ---------------------------------------------------------------------------
+    def _snap_cols(self, cols):
+        """cols as the time calls take them, or a ready abi.TimeCols (any strides: an interleaved P[])"""
+        if isinstance(cols, abi.TimeCols):
+            return cols, None
+        return self._time_cols(cols)
+
+    def _snapshot(self, tc, ti_current, pm_ti, mass_table, ids, potential, box_size=None, hubble_param=0.0):
+        """abi.Snapshot; ids / potential: an array of the kind of the columns (int32 / float64 [n]), or (address, stride)"""
+        s = abi.Snapshot()
+        keep = []
+        s.ti_current = int(ti_current)
+        if pm_ti is not None:
+            pm = (C.c_int32 * 2)(*[int(x) for x in pm_ti])
+            keep.append(pm)
+            s.pm_ti = C.addressof(pm)
+        s.mass_table = (C.c_double * 6)(*([0.0] * 6 if mass_table is None else [float(x) for x in mass_table]))
+        for name, col, key in (("ids", ids, "type"), ("potential", potential, "mass")):
+            if col is None:
+                continue
+            if isinstance(col, tuple):
+                a, stride = col
+            else:
+                chk, addr = _columns({name: col}, {name: (int(tc.n),)}, bool(tc.on_device), int_keys=("ids",))
+                keep.append(chk)
+                a, stride = addr(chk[name]), 4 if name == "ids" else 8
+            setattr(s, name, a)
+            setattr(s, name + "_stride", stride)
+        s.box_size = float(self.cfg.box_size if box_size is None else box_size)
+        s.hubble_param = float(hubble_param)
+        s._keep = keep
+        return s
+
+    def snapshot_plan(self, cols):
+        """The file order of io.c for the type column (cols: a dict with "type", or an abi.TimeCols): a stable partition of the
+        rows by type, kept in the engine until the next plan.  Returns npart, int64 [6]."""
+        tc, keep = self._snap_cols(cols if isinstance(cols, (dict, abi.TimeCols)) else dict(type=cols))
+        npart = np.zeros(6, dtype=np.int64)
+        self._check(lib().ngravs_snapshot_plan(self._h, C.byref(tc), npart.ctypes.data), "ngravs_snapshot_plan")
+        return npart
+
+    def snapshot_block_count(self, block, mass_table=None):
+        """get_particles_in_block (io.c:465-523) for the plan: (elements, bytes per element)"""
+        s = abi.Snapshot()
+        s.mass_table = (C.c_double * 6)(*([0.0] * 6 if mass_table is None else [float(x) for x in mass_table]))
+        cnt, bpe = C.c_int64(0), C.c_int32(0)
+        self._check(lib().ngravs_snapshot_block_count(self._h, C.byref(s), int(block), C.byref(cnt), C.byref(bpe)), "ngravs_snapshot_block_count")
+        return int(cnt.value), int(bpe.value)
+
+    def snapshot_block(self, block, cols, par, ti_current, pm_ti=None, mass_table=None, ids=None, potential=None, first=0, count=None,
+                       out=None, device_out=None):
+        """The elements [first, first + count) of a block (abi.SNAP_*) of the planned file order as they lie on disk: float32
+        [count] or [count, 3], int32 for ID.  Returns a numpy array, or a device tensor when the columns are device tensors
+        (device_out overrides); out: written through instead."""
+        tc, keep = self._snap_cols(cols)
+        s = self._snapshot(tc, ti_current, pm_ti, mass_table, ids, potential)
+        if count is None:
+            count = self.snapshot_block_count(block, mass_table)[0] - int(first)
+        on_dev = bool(tc.on_device) if device_out is None else bool(device_out)
+        shape = (int(count), 3) if block in abi.SNAP_VECTOR_BLOCKS else (int(count),)
+        if out is None:
+            if on_dev:
+                import torch
+                out = torch.zeros(shape, dtype=torch.int32 if block == abi.SNAP_ID else torch.float32, device="cuda")
+                torch.cuda.synchronize()
+            else:
+                out = np.zeros(shape, dtype=np.int32 if block == abi.SNAP_ID else np.float32)
+        addr = out.data_ptr() if _is_device(out) else out.ctypes.data
+        self._check(lib().ngravs_snapshot_block(self._h, C.byref(tc), C.byref(par), C.byref(s), int(block), int(first), int(count), addr,
+                                                int(_is_device(out))), "ngravs_snapshot_block")
+        return out
+
+    def snapshot_header(self, par, npart, time, mass_table=None, npart_total=None, num_files=1, hubble_param=0.0, box_size=None):
+        return snapshot_header(par, npart, time, mass_table, npart_total, num_files, hubble_param,
+                               self.cfg.box_size if box_size is None else box_size)
+
+    def write_snapshot(self, path, cols, par, ti_current, pm_ti=None, mass_table=None, ids=None, potential=None, blocks_mask=abi.SNAP_ALWAYS,
+                       snap_format=1, buffer_bytes=0, hubble_param=0.0, box_size=None):
+        """savepositions() for one task and one file (io.c:33-989): plan, header and every present block with elements, converted
+        and grouped by type on the device, framed on the host.  cols: the columns of the time calls (dict, or abi.TimeCols); ids:
+        P[].ID (int32 [n]); potential: P[].Potential for the POT block; blocks_mask: abi.snap_mask("ACCE", ...) for the
+        reference's OUTPUT* switches; snap_format 1 or 2; buffer_bytes: the chunk that crosses to the host at a time (0: 64 MiB)."""
+        tc, keep = self._snap_cols(cols)
+        s = self._snapshot(tc, ti_current, pm_ti, mass_table, ids, potential, box_size, hubble_param)
+        self._check(lib().ngravs_snapshot_write(self._h, C.byref(tc), C.byref(par), C.byref(s), int(blocks_mask), int(snap_format), int(buffer_bytes),
+                                                os.fsencode(path)), "ngravs_snapshot_write")
+
     def direct_sum(self, idx):
         idx = np.ascontiguousarray(idx, dtype=np.int32)
         out = np.zeros((len(idx), 3))
@@ -945,3 +1067,4 @@ class Engine:
 
 from . import sph_split  # noqa: E402,F401  (uses NgravsError and sph_density_update above)
 from . import timeline  # noqa: E402,F401
+from . import snapshot  # noqa: E402,F401

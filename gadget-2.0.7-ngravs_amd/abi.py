@@ -268,6 +268,48 @@ class SysState(C.Structure):
         (k, C.c_double * 4 * 6) for k in ("MomentumComp", "AngMomentumComp", "CenterOfMassComp")]
 
 
+# ---- snapshot files (ngravs_snapshot_plan ... ngravs_find_next_outputtime) ----
+SNAP_BLOCKS = ("POS", "VEL", "ID", "MASS", "U", "RHO", "HSML", "POT", "ACCE", "ENDT", "TSTP")   # enum iofields (allvars.h)
+(SNAP_POS, SNAP_VEL, SNAP_ID, SNAP_MASS, SNAP_U, SNAP_RHO, SNAP_HSML, SNAP_POT, SNAP_ACCE, SNAP_ENDT, SNAP_TSTP) = range(11)
+SNAP_LABELS = ("POS ", "VEL ", "ID  ", "MASS", "U   ", "RHO ", "HSML", "POT ", "ACCE", "ENDT", "TSTP")   # fill_Tab_IO_Labels
+SNAP_VECTOR_BLOCKS = (SNAP_POS, SNAP_VEL, SNAP_ACCE)
+SNAP_GAS_BLOCKS = (SNAP_U, SNAP_RHO, SNAP_HSML, SNAP_ENDT)
+SNAP_ALWAYS = 0x7F   # blockpresent: POS VEL ID MASS U RHO HSML
+
+
+def snap_mask(*names):
+    """the blocks_mask of ngravs_snapshot_write for the optional blocks given by label: snap_mask("POT", "ACCE", "ENDT", "TSTP")"""
+    m = SNAP_ALWAYS
+    for k in names:
+        m |= 1 << SNAP_BLOCKS.index(k.strip())
+    return m
+
+
+class Snapshot(C.Structure):
+    """ngravs_snapshot_t"""
+    _fields_ = [("ti_current", C.c_int32), ("reserved", C.c_int32), ("pm_ti", C.c_void_p), ("mass_table", C.c_double * 6),
+                ("ids", C.c_void_p), ("ids_stride", C.c_int64), ("potential", C.c_void_p), ("potential_stride", C.c_int64),
+                ("box_size", C.c_double), ("hubble_param", C.c_double)]
+
+
+class OutputRule(C.Structure):
+    """ngravs_output_rule_t"""
+    _fields_ = [("output_list_on", C.c_int32), ("output_list_length", C.c_int32), ("output_list_times", C.c_void_p),
+                ("time_of_first_snapshot", C.c_double), ("time_bet_snapshot", C.c_double)]
+
+
+def make_output_rule(output_list=None, time_of_first_snapshot=0.0, time_bet_snapshot=0.0):
+    """ngravs_output_rule_t: output_list (All.OutputListTimes; OutputListOn) or TimeOfFirstSnapshot / TimeBetSnapshot"""
+    r = OutputRule()
+    if output_list is not None:
+        import numpy as np
+        keep = np.ascontiguousarray(output_list, dtype=np.float64)
+        r.output_list_on, r.output_list_length, r.output_list_times = 1, len(keep), keep.ctypes.data
+        r._keep = keep
+    r.time_of_first_snapshot, r.time_bet_snapshot = float(time_of_first_snapshot), float(time_bet_snapshot)
+    return r
+
+
 class GravTargets(C.Structure):
     """ngravs_grav_targets_t"""
     _fields_ = [f for k in GRAV_TARGET_NAMES for f in ((k, C.c_void_p), (k + "_stride", C.c_int64))] + [("on_device", C.c_int32)]

@@ -347,6 +347,8 @@ extern "C" void ngravs_destroy(ngravs_ctx *c)
     }
   c->probe_out.release();
   c->time_buf.release();
+  c->snap_order.release();
+  c->snap_tmp.release();
   (void)hipStreamDestroy(c->stream);
   delete c;
 }
@@ -2530,4 +2532,35 @@ extern "C" int ngravs_global_finish(const double sums[NGRAVS_GLOBAL_NSUMS], ngra
 extern "C" int ngravs_energy_line(const ngravs_sysstate_t *s, double time, char *buf, int64_t len)
 {
   return s && buf ? time_energy_line(s, time, buf, len) : NGRAVS_ERR_ARG;
+}
+
+// ---- snapshot files: savepositions (io.c:33-989) and find_next_outputtime (run.c:244-361); kernels_snapshot.hip ---------------------
+static_assert(sizeof(ngravs_snapshot_t) == 112 && sizeof(ngravs_output_rule_t) == 32,
+              "the Python mirror (abi.Snapshot / OutputRule) assumes this layout");
+extern "C" int ngravs_snapshot_plan(ngravs_ctx *c, const ngravs_time_cols_t *cols, int64_t npart[6])
+{
+  return c ? snapshot_plan(c, cols, npart) : NGRAVS_ERR_ARG;
+}
+extern "C" int ngravs_snapshot_block_count(ngravs_ctx *c, const ngravs_snapshot_t *snap, int32_t block, int64_t *count, int32_t *bytes_per_element)
+{
+  return c ? snapshot_block_count(c, snap, block, count, bytes_per_element) : NGRAVS_ERR_ARG;
+}
+extern "C" int ngravs_snapshot_block(ngravs_ctx *c, const ngravs_time_cols_t *cols, const ngravs_time_params_t *par, const ngravs_snapshot_t *snap,
+                                     int32_t block, int64_t first, int64_t count, void *out, int32_t out_on_device)
+{
+  return c ? snapshot_block(c, cols, par, snap, block, first, count, out, out_on_device) : NGRAVS_ERR_ARG;
+}
+extern "C" int ngravs_snapshot_header(const ngravs_time_params_t *par, const ngravs_snapshot_t *snap, const int64_t npart[6],
+                                      const int64_t npart_total[6], int32_t num_files, double time, unsigned char out[256])
+{
+  return par && snap && npart && npart_total && out ? snapshot_header(par, snap, npart, npart_total, num_files, time, out) : NGRAVS_ERR_ARG;
+}
+extern "C" int ngravs_snapshot_write(ngravs_ctx *c, const ngravs_time_cols_t *cols, const ngravs_time_params_t *par, const ngravs_snapshot_t *snap,
+                                     uint32_t blocks_mask, int32_t snap_format, int64_t buffer_bytes, const char *path)
+{
+  return c ? snapshot_write(c, cols, par, snap, blocks_mask, snap_format, buffer_bytes, path) : NGRAVS_ERR_ARG;
+}
+extern "C" int ngravs_find_next_outputtime(const ngravs_time_params_t *par, const ngravs_output_rule_t *rule, int32_t ti_curr, int32_t *ti_next)
+{
+  return snapshot_next_outputtime(par, rule, ti_curr, ti_next);
 }

@@ -421,6 +421,11 @@ struct ngravs_ctx
   // time integration (kernels_time.hip): counters, the decided steps of one advance call, the look-up tables, and the device
   // copies of host columns; nothing in it outlives a call
   DevBuf<unsigned char> time_buf;
+  // the snapshot plan (kernels_snapshot.hip): the file order of the rows of the last ngravs_snapshot_plan, order[dest] = source
+  // row, for snap_n rows (-1: no plan) with snap_npart[type] of each type; snap_tmp holds the partition's counts and bases
+  DevBuf<int> snap_order, snap_tmp;
+  long long snap_n = -1;
+  int64_t snap_npart[NGRAVS_NTYPES] = {0, 0, 0, 0, 0, 0};
 };
 
 // Routes the context's launches to stream `s`, whose CU mask leaves them `cus` CUs, until the end of the scope (the kernels
@@ -702,3 +707,13 @@ int time_global_sums(ngravs_ctx *c, const ngravs_time_cols_t *cols, const ngravs
                      const double *potential, int64_t potential_stride, double sums[NGRAVS_GLOBAL_NSUMS]);
 int time_global_finish(const double sums[NGRAVS_GLOBAL_NSUMS], ngravs_sysstate_t *out);
 int time_energy_line(const ngravs_sysstate_t *s, double time, char *buf, int64_t len);
+// ---- snapshot files (kernels_snapshot.hip)
+int snapshot_plan(ngravs_ctx *c, const ngravs_time_cols_t *cols, int64_t npart[6]);
+int snapshot_block_count(ngravs_ctx *c, const ngravs_snapshot_t *snap, int block, int64_t *count, int32_t *bytes_per_element);
+int snapshot_block(ngravs_ctx *c, const ngravs_time_cols_t *cols, const ngravs_time_params_t *par, const ngravs_snapshot_t *snap, int block,
+                   int64_t first, int64_t count, void *out, int out_on_device);
+int snapshot_header(const ngravs_time_params_t *par, const ngravs_snapshot_t *snap, const int64_t npart[6], const int64_t npart_total[6],
+                    int num_files, double time, unsigned char out[256]);
+int snapshot_write(ngravs_ctx *c, const ngravs_time_cols_t *cols, const ngravs_time_params_t *par, const ngravs_snapshot_t *snap,
+                   uint32_t blocks_mask, int snap_format, int64_t buffer_bytes, const char *path);
+int snapshot_next_outputtime(const ngravs_time_params_t *par, const ngravs_output_rule_t *rule, int ti_curr, int32_t *ti_next);

@@ -32,7 +32,7 @@ class Timeline:
     are the reference's globals of the same names after the last step()."""
 
     def __init__(self, engine, cols, par, sph=None, tree_domain_update_frequency=0.0, softening=None, on_station=None,
-                 time_bet_statistics=None, energy_file=None, potential=None):
+                 time_bet_statistics=None, energy_file=None, potential=None, output=None):
         """par: abi.make_time_params(...).  sph: the keyword arguments of Engine.sph_accelerations that are not columns or times
         (des_num_ngb, max_num_ngb_deviation, art_bulk_visc_const, ...), required with gas.  tree_domain_update_frequency:
         All.TreeDomainUpdateFrequency (domain.c:66-76); 0 decomposes and builds on every step.  softening: None, or a function
@@ -43,7 +43,14 @@ class Timeline:
         statistics by that much (run.c:52-59), on_station("statistics", timeline) is called in front of the "advance" station,
         sys_state becomes the abi.SysState of compute_global_quantities_of_system(), and the line of energy.txt is appended to
         energy_lines and to energy_file (a path opened for append, or an object with write).  potential: None, or a function of
-        the timeline that returns the P[].Potential column (of the kind of the columns) or None; the loop computes no potentials."""
+        the timeline that returns the P[].Potential column (of the kind of the columns) or None; the loop computes no potentials.
+        output: None (no snapshot files; the loop is then exactly the one without this argument), or a dict: dir (All.OutputDir,
+        with its separator), base (All.SnapshotFileBase), snap_format (1 or 2), rule (abi.make_output_rule: the list of output
+        times, or TimeOfFirstSnapshot / TimeBetSnapshot), blocks_mask (abi.snap_mask), mass_table (All.MassTable), ids (a function
+        of the timeline that returns the P[].ID column, int32, of the kind of the columns), and optionally buffer_bytes and
+        hubble_param.  Whenever the next sync point has reached ti_nextoutput (run.c:206-225) the particles are moved to the
+        output time, on_station("snapshot", timeline) is called and <dir><base>_%03d is written (snapshot_file_count counts them,
+        snapshot_files lists them); the POT block is written when `potential` gives a column."""
         from . import lib
         self._lib = lib()
         self.eng, self.cols, self.par = engine, cols, par
@@ -69,6 +76,15 @@ class Timeline:
             self.time_last_statistics = par.time_begin - self.time_bet_statistics   # init.c:94
         self.potential, self.sys_state, self.energy_lines = potential, None, []
         self._energy_file = open(energy_file, "a") if isinstance(energy_file, (str, bytes)) or hasattr(energy_file, "__fspath__") else energy_file
+        self.output = None if output is None else dict(output)
+        if self.output is not None:
+            unknown = set(self.output) - {"dir", "base", "snap_format", "rule", "blocks_mask", "mass_table", "ids", "buffer_bytes", "hubble_param"}
+            if unknown or "rule" not in self.output or "ids" not in self.output:
+                raise TypeError("output: dir, base, snap_format, rule, blocks_mask, mass_table, ids[, buffer_bytes, hubble_param]")
+            from . import find_next_outputtime
+            self.ti_nextoutput = find_next_outputtime(par, self.output["rule"], 0)   # begrun.c:141
+            self.snapshot_file_count = 0
+            self.snapshot_files = []
 
     def _station(self, name):
         if self.on_station:
@@ -126,6 +142,31 @@ class Timeline:
             self._energy_file.flush()
         self.time_last_statistics += self.time_bet_statistics
 
+    def _time_of(self, ti):
+        par = self.par
+        if par.comoving:
+            return par.time_begin * math.exp(ti * par.timebase_interval)
+        return par.time_begin + ti * par.timebase_interval
+
+    def write_snapshot(self):
+        """savepositions(All.SnapshotFileCount++) on the columns as they are, at ti_current (run.c:222; a caller writes the last
+        snapshot of run.c:136 with it).  Returns the file's path."""
+        import os
+        o = self.output
+        if o is None:
+            raise ValueError("the timeline has no output=")
+        self._station("snapshot")
+        pot = self.potential(self) if self.potential else None
+        mask = int(o.get("blocks_mask", abi.SNAP_ALWAYS))
+        mask = (mask | (1 << abi.SNAP_POT)) if pot is not None else (mask & ~(1 << abi.SNAP_POT))
+        path = "%s%s_%03d" % (os.fspath(o.get("dir", "")), o.get("base", "snapshot"), self.snapshot_file_count)
+        self.eng.write_snapshot(path, self._time_cols(TIME_COLS), self.par, self.ti_current, pm_ti=self.pm_ti, mass_table=o.get("mass_table"),
+                                ids=o["ids"](self), potential=pot, blocks_mask=mask, snap_format=o.get("snap_format", 1),
+                                buffer_bytes=o.get("buffer_bytes", 0), hubble_param=o.get("hubble_param", 0.0))
+        self.snapshot_file_count += 1
+        self.snapshot_files.append(path)
+        return path
+
     def step(self):
         """one pass of the main loop (run.c:36-61); returns ti_current"""
         eng, c, par = self.eng, self.cols, self.par
@@ -136,6 +177,15 @@ class Timeline:
         if pm_step:   # domain.c:66-73
             self.num_forces_since_decomp = 1 + self.n * self.freq
         rebuild = not self.have_tree or self.num_forces_since_decomp > self.n * self.freq   # domain.c:76
+        # 1a. the output times that the sync point has reached (run.c:206-225)
+        if self.output is not None:
+            from . import find_next_outputtime
+            while ti_next >= self.ti_nextoutput and self.ti_nextoutput >= 0:
+                eng.move_particles(self._time_cols(TIME_COLS), par, self.ti_current, self.ti_nextoutput, wrap=False)
+                self.ti_current = self.ti_nextoutput
+                self.time = self._time_of(self.ti_current)
+                self.write_snapshot()
+                self.ti_nextoutput = find_next_outputtime(par, self.output["rule"], self.ti_nextoutput + 1)
         self._station("drift")
         # 2. the drift; in front of a decomposition the particles are mapped back onto the box (domain.c:80-82)
         self.wrapped = bool(rebuild and eng.cfg.periodic)

@@ -757,8 +757,8 @@ int64_t ngravs_sph_density_update(int64_t n, const double *sums, double *hsml, d
  * Refusals (NGRAVS_ERR_ARG with a message, nothing written): NULL ctx, cols or params, n < 0, NULL where a column is required, a gas
  * column missing while a type-0 row exists, a type outside 0..5, timebase_interval <= 0, gamma < 1, time1 < time0, a comoving
  * call without tables.
- * Not provided: FLEXSTEPS, PSEUDOSYMMETRIC, MAKEGLASS, CONDUCTION, NOPMSTEPADJUSTMENT, PLACEHIGHRESREGION, snapshot times
- * (run.c:206-225), the node drift and node kicks (predict.c:79-91, timestep.c:331-344: the library refits its tree instead). */
+ * Not provided: FLEXSTEPS, PSEUDOSYMMETRIC, MAKEGLASS, CONDUCTION, NOPMSTEPADJUSTMENT, PLACEHIGHRESREGION, the node drift and
+ * node kicks (predict.c:79-91, timestep.c:331-344: the library refits its tree instead). */
 #define NGRAVS_TIMEBASE (1 << 28)          /* allvars.h: TIMEBASE                                     */
 #define NGRAVS_DRIFT_TABLE_LENGTH 1000     /* allvars.h: DRIFT_TABLE_LENGTH                           */
 typedef struct {   /* strides in bytes; n rows */
@@ -874,6 +874,72 @@ int ngravs_global_finish(const double sums[NGRAVS_GLOBAL_NSUMS], ngravs_sysstate
  * three per type, MassComp[6] -- 28 %g fields separated by blanks, a newline, a terminating 0.  Returns the length without the
  * 0, or NGRAVS_ERR_ARG for a NULL argument or a buffer shorter than length + 1. */
 int ngravs_energy_line(const ngravs_sysstate_t *s, double time, char *buf, int64_t len);
+
+/* ---- Snapshot files: savepositions() (io.c:33-989) for one task and one file, and find_next_outputtime() (run.c:244-361), the
+ * station of the main loop inside find_next_sync_point_and_drift (run.c:206-225).  The device does the per-row conversions of
+ * fill_write_buffer (io.c:129-357) and the grouping by type; the host frames the records.
+ * The FILE ORDER of io.c is type by type, and within a type the order of P[] (io.c:178-206).  ngravs_snapshot_plan builds it once
+ * per snapshot from the type column, a stable partition, as a permutation kept in the context until the next plan or
+ * ngravs_destroy; the same permutation on every call.  Every block call then takes a range [first, first + count) of a block's
+ * elements in that order and writes them as they lie on disk: float32 (int32 for ID), three per element for POS, VEL and ACCE.
+ * The statements are the reference's and round to float after EACH of them, with nothing contracted into a fused multiply-add:
+ *   POS   (float) Pos; periodic: the two while loops of io.c:198-201 on the float (-1e-9 becomes BoxSize and then 0)
+ *   VEL   Vel + GravAccel dt_gravkick; type 0: += HydroAccel dt_hydrokick; with a mesh: += GravPM dt_gravkick_pm; *= sqrt(a3inv);
+ *         the kick factors as in ngravs_global_sums
+ *   ID    snap->ids (int32; LONGIDS is not provided)
+ *   MASS  Mass, only for the types whose mass_table entry is 0 (io.c:501-508)
+ *   U     dmax(MinEgySpec, Entropy / (gamma - 1) * pow(Density a3inv, gamma - 1)); gamma == 1: Entropy (ISOTHERM_EQS)
+ *   RHO HSML ENDT   Density, Hsml, DtEntropy of the type-0 rows
+ *   POT   snap->potential (the library computes none); the block exists only with the column
+ *   ACCE  fac1 GravAccel; with a mesh: += fac1 GravPM; type 0: += fac2 HydroAccel  (fac1 = 1 / a^2, fac2 = 1 / a^(3 gamma - 2))
+ *   TSTP  (Ti_endstep - Ti_begstep) Timebase_interval
+ * a = time_begin exp(ti_current timebase_interval) when comoving, else 1.  The context supplies PERIODIC, BoxSize and PMGRID.
+ * Refusals (NGRAVS_ERR_ARG with a message, nothing written, a file not touched): those of the other time calls, a type outside
+ * 0..5 (at the plan), a block whose column is missing, a range outside the block, a mesh without pm_ti, a periodic POS coordinate
+ * that is not finite or has |x| >= 1024 BoxSize (the reference's loops would run that many trips, and for ever from 2^24 box
+ * lengths on), snap_format 3 (no HDF5).  NGRAVS_ERR_STATE: a block call before a plan or with an n that is not the plan's.
+ * Not provided: HDF5, LONGIDS, LONG_X/Y/Z, several files per snapshot and the communicator driver for several tasks (the ranged
+ * block call is the per-task half), restart files, the computation of potentials. */
+enum { NGRAVS_SNAP_POS, NGRAVS_SNAP_VEL, NGRAVS_SNAP_ID, NGRAVS_SNAP_MASS, NGRAVS_SNAP_U, NGRAVS_SNAP_RHO, NGRAVS_SNAP_HSML,
+       NGRAVS_SNAP_POT, NGRAVS_SNAP_ACCE, NGRAVS_SNAP_ENDT, NGRAVS_SNAP_TSTP, NGRAVS_SNAP_NBLOCKS };   /* enum iofields, allvars.h */
+typedef struct {
+  int32_t ti_current, reserved;      /* All.Ti_Current                                                                        */
+  const int32_t *pm_ti;              /* {All.PM_Ti_begstep, All.PM_Ti_endstep}, HOST; required with a mesh, else NULL         */
+  double mass_table[6];              /* All.MassTable: header.mass, and which types the MASS block holds                      */
+  const int32_t *ids;     int64_t ids_stride;         /* P[].ID, of the kind of the columns (cols->on_device)                 */
+  const double *potential; int64_t potential_stride;  /* P[].Potential or NULL, of the kind of the columns                    */
+  double box_size;                   /* header.BoxSize (the block calls wrap with the context's BoxSize)                      */
+  double hubble_param;               /* header.HubbleParam = All.HubbleParam                                                  */
+} ngravs_snapshot_t;
+typedef struct {
+  int32_t output_list_on, output_list_length;   /* All.OutputListOn, All.OutputListLength                                     */
+  const double *output_list_times;              /* All.OutputListTimes, HOST                                                  */
+  double time_of_first_snapshot, time_bet_snapshot;   /* All.TimeOfFirstSnapshot, All.TimeBetSnapshot                         */
+} ngravs_output_rule_t;
+/* The file order of cols->type, cols->n rows, into the context; npart[6]: the rows of each type.  Reads the type column only. */
+int ngravs_snapshot_plan(ngravs_ctx *ctx, const ngravs_time_cols_t *cols, int64_t npart[6]);
+/* get_particles_in_block (io.c:465-523) for the plan's counts and snap->mass_table, host: the block's number of elements and the
+ * bytes of one (12 or 4; may be NULL). */
+int ngravs_snapshot_block_count(ngravs_ctx *ctx, const ngravs_snapshot_t *snap, int32_t block, int64_t *count, int32_t *bytes_per_element);
+/* The elements [first, first + count) of `block` -> out, count * bytes_per_element bytes, a device pointer when out_on_device != 0.
+ * A host writes with a bounded buffer this way (All.BufferSize, io.c:821), and a host with several tasks asks each for its share. */
+int ngravs_snapshot_block(ngravs_ctx *ctx, const ngravs_time_cols_t *cols, const ngravs_time_params_t *par, const ngravs_snapshot_t *snap,
+                          int32_t block, int64_t first, int64_t count, void *out, int32_t out_on_device);
+/* struct io_header as write_file fills it (io.c:720-761), host, no GPU: npart, mass = mass_table, time, redshift (1 / time - 1 when
+ * comoving, else 0), five zero flags, npartTotal and its high word, num_files, BoxSize, Omega0, OmegaLambda, HubbleParam, zeros. */
+int ngravs_snapshot_header(const ngravs_time_params_t *par, const ngravs_snapshot_t *snap, const int64_t npart[6], const int64_t npart_total[6],
+                           int32_t num_files, double time, unsigned char out[256]);
+/* savepositions() for one task and one file: plan (the context's plan is this call's afterwards), header, and every present block
+ * with elements, in the reference's order, in chunks of buffer_bytes (0: 64 MiB) through the device.  snap_format 1, or 2 with the
+ * label records of io.c:796-803, 832-839.  blocks_mask: bit NGRAVS_SNAP_* set = the block is present (blockpresent, io.c:532-556: the
+ * four OUTPUT* switches); POS VEL ID MASS U RHO HSML always are.  Everything is checked before the file is opened. */
+int ngravs_snapshot_write(ngravs_ctx *ctx, const ngravs_time_cols_t *cols, const ngravs_time_params_t *par, const ngravs_snapshot_t *snap,
+                          uint32_t blocks_mask, int32_t snap_format, int64_t buffer_bytes, const char *path);
+/* find_next_outputtime(ti_curr) (run.c:244-361), host, no GPU: the first output time >= ti_curr on the integer time line, from the
+ * list of times or from TimeOfFirstSnapshot / TimeBetSnapshot; 2 * NGRAVS_TIMEBASE when there is none.  Reads timebase_interval,
+ * time_begin, time_max and comoving of par.  NGRAVS_ERR_ARG with a message in ngravs_last_error(NULL) where the reference ends
+ * with 13123 (TimeBetSnapshot <= 1 comoving, <= 0 otherwise), 110 or 111 (no time found in a million steps). */
+int ngravs_find_next_outputtime(const ngravs_time_params_t *par, const ngravs_output_rule_t *rule, int32_t ti_curr, int32_t *ti_next);
 
 #ifdef __cplusplus
 }
