@@ -49,6 +49,7 @@ EXPORTS = [
     "ngravs_global_sums", "ngravs_global_finish", "ngravs_energy_line",
     "ngravs_snapshot_plan", "ngravs_snapshot_block_count", "ngravs_snapshot_block", "ngravs_snapshot_header", "ngravs_snapshot_write",
     "ngravs_find_next_outputtime",
+    "ngravs_compute_potential", "ngravs_potential_targets", "ngravs_lattice_potential_table", "ngravs_last_potential_ms",
 ]
 # include/ngravs_host.h (plain-C multi-task drivers over a communicator vtable, linked into the same library)
 HOST_EXPORTS = ["ngravs_host_comm_selftest", "ngravs_host_kept_step", "ngravs_host_toptree_borrow", "ngravs_host_domain_decomposition", "ngravs_host_domain_owners", "ngravs_host_domain_halo",
@@ -163,6 +164,10 @@ def lib():
         L.ngravs_snapshot_header.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_void_p]
         L.ngravs_snapshot_write.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_int64, C.c_char_p]
         L.ngravs_find_next_outputtime.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+        L.ngravs_compute_potential.argtypes = abi.COMPUTE_POTENTIAL_ARGTYPES
+        L.ngravs_potential_targets.argtypes = abi.POTENTIAL_TARGETS_ARGTYPES
+        L.ngravs_lattice_potential_table.argtypes = abi.LATTICE_POTENTIAL_TABLE_ARGTYPES
+        L.ngravs_last_potential_ms.argtypes = [C.c_void_p, C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -881,6 +886,62 @@ class Engine:
             self._check(lib().ngravs_pm_targets(self._h, C.byref(tg), nt, pm.data_ptr() if on_device else pm.ctypes.data), "ngravs_pm_targets")
         del keep
         return pm
+
+    # -- gravitational potentials: compute_potential() (potential.c:22-345) ----------------------------------------------------
+    def compute_potential(self, par=None, into=None, want_nint=False):
+        """P[].Potential of ALL rows of the last hand-over, in the caller's order, from the built tree (and, with a mesh, a mesh
+        potential at the current positions): walk, self term, G, mesh part, cosmological term (ngravs_compute_potential).  par:
+        abi.make_time_params(...) for a comoving run or one with OmegaLambda, else None.  into: None (a fresh numpy array), or the
+        float64 [n] column to write, a C-contiguous numpy array or a contiguous torch tensor on the device.  Returns the column,
+        or (column, nint) with the int32 interaction counts of the walk.  Accelerations, GravPM and costs are not touched; with a
+        mesh pm_targets() is refused afterwards until the next PM step."""
+        on_device = into is not None and _is_device(into)
+        if into is not None:
+            if "float64" not in str(into.dtype) or len(into.shape) != 1:
+                raise ValueError("into must be a float64 array of shape [n], not %s %s" % (into.dtype, tuple(into.shape)))
+            if not (into.is_contiguous() if on_device else into.flags.c_contiguous):
+                raise ValueError("into must be contiguous: it is written through")
+            if int(into.shape[0]) != self.n:
+                raise ValueError("into has %d rows, the engine %d" % (int(into.shape[0]), self.n))
+        pot = into if into is not None else np.zeros(self.n)
+        nint = _zeros(self.n, into, on_device, np.int32) if want_nint else None
+        if on_device:
+            import torch
+            torch.cuda.synchronize()   # the library works on a stream of its own
+        addr = (lambda a: None if a is None else a.data_ptr()) if on_device else _ptr
+        self._check(lib().ngravs_compute_potential(self._h, C.byref(par) if par is not None else None, addr(pot), 8, int(on_device),
+                                                   addr(nint)), "ngravs_compute_potential")
+        return (pot, nint) if want_nint else pot
+
+    def potential_targets(self, pos, ptype, old_acc=None, mass=None, want_nint=False):
+        """The potential of this engine's particles at targets that need not be its particles: the records of
+        gravity_tree_targets(), in any order.  Returns pot [nt] = the potential walk x G, plus the mesh part with a mesh (that of
+        the last compute_potential(), which must have been called since the last PM step and hand-over); no self term and no
+        cosmological term, so the potentials of a set split over engines add up.  Or (pot, nint)."""
+        tg, nt, on_device, keep = self._grav_targets(pos, ptype, old_acc, mass)
+        pot = _zeros(nt, pos, on_device)
+        nint = _zeros(nt, pos, on_device, np.int32)
+        if nt > 0:
+            addr = (lambda a: a.data_ptr()) if on_device else (lambda a: a.ctypes.data)
+            self._check(lib().ngravs_potential_targets(self._h, C.byref(tg), nt, addr(pot), addr(nint)), "ngravs_potential_targets")
+        del keep
+        return (pot, nint) if want_nint else pot
+
+    def lattice_potential_table(self, t, s):
+        """the lattice potential table of the species pair (t, s) as the periodic tree-only potential walk reads it: float64
+        [65, 65, 65], sign(law) ewald_psi(i / 128, j / 128, k / 128) / BoxSize, the origin sign(law) 2.8372975 / BoxSize"""
+        for k in (t, s):
+            if int(k) != k or not 0 <= int(k) < abi.MAX_GRAVS:
+                raise ValueError("species %r is outside 0..%d" % (k, abi.MAX_GRAVS - 1))
+        out = np.zeros((65, 65, 65))
+        self._check(lib().ngravs_lattice_potential_table(self._h, int(t), int(s), out.ctypes.data), "ngravs_lattice_potential_table")
+        return out
+
+    def last_potential_ms(self):
+        """device milliseconds of the walk kernel of the last compute_potential()"""
+        ms = C.c_double(0)
+        self._check(lib().ngravs_last_potential_ms(self._h, C.byref(ms)), "ngravs_last_potential_ms")
+        return float(ms.value)
 
     # -- time integration: the stations of run.c:32-65 around the forces ------------------------------------------------------
     @staticmethod

@@ -319,6 +319,13 @@ class GravTargets(C.Structure):
 GRAVITY_TREE_TARGETS_ARGTYPES = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
 # int ngravs_pm_targets(ctx, targets, nt, grav_pm)
 PM_TARGETS_ARGTYPES = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+# int ngravs_compute_potential(ctx, par, potential, potential_stride, on_device, nint)
+COMPUTE_POTENTIAL_ARGTYPES = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
+# int ngravs_potential_targets(ctx, targets, nt, pot, nint)
+POTENTIAL_TARGETS_ARGTYPES = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+# int ngravs_lattice_potential_table(ctx, target, source, out)
+LATTICE_POTENTIAL_TABLE_ARGTYPES = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+LATTICE_ZERO = 2.8372975     # ngravs.c:133
 
 
 def make_config(n_gravs=1, periodic=0, pmgrid=0, box_size=0.0, G=1.0, theta=0.5, err_tol_force_acc=0.005,

@@ -328,6 +328,9 @@ extern "C" void ngravs_destroy(ngravs_ctx *c)
   c->gt_acc.release();
   c->gt_nint.release();
   c->gt_counters.release();
+  c->pot_table.release();
+  c->pot_lat.release();
+  c->r_pot.release();
   (void)hipEventDestroy(c->ev0);
   (void)hipEventDestroy(c->ev1);
   (void)hipEventDestroy(c->evk0);
@@ -506,6 +509,7 @@ static void handed_over(ngravs_ctx *c, bool keep_tree)
   c->pm_solo_steps = 0, c->pm_auto_cus = -1;   // ... and so are the CUs reserved for PM
   c->walk_unit_state = 4;
   c->have_particles = true;
+  c->pot_mesh_valid = false;   // the mesh of the last ngravs_compute_potential belongs to the positions of that call
   if(keep_tree)
     {
       c->tree_stale = true;    // same order and topology; columns and moments are refreshed by ngravs_force_update_tree
@@ -2483,6 +2487,122 @@ extern "C" int ngravs_pm_targets(ngravs_ctx *c, const ngravs_grav_targets_t *t, 
   if((rc = pm_targets_run(c, nt, c->gt_acc.p)))
     return rc;
   return col_deliver_or_zeros(c, c->gt_acc.p, sizeof(double) * 3 * (size_t)nt, grav_pm, t->on_device);
+}
+
+// ---- gravitational potentials (kernels_potential.hip) --------------------------------------------------------------------------------
+// What the potential calls refuse whatever the arguments: the configurations they are not built for, then a missing tree
+static int potential_refusals(ngravs_ctx *c, const Refuse &refuse)
+{
+  if(c->cfg.world_size > 1 || c->top.on || c->n_local != c->n)
+    return refuse(NGRAVS_ERR_ARG, "single task only (world_size > 1 or a multi-task working set)");
+  if(c->gsoft_on)
+    return refuse(NGRAVS_ERR_ARG, "adaptive gas softening is on (ngravs_set_gas_softening(ctx, NULL, 0, 0) switches it off)");
+  for(int a = 0; a < c->cfg.n_gravs; a++)
+    for(int b = 0; b < c->cfg.n_gravs; b++)
+      {
+        const int law = c->cfg.law_accel[a][b], spl = c->cfg.law_spline[a][b];
+        const std::string at = "[" + std::to_string(a) + "][" + std::to_string(b) + "]";
+        if(law != NGRAVS_LAW_NONE && law != NGRAVS_LAW_NEWTON && law != NGRAVS_LAW_NEG_NEWTON)
+          return refuse(NGRAVS_ERR_ARG, "law_accel" + at + " has no wired potential companion (only newtonian and neg_newtonian have; Yukawa, "
+                                        "coloyuk, BAM and user laws are not served)");
+        if(spl != NGRAVS_SPLINE_NONE && spl != NGRAVS_SPLINE_PLUMMER && spl != NGRAVS_SPLINE_NEG_PLUMMER)
+          return refuse(NGRAVS_ERR_ARG, "law_spline" + at + " has no wired potential companion (only plummer and neg_plummer have; BAM and "
+                                        "user splines are not served)");
+      }
+  if(c->cfg.pmgrid && !c->cfg.periodic)
+    return refuse(NGRAVS_ERR_ARG, "a mesh without periodic boundaries (non-periodic PM) is not served");
+  if(!c->have_order || !c->have_tree)
+    return refuse(NGRAVS_ERR_STATE, "needs a built tree of the current particle set");
+  return NGRAVS_OK;
+}
+
+extern "C" int ngravs_compute_potential(ngravs_ctx *c, const ngravs_time_params_t *par, double *potential, int64_t potential_stride,
+                                        int32_t on_device, int32_t *nint)
+{
+  if(!c)
+    return NGRAVS_ERR_ARG;
+  const Refuse refuse = {c, "ngravs_compute_potential"};
+  if(!potential)
+    return refuse(NGRAVS_ERR_ARG, "potential is NULL");
+  if(on_device && potential_stride != (int64_t)sizeof(double))
+    return refuse(NGRAVS_ERR_ARG, "a device column must be contiguous");
+  int rc;
+  if((rc = potential_refusals(c, refuse)))
+    return rc;
+  const int64_t n = c->n_local;
+  if(n == 0)
+    return NGRAVS_OK;
+  if(c->nnodes <= 0)
+    return refuse(NGRAVS_ERR_STATE, "the tree has no nodes");
+  (void)hipSetDevice(c->cfg.device);
+  if(c->tree_stale && (rc = ngravs_force_update_tree(c)))   // drifted tree: refresh columns and moments first
+    return rc;
+  if(c->out_tmp.ensure(3 * (size_t)n))   // [n] the column in caller order, behind it room for the counts
+    return refuse(NGRAVS_ERR_NOMEM, "device allocation failed");
+  int *d_nint = nint ? reinterpret_cast<int *>(c->out_tmp.p + n) : nullptr;
+  if((rc = potential_run(c, par, c->out_tmp.p, d_nint)))
+    return rc;
+  if((rc = col_download(c, c->out_tmp.p, sizeof(double), 1, n, potential, potential_stride, on_device, nullptr)))
+    return rc;
+  return nint ? col_deliver_or_zeros(c, d_nint, sizeof(int) * (size_t)n, nint, on_device) : NGRAVS_OK;
+}
+
+extern "C" int ngravs_potential_targets(ngravs_ctx *c, const ngravs_grav_targets_t *t, int64_t nt, double *pot, int32_t *nint)
+{
+  if(!c)
+    return NGRAVS_ERR_ARG;
+  const Refuse refuse = {c, "ngravs_potential_targets"};
+  if(!t || !t->pos || !t->type || !pot)
+    return refuse(NGRAVS_ERR_ARG, "targets, targets->pos, targets->type or pot is NULL");
+  if(nt < 0 || nt > 0x7fffffff)
+    return refuse(NGRAVS_ERR_ARG, "nt must be >= 0 (and below 2^31)");
+  int rc;
+  if((rc = potential_refusals(c, refuse)))
+    return rc;
+  if(c->cfg.pmgrid && !c->pot_mesh_valid)
+    return refuse(NGRAVS_ERR_STATE, "no valid potential mesh: needs an ngravs_compute_potential since the last PM step and hand-over");
+  if(nt == 0)
+    return NGRAVS_OK;
+  (void)hipSetDevice(c->cfg.device);
+  if(c->tree_stale && (rc = ngravs_force_update_tree(c)))
+    return rc;
+  double far = 0;
+  if((rc = grav_targets_stage(c, refuse, t, nt, &far)))
+    return rc;
+  const bool empty = c->n_local == 0 || c->nnodes <= 0;   // nothing to walk
+  if(!empty && (rc = potential_targets_run(c, nt)))
+    return rc;
+  if((rc = col_deliver_or_zeros(c, empty ? nullptr : c->gt_acc.p, sizeof(double) * (size_t)nt, pot, t->on_device)))
+    return rc;
+  return nint ? col_deliver_or_zeros(c, empty ? nullptr : c->gt_nint.p, sizeof(int) * (size_t)nt, nint, t->on_device) : NGRAVS_OK;
+}
+
+extern "C" int ngravs_lattice_potential_table(ngravs_ctx *c, int32_t target, int32_t source, double *out)
+{
+  if(!c)
+    return NGRAVS_ERR_ARG;
+  const Refuse refuse = {c, "ngravs_lattice_potential_table"};
+  const int ng = c->cfg.n_gravs;
+  if(!out || target < 0 || target >= ng || source < 0 || source >= ng)
+    return refuse(NGRAVS_ERR_ARG, "out is NULL, or the pair is outside [0, N_GRAVS)");
+  if(!c->cfg.periodic || c->cfg.pmgrid)
+    return refuse(NGRAVS_ERR_ARG, "only periodic configurations without a mesh read a lattice potential table");
+  (void)hipSetDevice(c->cfg.device);
+  int rc;
+  if((rc = potential_lattice_ensure(c)))
+    return rc;
+  const size_t sz = (size_t)65 * 65 * 65;
+  HIP_TRY(c, hipMemcpyAsync(out, c->pot_lat.p + ((size_t)target * ng + source) * sz, sizeof(double) * sz, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return NGRAVS_OK;
+}
+
+extern "C" int ngravs_last_potential_ms(ngravs_ctx *c, double *walk_ms)
+{
+  if(!c || !walk_ms)
+    return NGRAVS_ERR_ARG;
+  *walk_ms = c->pot_walk_ms;
+  return NGRAVS_OK;
 }
 
 // ---- time integration: drift, kick and timestep assignment (run.c:32-65 around the forces; kernels_time.hip) ------------------------

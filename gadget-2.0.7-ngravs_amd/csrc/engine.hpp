@@ -418,6 +418,16 @@ struct ngravs_ctx
   // pm_phi holds the complete potentials of the last single-mesh PM step (pm_finish); false before one, while they are being
   // rewritten, and when the last PM step went through the slab path, which has no whole mesh
   bool pm_mesh_valid = false;
+  // potentials (kernels_potential.hip); empty until ngravs_compute_potential / ngravs_potential_targets are used
+  DevBuf<double> pot_table;   // [ng][ng][NTAB]: E = (force_tab + pot_tab) u, the long-range potential tempI / u of the TreePM split
+  bool pot_table_ready = false;
+  DevBuf<double> pot_lat;     // [ng][ng][65^3]: sign(law) ewald_psi / BoxSize on the octant grid of `lat` (periodic tree-only)
+  bool pot_lat_ready = false;
+  DevBuf<double> r_pot;       // [n], Peano order: the walk's sum, then the finished potential
+  // pm_phi holds the potentials of the mesh of the last ngravs_compute_potential, at the positions of that call; cleared by the
+  // next deposit and by every hand-over of particles
+  bool pot_mesh_valid = false;
+  double pot_walk_ms = 0;     // device time of the walk kernel of the last ngravs_compute_potential
   // time integration (kernels_time.hip): counters, the decided steps of one advance call, the look-up tables, and the device
   // copies of host columns; nothing in it outlives a call
   DevBuf<unsigned char> time_buf;
@@ -526,6 +536,17 @@ struct GravTargetsStats
 };
 int grav_targets_check(ngravs_ctx *c, long long nt, GravTargetsStats *st, double *far);   // far: the largest distance of a target from the domain's centre
 int walk_targets_run(ngravs_ctx *c, long long nt, double far);
+TreeView tree_view(ngravs_ctx *c);
+// the order the targets of gt_in are walked in: gt_ord's 0 .. nt-1, or (walk_tg_sort) the caller's indices along the Peano curve
+int grav_targets_order(ngravs_ctx *c, long long nt, const unsigned int **ord);
+// ---- kernels_potential.hip
+// The potential walk over ALL own rows into r_pot, self term, LatticeZero term, G, mesh part and the cosmological term (potential.c:
+// 244-337); the column in caller order -> d_out[n_local] (a device buffer of the caller's).  nint: r_nint is NOT written; d_nint
+// (may be null) gets the interaction counts in caller order.
+int potential_run(ngravs_ctx *c, const ngravs_time_params_t *par, double *d_out, int *d_nint);
+// the walk x G (+ the mesh part with a mesh) at the targets of gt_in / gt_type -> gt_acc[nt], gt_nint[nt], caller order
+int potential_targets_run(ngravs_ctx *c, long long nt);
+int potential_lattice_ensure(ngravs_ctx *c);
 // ---- kernels_eval.hip
 int eval_ring_slots(const WalkParams &wp, bool yuk, int waves);
 int launch_eval_ring(ngravs_ctx *c, const TreeView &tv, const WalkParams &wp, bool yuk, int nblk, int waves, int K, const int *region,
@@ -681,6 +702,10 @@ int sph_density_update_device(long long n, const double *sums, double *h, double
 int pm_run(ngravs_ctx *c);
 int pm_deposit(ngravs_ctx *c);
 int pm_finish(ngravs_ctx *c);
+int pm_solve(ngravs_ctx *c);   // the first half of pm_finish: forward FFTs, Green multiply, inverse FFTs -> pm_phi complete
+// += G / (pi BoxSize) x the CIC-weighted potential of the 8 corners of pm_phi, each row reading its species' mesh: for the own rows
+// (tpos null: r_pot, Peano order) or for nt target records (tpos [nt][3], ttype) into out[nt]
+int pm_potential_gather(ngravs_ctx *c, const double *tpos, const int *ttype, long long nt, double *out);
 void pm_release(ngravs_ctx *c);
 // GravPM from pm_phi (pm_mesh_valid) at the targets of gt_in / gt_type -> d_out [nt][3], G included
 int pm_targets_run(ngravs_ctx *c, long long nt, double *d_out);

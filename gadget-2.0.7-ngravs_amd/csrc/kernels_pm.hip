@@ -134,6 +134,49 @@ __global__ void k_gradient_gather_targets(const double *__restrict__ tpos, const
   out[3 * t + 2] = acc[2];
 }
 
+// The mesh potential at one point: the CIC-weighted sum of the 8 corner values, the cells and the corner order of
+// gradient_gather_point (what pmpotential_periodic's read-back means; k = 0 is 0 in pm_phi, as for the force)
+__device__ __forceinline__ double potential_gather_point(const double *__restrict__ grid, double px, double py, double pz, double to_slab, int N)
+{
+  const long long NZ = N + 2;
+  double dx, dy, dz;
+  const int sx = cell_of(px, to_slab, N, &dx), sy = cell_of(py, to_slab, N, &dy), sz = cell_of(pz, to_slab, N, &dz);
+  const double wx[2] = {1.0 - dx, dx}, wy[2] = {1.0 - dy, dy}, wz[2] = {1.0 - dz, dz};
+  const int ox[8] = {0, 0, 0, 0, 1, 1, 1, 1}, oy[8] = {0, 1, 0, 1, 0, 1, 0, 1}, oz[8] = {0, 0, 1, 1, 0, 0, 1, 1};
+  double pot = 0;
+  for(int c = 0; c < 8; c++)
+    {
+      // (a full modulo: a row that has drifted out of the box since the last wrap must not read outside the mesh)
+      const int x = wrapN((sx + ox[c]) % N, N), y = wrapN((sy + oy[c]) % N, N), z = wrapN((sz + oz[c]) % N, N);
+      pot += grid[((long long)x * N + y) * NZ + z] * (wx[ox[c]] * wy[oy[c]] * wz[oz[c]]);
+    }
+  return pot;
+}
+
+// out[i] += fac x the mesh potential of the row's species: the own rows [0, n) of s_pm / s_type (tpos null), or target records
+__global__ void k_potential_gather(const double4 *__restrict__ s_pm, const unsigned char *__restrict__ s_type, const double *__restrict__ tpos,
+                                   const int *__restrict__ ttype, long long n, double to_slab, int N, TypeToGrav t2g,
+                                   const double *__restrict__ phi, double fac, double *__restrict__ out)
+{
+  const long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+  if(i >= n)
+    return;
+  double x, y, z;
+  int type;
+  if(tpos)
+    {
+      x = tpos[3 * i], y = tpos[3 * i + 1], z = tpos[3 * i + 2];
+      type = ttype[i];
+    }
+  else
+    {
+      const double4 p = s_pm[i];
+      x = p.x, y = p.y, z = p.z;
+      type = s_type[i];
+    }
+  out[i] += fac * potential_gather_point(phi + (size_t)t2g.g[type] * N * N * (N + 2), x, y, z, to_slab, N);
+}
+
 // ---------------------------------------------------------------------------------------------------
 // Two-pass gather, per target species: (1) the 4-point finite-difference force of every mesh cell, 3 doubles per cell,
 // streamed; (2) the CIC gather of 8 cell forces per particle (8 x 24 contiguous bytes instead of 96 scattered potential
@@ -458,6 +501,7 @@ int pm_deposit(ngravs_ctx *c)
     }
   const size_t real_elems = (size_t)N * N * (N + 2);
   c->pm_mesh_valid = false;   // a new PM step: pm_phi is rewritten (and may move) before pm_finish has it complete again
+  c->pot_mesh_valid = false;  // ... nor is it the mesh of the last ngravs_compute_potential any more
   if(c->pm_rho.ensure(real_elems * ng) || c->pm_phi.ensure(real_elems * ng) || c->r_pm.ensure(3 * n) || c->d_counters.ensure(16))
     return NGRAVS_ERR_NOMEM;
   if(c->pm_plan_n != N)
@@ -500,36 +544,13 @@ int pm_deposit(ngravs_ctx *c)
 // host all-reduces the density mesh (pm_periodic.c:333-427 ships patches to slab owners instead).
 int pm_finish(ngravs_ctx *c)
 {
+  if(int rc = pm_solve(c))
+    return rc;
   const int N = c->cfg.pmgrid, ng = c->cfg.n_gravs;
   const long long n = c->n;
   const size_t real_elems = (size_t)N * N * (N + 2);
   const double L = c->cfg.box_size, to_slab = N / L;
   const int bs = 256;
-  for(int a = 0; a < ng; a++)
-    FFT_TRY(c, hipfftExecD2Z(*(hipfftHandle *)c->fft_fwd, c->pm_rho.p + real_elems * a,
-                             (hipfftDoubleComplex *)(c->pm_rho.p + real_elems * a)));
-  int rcg = user_green_ensure(c);
-  if(rcg)
-    return rcg;
-  GreenParams gp;
-  make_green_params(c, &gp);
-  long long modes = (long long)N * N * (N / 2 + 1);
-  unsigned nbm = (unsigned)((modes + bs - 1) / bs);
-  switch(ng)
-    {
-    case 1:
-      hipLaunchKernelGGL(k_green<1>, dim3(nbm), dim3(bs), 0, c->stream, (const double2 *)c->pm_rho.p, (double2 *)c->pm_phi.p, gp);
-      break;
-    case 2:
-      hipLaunchKernelGGL(k_green<2>, dim3(nbm), dim3(bs), 0, c->stream, (const double2 *)c->pm_rho.p, (double2 *)c->pm_phi.p, gp);
-      break;
-    default:
-      hipLaunchKernelGGL(k_green<3>, dim3(nbm), dim3(bs), 0, c->stream, (const double2 *)c->pm_rho.p, (double2 *)c->pm_phi.p, gp);
-      break;
-    }
-  for(int b = 0; b < ng; b++)
-    FFT_TRY(c, hipfftExecZ2D(*(hipfftHandle *)c->fft_inv, (hipfftDoubleComplex *)(c->pm_phi.p + real_elems * b),
-                             c->pm_phi.p + real_elems * b));
   double fac = c->cfg.G / (M_PI * L);      // pm_periodic.c:237-238
   fac *= 1 / (2 * L / N);
   // GravPM is needed for this task's own particles only (its target shard); the rest stays zero
@@ -578,6 +599,41 @@ int pm_finish(ngravs_ctx *c)
   return NGRAVS_OK;
 }
 
+// pm_phi from the deposited pm_rho: what the force (pm_finish) and the potential (pm_potential_gather) both read
+int pm_solve(ngravs_ctx *c)
+{
+  const int N = c->cfg.pmgrid, ng = c->cfg.n_gravs;
+  const size_t real_elems = (size_t)N * N * (N + 2);
+  const int bs = 256;
+  for(int a = 0; a < ng; a++)
+    FFT_TRY(c, hipfftExecD2Z(*(hipfftHandle *)c->fft_fwd, c->pm_rho.p + real_elems * a,
+                             (hipfftDoubleComplex *)(c->pm_rho.p + real_elems * a)));
+  int rcg = user_green_ensure(c);
+  if(rcg)
+    return rcg;
+  GreenParams gp;
+  make_green_params(c, &gp);
+  long long modes = (long long)N * N * (N / 2 + 1);
+  unsigned nbm = (unsigned)((modes + bs - 1) / bs);
+  switch(ng)
+    {
+    case 1:
+      hipLaunchKernelGGL(k_green<1>, dim3(nbm), dim3(bs), 0, c->stream, (const double2 *)c->pm_rho.p, (double2 *)c->pm_phi.p, gp);
+      break;
+    case 2:
+      hipLaunchKernelGGL(k_green<2>, dim3(nbm), dim3(bs), 0, c->stream, (const double2 *)c->pm_rho.p, (double2 *)c->pm_phi.p, gp);
+      break;
+    default:
+      hipLaunchKernelGGL(k_green<3>, dim3(nbm), dim3(bs), 0, c->stream, (const double2 *)c->pm_rho.p, (double2 *)c->pm_phi.p, gp);
+      break;
+    }
+  for(int b = 0; b < ng; b++)
+    FFT_TRY(c, hipfftExecZ2D(*(hipfftHandle *)c->fft_inv, (hipfftDoubleComplex *)(c->pm_phi.p + real_elems * b),
+                             c->pm_phi.p + real_elems * b));
+  HIP_TRY(c, hipGetLastError());
+  return NGRAVS_OK;
+}
+
 int pm_targets_run(ngravs_ctx *c, long long nt, double *d_out)
 {
   const int N = c->cfg.pmgrid;
@@ -589,6 +645,21 @@ int pm_targets_run(ngravs_ctx *c, long long nt, double *d_out)
     t2g.g[t] = c->cfg.type_to_grav[t];
   hipLaunchKernelGGL(k_gradient_gather_targets, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, c->stream, c->gt_in.p, c->gt_type.p, nt, N / L, N,
                      t2g, c->pm_phi.p, fac, d_out);
+  HIP_TRY(c, hipGetLastError());
+  return NGRAVS_OK;
+}
+
+int pm_potential_gather(ngravs_ctx *c, const double *tpos, const int *ttype, long long nt, double *out)
+{
+  const int N = c->cfg.pmgrid;
+  const double L = c->cfg.box_size;
+  const double fac = c->cfg.G / (M_PI * L);   // pm_periodic.c:237-238 without the gradient's 1 / (2 L / N)
+  TypeToGrav t2g;
+  for(int t = 0; t < NGRAVS_NTYPES; t++)
+    t2g.g[t] = c->cfg.type_to_grav[t];
+  if(nt <= 0)
+    return NGRAVS_OK;
+  hipLaunchKernelGGL(k_potential_gather, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, c->stream, c->s_pm.p, c->s_type.p, tpos, ttype, nt, N / L, N, t2g, c->pm_phi.p, fac, out);
   HIP_TRY(c, hipGetLastError());
   return NGRAVS_OK;
 }

@@ -1,0 +1,614 @@
+// kernels_potential.hip -- gravitational potentials: P[].Potential of compute_potential() (potential.c:22-345).
+//
+// What the reference's routines MEAN, not what they do (DESIGN.md §8 lists why they cannot be a parity target):
+//   force_treeevaluate_potential            forcetree.c:2560-2768   potential_walk_lane<NG, 0, LATT>
+//   force_treeevaluate_potential_shortrange forcetree.c:2871-3150   potential_walk_lane<NG, 1, 0>
+//   lattice_pot_corr / ewald_psi            forcetree.c:3895ff, ngravs.c:761-816   lat_pot_lookup / k_lattice_pot_table
+//   the tail of compute_potential           potential.c:244-337     k_potential_finish
+// The mesh part (pmpotential_periodic) is kernels_pm.hip's pm_solve + k_potential_gather.
+//
+// The walk is the strict walk's traversal (kernels_walk.hip: wave-lock-step depth-first, every lane its own decision, lane_skip,
+// the pseudo-node flag) with the potential walk's two differences: a periodic tree-only run adds the lattice term in the same
+// visit (no second walk), and the short-range walk prunes by the eff_dist box alone -- here with the table's reach.  Wired companions: newtonian_pot,
+// neg_newtonian_pot, plummer_pot, neg_plummer_pot (ngravs.c:368-489), as the coefficients cN / cS of WalkParams (+1, -1, 0).
+#include "engine.hpp"
+#include "walk_device.hpp"
+#include "columns.hpp"
+
+#pragma clang fp contract(off)
+
+#define POT_LAT_SZ ((size_t)LAT_E1 * LAT_E1 * LAT_E1)
+#define LATTICE_ZERO 2.8372975   // ngravs.c:133
+
+// plummer_pot (ngravs.c:459-472), literal constants
+__device__ __forceinline__ double plummer_pot(double m, double h, double r)
+{
+  const double h_inv = 1 / h;
+  r *= h_inv;
+  if(r < 0.5)
+    return m * h_inv * (-2.8 + r * r * (5.333333333333 + r * r * (6.4 * r - 9.6)));
+  return m * h_inv * (-3.2 + 0.066666666667 / r + r * r * (10.666666666667 + r * (-16.0 + r * (9.6 - 2.133333333333 * r))));
+}
+
+// ewald_psi (ngravs.c:761-816) at x in box units, summed in its order
+__host__ __device__ inline double ewald_psi(const double x[3])
+{
+  const double alpha = 2.0;
+  double sum1 = 0, sum2 = 0;
+  for(int n0 = -4; n0 <= 4; n0++)
+    for(int n1 = -4; n1 <= 4; n1++)
+      for(int n2 = -4; n2 <= 4; n2++)
+        {
+          const double dx[3] = {x[0] - n0, x[1] - n1, x[2] - n2};
+          const double r = sqrt(dx[0] * dx[0] + dx[1] * dx[1] + dx[2] * dx[2]);
+          sum1 += erfc(alpha * r) / r;
+        }
+  for(int h0 = -4; h0 <= 4; h0++)
+    for(int h1 = -4; h1 <= 4; h1++)
+      for(int h2_ = -4; h2_ <= 4; h2_++)
+        {
+          const double hdotx = x[0] * h0 + x[1] * h1 + x[2] * h2_;
+          const int h2 = h0 * h0 + h1 * h1 + h2_ * h2_;
+          if(h2 > 0)
+            sum2 += 1 / (M_PI * h2) * exp(-M_PI * M_PI * h2 / (alpha * alpha)) * cos(2 * M_PI * hdotx);
+        }
+  const double r = sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
+  return M_PI / (alpha * alpha) - sum1 - sum2 + 1 / r;
+}
+
+// one thread per point of the octant grid: out[E1^3] = sign ewald_psi(x) / BoxSize, the origin LatticeZero (forcetree.c:3699-3702)
+__global__ void k_lattice_pot_table(double sign, double box, double *__restrict__ out)
+{
+  const int n = blockIdx.x * blockDim.x + threadIdx.x;
+  if(n >= LAT_E1 * LAT_E1 * LAT_E1)
+    return;
+  const int i = n / (LAT_E1 * LAT_E1), j = (n / LAT_E1) % LAT_E1, k = n % LAT_E1;
+  const double x[3] = {0.5 * ((double)i) / LAT_EN, 0.5 * ((double)j) / LAT_EN, 0.5 * ((double)k) / LAT_EN};
+  out[n] = sign * (n == 0 ? LATTICE_ZERO : ewald_psi(x)) / box;
+}
+
+// lattice_pot_corr (forcetree.c:3895-3941): trilinear lookup in the octant table of one species pair, to be multiplied by the mass
+__device__ __forceinline__ double lat_pot_lookup(const double *__restrict__ a, double fac_intp, double dx, double dy, double dz)
+{
+  double u = fabs(dx) * fac_intp, v = fabs(dy) * fac_intp, w = fabs(dz) * fac_intp;
+  int i = (int)u, j = (int)v, k = (int)w;
+  i = i >= LAT_EN ? LAT_EN - 1 : (i < 0 ? 0 : i);
+  j = j >= LAT_EN ? LAT_EN - 1 : (j < 0 ? 0 : j);
+  k = k >= LAT_EN ? LAT_EN - 1 : (k < 0 ? 0 : k);
+  u -= i;
+  v -= j;
+  w -= k;
+  const double f1 = (1 - u) * (1 - v) * (1 - w), f2 = (1 - u) * (1 - v) * (w), f3 = (1 - u) * (v) * (1 - w), f4 = (1 - u) * (v) * (w),
+               f5 = (u) * (1 - v) * (1 - w), f6 = (u) * (1 - v) * (w), f7 = (u) * (v) * (1 - w), f8 = (u) * (v) * (w);
+  const size_t o = ((size_t)i * LAT_E1 + j) * LAT_E1 + k, sj = LAT_E1, si = (size_t)LAT_E1 * LAT_E1;
+  return a[o] * f1 + a[o + 1] * f2 + a[o + sj] * f3 + a[o + sj + 1] * f4 + a[o + si] * f5 + a[o + si + 1] * f6 + a[o + si + sj] * f7 +
+         a[o + si + sj + 1] * f8;
+}
+
+// One lane's potential walk for a target given by value: the one body of k_potential_walk (own rows) and k_potential_targets
+// (records handed in).  table: PM the long-range potential E [tg][sg][NTAB], LATT the lattice potential [tg][sg][E1^3].
+template <int NG, bool PM, bool LATT>
+__device__ __forceinline__ void potential_walk_lane(const TreeView &tv, const double4 *__restrict__ s_pm, const unsigned char *__restrict__ s_type,
+                                                    const double *__restrict__ table, const WalkParams &wp, const double utorwpi,
+                                                    const double reach, const bool valid, const StrictTarget &T, int *sn, int *ss, int *__restrict__ err_flag,
+                                                    double &pot_out, int &nint_out)
+{
+  const double px = T.x, py = T.y, pz = T.z, aold = T.aold, hT = T.h;
+  const int tg = T.tg;
+  double pot = 0;
+  int nint = 0;
+  const int NO_SKIP = 0x7fffffff;
+  int lane_skip = valid ? NO_SKIP : -1;   // (kernels_walk.hip, strict_walk_lane)
+  int sp = -1;
+
+  // one source (particle or one species of a node): forcetree.c:2725-2768 / :3104ff
+  auto interact = [&](int g, double dx, double dy, double dz, double r2, double m, double h) -> bool {
+    const double r = sqrt(r2);
+    if(PM)
+      {
+        const int tab = (int)(wp.asmthfac * r);
+        if(tab >= NTAB || tab < 0)
+          return false;
+        // the mesh's share of this pair, removed inside h too: the mesh holds it for close pairs and for the particle itself
+        const double lr = m * utorwpi * table[((size_t)tg * NG + g) * NTAB + tab];
+        if(r >= h)
+          pot -= wp.cN[tg][g] * (m / r) - lr;
+        else
+          pot += wp.cS[tg][g] * plummer_pot(m, h, r) + lr;
+      }
+    else
+      {
+        if(r >= h)
+          pot -= wp.cN[tg][g] * (m / r);
+        else
+          pot += wp.cS[tg][g] * plummer_pot(m, h, r);
+        if(LATT)
+          pot += m * lat_pot_lookup(table + ((size_t)tg * NG + g) * POT_LAT_SZ, wp.fac_intp, dx, dy, dz);   // forcetree.c:2737
+      }
+    return true;
+  };
+
+  auto do_particle = [&](int p) {
+    const double4 q = s_pm[p];   // uniform address -> scalar load
+    const int qt = s_type[p];
+    if(lane_skip > sp)
+      {
+        double dx = q.x - px, dy = q.y - py, dz = q.z - pz;
+        if(wp.periodic)
+          {
+            dx = nearest(dx, wp.box, wp.boxhalf);
+            dy = nearest(dy, wp.box, wp.boxhalf);
+            dz = nearest(dz, wp.box, wp.boxhalf);
+          }
+        double h = hT;
+        if(h < wp.fsoft[qt])
+          h = wp.fsoft[qt];
+        const bool added = interact(wp.t2g[qt], dx, dy, dz, dx * dx + dy * dy + dz * dz, q.w, h);
+        if(added || !PM)
+          nint++;
+      }
+  };
+
+  // returns true if some lane wants the node opened
+  auto visit = [&](int c) -> bool {
+    const int fl = tv.flags[c];
+    const double4 geo = tv.geo[c];
+    double4 mom[NG];
+#pragma unroll
+    for(int g = 0; g < NG; g++)
+      mom[g] = tv.mom[(long long)c * NG + g];
+    bool open = false;
+    const bool takes_part = lane_skip > sp;
+    if(takes_part)
+      {
+        double dx[NG], dy[NG], dz[NG], r2[NG];
+        double r2min = INFINITY, r2max = -INFINITY, summass = 0;
+#pragma unroll
+        for(int g = 0; g < NG; g++)
+          {
+            summass += mom[g].w;
+            dx[g] = mom[g].x - px;
+            dy[g] = mom[g].y - py;
+            dz[g] = mom[g].z - pz;
+            if(wp.periodic)
+              {
+                dx[g] = nearest(dx[g], wp.box, wp.boxhalf);
+                dy[g] = nearest(dy[g], wp.box, wp.boxhalf);
+                dz[g] = nearest(dz[g], wp.box, wp.boxhalf);
+              }
+            r2[g] = dx[g] * dx[g] + dy[g] * dy[g] + dz[g] * dz[g];
+            if(r2[g] < r2min)
+              r2min = r2[g];
+            if(r2[g] > r2max)
+              r2max = r2[g];
+          }
+        const double len = geo.w;
+        bool done = false;   // pruned
+        if(PM)
+          {
+            // the eff_dist box of forcetree.c:2990-3021 (no test on r2min in front of it), with the reach of the table, 6 Asmth,
+            // in the place of rcut = 4.5 Asmth: a cell outside it holds no pair with tab < NTAB, so nothing is lost.  The
+            // reference's box drops pairs between the two, each worth erfc(2.25) = 1.5e-3 of its m / r
+            const double eff = reach + 0.5 * len;
+            double d0 = geo.x - px, d1 = geo.y - py, d2 = geo.z - pz;
+            if(wp.periodic)
+              {
+                d0 = nearest(d0, wp.box, wp.boxhalf);
+                d1 = nearest(d1, wp.box, wp.boxhalf);
+                d2 = nearest(d2, wp.box, wp.boxhalf);
+              }
+            if(d0 < -eff || d0 > eff || d1 < -eff || d1 > eff || d2 < -eff || d2 > eff)
+              done = true;
+          }
+        if(!done)
+          {
+            if(wp.use_theta)
+              {
+                if(len * len > r2min * wp.theta2)                      // forcetree.c:2642-2650
+                  open = true;
+              }
+            else
+              {
+                if(summass * len * len > r2min * r2min * aold)         // forcetree.c:2653
+                  open = true;
+                else if(fabs(geo.x - px) < 0.60 * len && fabs(geo.y - py) < 0.60 * len &&
+                        fabs(geo.z - pz) < 0.60 * len)                 // forcetree.c:2660-2670 (no NEAREST)
+                  open = true;
+              }
+          }
+        if(!done && !open)
+          {
+            double h = hT;
+            const int mst = (fl >> 2) & 7;
+            if(mst == 7)
+              open = true;                                             // empty node: nothing below, harmless
+            else
+              {
+                if(h < wp.fsoft[mst])
+                  {
+                    h = wp.fsoft[mst];
+                    if(r2max < h * h && ((fl >> 5) & 1))               // forcetree.c:2685-2696
+                      open = true;
+                  }
+                if(!open)
+                  {
+                    bool added = false;
+#pragma unroll
+                    for(int g = 0; g < NG; g++)
+                      if(mom[g].w != 0.0)
+                        added |= interact(g, dx[g], dy[g], dz[g], r2[g], mom[g].w, h);
+                    if(added || !PM)
+                      nint++;
+                  }
+              }
+          }
+      }
+    const bool wave_open = __any(open ? 1 : 0) != 0;
+    if(wave_open && takes_part && !open)
+      lane_skip = sp + 1;   // the node goes onto the stack at depth sp + 1: this lane is done with everything below it
+    if(wave_open && (fl & FLAG_PSEUDO) && threadIdx.x % WAVE == 0)
+      atomicOr(err_flag, 4);   // a top leaf that was not imported (k_walk_strict reports the same)
+    return wave_open;
+  };
+
+  // lock-step depth-first driver (kernels_walk.hip, strict_walk_lane)
+  if(visit(0))
+    {
+      sp = 0;
+      sn[0] = 0;
+      ss[0] = 0;
+    }
+  while(sp >= 0)
+    {
+      const int node = __builtin_amdgcn_readfirstlane(sn[sp]);
+      const int slot = __builtin_amdgcn_readfirstlane(ss[sp]);
+      const int fl = tv.flags[node];
+      if(fl & FLAG_BUCKET)
+        {
+          const int f = tv.first[node], cnt = tv.count[node];
+          if(slot >= cnt)
+            {
+              sp--;
+              if(lane_skip > sp && lane_skip >= 0)
+                lane_skip = NO_SKIP;
+              continue;
+            }
+          ss[sp] = slot + 1;
+          do_particle(f + slot);
+          continue;
+        }
+      if(slot >= 8)
+        {
+          sp--;
+          if(lane_skip > sp && lane_skip >= 0)
+            lane_skip = NO_SKIP;   // the walk has left the subtree this lane sat out
+          continue;
+        }
+      ss[sp] = slot + 1;
+      const int c = __builtin_amdgcn_readfirstlane(tv.child[8 * (long long)node + slot]);
+      if(c == -1)
+        continue;
+      if(c <= -2)
+        {
+          do_particle(-2 - c);
+          continue;
+        }
+      if(visit(c))
+        {
+          sp++;
+          sn[sp] = c;
+          ss[sp] = 0;
+        }
+    }
+  pot_out = pot;
+  nint_out = nint;
+}
+
+// targets: ALL own rows [0, n) in Peano order, whatever their active flags, 64 consecutive rows per wave
+template <int NG, bool PM, bool LATT>
+__global__ __launch_bounds__(256) void k_potential_walk(TreeView tv, const double4 *__restrict__ s_pm, const unsigned char *__restrict__ s_type,
+                                                        const double *__restrict__ s_oldacc, const double *__restrict__ table, WalkParams wp,
+                                                        double utorwpi, double reach, long long n, double *__restrict__ r_pot, int *__restrict__ r_nint,
+                                                        int *__restrict__ err_flag)
+{
+  __shared__ int st_node[4][MAX_LEVELS + 2], st_slot[4][MAX_LEVELS + 2];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const long long grp = (long long)blockIdx.x * 4 + wave;
+  const long long ti = grp * WAVE + lane;
+  if(grp * WAVE >= n)
+    return;
+  const bool valid = ti < n;
+  StrictTarget T = {0, 0, 0, 0, 0, 1.0, 0};
+  if(valid)
+    {
+      const double4 p = s_pm[ti];
+      T.x = p.x;
+      T.y = p.y;
+      T.z = p.z;
+      T.mass = p.w;
+      const int ptype = s_type[ti];
+      T.tg = wp.t2g[ptype];
+      T.h = wp.fsoft[ptype];
+      T.aold = wp.errtol_acc * s_oldacc[ti];
+    }
+  double pot;
+  int nint;
+  potential_walk_lane<NG, PM, LATT>(tv, s_pm, s_type, table, wp, utorwpi, reach, valid, T, st_node[wave], st_slot[wave], err_flag, pot, nint);
+  if(valid)
+    {
+      r_pot[ti] = pot;
+      r_nint[ti] = nint;
+    }
+}
+
+// targets: records handed in (ngravs_potential_targets), the columns of k_walk_targets; the sum x G goes to the caller's index
+template <int NG, bool PM, bool LATT>
+__global__ __launch_bounds__(256) void k_potential_targets(TreeView tv, const double4 *__restrict__ s_pm, const unsigned char *__restrict__ s_type,
+                                                           const double *__restrict__ table, WalkParams wp, double utorwpi, double reach,
+                                                           const double *__restrict__ t_pos, const double *__restrict__ t_oldacc,
+                                                           const double *__restrict__ t_mass, const int *__restrict__ t_type,
+                                                           const unsigned int *__restrict__ ord, long long nt, double G,
+                                                           double *__restrict__ o_pot, int *__restrict__ o_nint, int *__restrict__ err_flag)
+{
+  __shared__ int st_node[4][MAX_LEVELS + 2], st_slot[4][MAX_LEVELS + 2];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const long long grp = (long long)blockIdx.x * 4 + wave;
+  const long long t = grp * WAVE + lane;
+  if(grp * WAVE >= nt)
+    return;
+  const bool valid = t < nt;
+  StrictTarget T = {0, 0, 0, 0, 0, 1.0, 0};
+  long long me = 0;
+  if(valid)
+    {
+      me = ord[t];
+      T.x = t_pos[3 * me];
+      T.y = t_pos[3 * me + 1];
+      T.z = t_pos[3 * me + 2];
+      T.mass = t_mass[me];
+      const int ptype = t_type[me];
+      T.tg = wp.t2g[ptype];
+      T.h = wp.fsoft[ptype];
+      T.aold = wp.errtol_acc * t_oldacc[me];
+    }
+  double pot;
+  int nint;
+  potential_walk_lane<NG, PM, LATT>(tv, s_pm, s_type, table, wp, utorwpi, reach, valid, T, st_node[wave], st_slot[wave], err_flag, pot, nint);
+  if(valid)
+    {
+      o_pot[me] = pot * G;
+      o_nint[me] = nint;
+    }
+}
+
+// The tail of compute_potential (potential.c:244-337) for one own row, in its order: the self term m / SofteningTable[type] (the
+// negative of what the walk added for the row itself: plummer_pot(m, h, 0) = -2.8 m / h, the same operations), the LatticeZero
+// term of a comoving periodic run, G, the mesh part, the cosmological term
+struct PotTail
+{
+  double fsoft[NGRAVS_NTYPES];
+  int t2g[NGRAVS_NTYPES];
+  double lz[NG_MAX];    // LatticeZero[g][g] (Omega0 3 H^2 / (8 pi G))^(1/3), 0 unless comoving and periodic
+  double G, rfac;       // rfac: -0.5 Omega0 H^2 (comoving, not periodic) or -0.5 OmegaLambda H^2 (not comoving), else 0
+};
+__global__ void k_potential_finish(const double4 *__restrict__ s_pm, const unsigned char *__restrict__ s_type, long long n, PotTail pt,
+                                   const double *__restrict__ mesh, double *__restrict__ r_pot)
+{
+  const long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+  if(i >= n)
+    return;
+  const double4 p = s_pm[i];
+  const int type = s_type[i];
+  double pot = r_pot[i];
+  const double h_inv = 1 / pt.fsoft[type];
+  pot += p.w * h_inv * 2.8;
+  const double lz = pt.lz[pt.t2g[type]];
+  if(lz != 0)
+    pot -= lz * pow(p.w, 2.0 / 3);
+  pot *= pt.G;
+  if(mesh)
+    pot += mesh[i];
+  if(pt.rfac != 0)
+    pot += pt.rfac * (p.x * p.x + p.y * p.y + p.z * p.z);
+  r_pot[i] = pot;
+}
+
+__global__ void k_unpermute_i32(const unsigned int *idx, long long n, const int *src, int *dst)
+{
+  const long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+  if(i < n)
+    dst[idx[i]] = src[i];
+}
+
+#pragma clang fp contract(fast)
+
+// ---- host side ------------------------------------------------------------------------------------------------------------------
+static double law_sign(int law) { return law == NGRAVS_LAW_NEWTON ? 1.0 : (law == NGRAVS_LAW_NEG_NEWTON ? -1.0 : 0.0); }
+
+// the lattice potential tables: one Ewald sum per distinct law, replicated into the [target][source] slots (as ensure_lattice)
+int potential_lattice_ensure(ngravs_ctx *c)
+{
+  if(c->pot_lat_ready)
+    return NGRAVS_OK;
+  const int ng = c->cfg.n_gravs, npts = LAT_E1 * LAT_E1 * LAT_E1;
+  if(c->pot_lat.ensure((size_t)ng * ng * POT_LAT_SZ))
+    return NGRAVS_ERR_NOMEM;
+  for(int k = 0; k < ng * ng; k++)
+    {
+      const double sign = law_sign(c->cfg.law_accel[k / ng][k % ng]);
+      int src = -1;
+      for(int q = 0; q < k && src < 0; q++)
+        if(law_sign(c->cfg.law_accel[q / ng][q % ng]) == sign)
+          src = q;
+      double *dst = c->pot_lat.p + (size_t)k * POT_LAT_SZ;
+      if(src >= 0)
+        HIP_TRY(c, hipMemcpyAsync(dst, c->pot_lat.p + (size_t)src * POT_LAT_SZ, sizeof(double) * POT_LAT_SZ, hipMemcpyDeviceToDevice, c->stream));
+      else
+        hipLaunchKernelGGL(k_lattice_pot_table, dim3((npts + 63) / 64), dim3(64), 0, c->stream, sign, c->cfg.box_size, dst);
+    }
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipGetLastError());
+  c->pot_lat_ready = true;
+  return NGRAVS_OK;
+}
+
+// E[i] = (force_tab[i] + pot_tab[i]) u_i = tempI(u_i) / u_i, the long-range potential of the split (pi erf(u) / u for Newton)
+static int potential_table_ensure(ngravs_ctx *c)
+{
+  if(c->pot_table_ready)
+    return NGRAVS_OK;
+  const int ng = c->cfg.n_gravs;
+  const size_t len = (size_t)ng * ng * NTAB;
+  std::vector<double> f(len), p(len);
+  host_shortrange_table(&c->cfg, f.data(), p.data(), c->user_fns.data(), (int)c->user_fns.size());
+  for(size_t k = 0; k < len; k++)
+    f[k] = (f[k] + p[k]) * (3.0 / NTAB * ((double)(k % NTAB) + 0.5));
+  if(c->pot_table.ensure(len))
+    return NGRAVS_ERR_NOMEM;
+  HIP_TRY(c, hipMemcpyAsync(c->pot_table.p, f.data(), sizeof(double) * len, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  c->pot_table_ready = true;
+  return NGRAVS_OK;
+}
+
+// k_potential_walk / k_potential_targets<NG, PM, LATT>: TreePM, periodic tree-only, tree-only
+template <int NG> using PotRowsNG = Table<Row<NG, 1, 0>, Row<NG, 0, 1>, Row<NG, 0, 0>>;
+using PotRows = decltype(PotRowsNG<1>{} + PotRowsNG<2>{} + PotRowsNG<3>{});
+
+struct PotWalk
+{
+  WalkParams wp;
+  double utorwpi, reach;   // 1 / (2 pi Asmth); NTAB / asmthfac = 6 Asmth: tab < NTAB inside it
+  const double *table;
+  int key[3];
+  int *flag;
+};
+// tables, parameters and the zeroed flag word of one potential walk
+static int potential_walk_setup(ngravs_ctx *c, PotWalk *w)
+{
+  const bool pm = c->cfg.pmgrid != 0, latt = c->cfg.periodic && !pm;
+  int rc;
+  if(pm && (rc = potential_table_ensure(c)))
+    return rc;
+  if(latt && (rc = potential_lattice_ensure(c)))
+    return rc;
+  make_walk_params(c, &w->wp);
+  w->utorwpi = pm ? 1.0 / (2 * M_PI * c->asmth) : 0.0;
+  w->reach = pm ? NTAB / w->wp.asmthfac : 0.0;
+  w->table = pm ? c->pot_table.p : (latt ? c->pot_lat.p : nullptr);
+  w->key[0] = c->cfg.n_gravs, w->key[1] = pm, w->key[2] = latt;
+  if(c->gt_counters.ensure(GT_C_COUNT))
+    return NGRAVS_ERR_NOMEM;
+  HIP_TRY(c, hipMemsetAsync(c->gt_counters.p, 0, GT_C_COUNT * sizeof(unsigned long long), c->stream));
+  w->flag = reinterpret_cast<int *>(c->gt_counters.p + GT_C_FLAG);
+  return NGRAVS_OK;
+}
+static int potential_walk_flag(ngravs_ctx *c, const PotWalk &w)
+{
+  int flag = 0;
+  HIP_TRY(c, hipMemcpyAsync(&flag, w.flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if(flag & 4)
+    {
+      ngravs_report(c, NGRAVS_ERR_STATE, "the potential walk met a top-level cell whose particles are not on this task");
+      return NGRAVS_ERR_STATE;
+    }
+  return NGRAVS_OK;
+}
+
+template <int NG, int PM, int LATT> static int launch_potential(Row<NG, PM, LATT>, ngravs_ctx *c, const PotWalk &w, long long n, int *d_nint)
+{
+  const long long ngroups = (n + WAVE - 1) / WAVE;
+  hipLaunchKernelGGL((k_potential_walk<NG, PM, LATT>), dim3((unsigned)((ngroups + 3) / 4)), dim3(256), 0, c->stream, tree_view(c), c->s_pm.p,
+                     c->s_type.p, c->s_oldacc.p, w.table, w.wp, w.utorwpi, w.reach, n, c->r_pot.p, d_nint, w.flag);
+  return NGRAVS_OK;
+}
+template <int NG, int PM, int LATT>
+static int launch_potential_targets(Row<NG, PM, LATT>, ngravs_ctx *c, const PotWalk &w, long long nt, const unsigned int *ord)
+{
+  const long long ngroups = (nt + WAVE - 1) / WAVE;
+  hipLaunchKernelGGL((k_potential_targets<NG, PM, LATT>), dim3((unsigned)((ngroups + 3) / 4)), dim3(256), 0, c->stream, tree_view(c), c->s_pm.p,
+                     c->s_type.p, w.table, w.wp, w.utorwpi, w.reach, c->gt_in.p, c->gt_in.p + 3 * nt, c->gt_in.p + 4 * nt, c->gt_type.p, ord, nt, c->cfg.G,
+                     c->gt_acc.p, c->gt_nint.p, w.flag);
+  return NGRAVS_OK;
+}
+
+int potential_run(ngravs_ctx *c, const ngravs_time_params_t *par, double *d_out, int *d_nint)
+{
+  const long long n = c->n;
+  const bool pm = c->cfg.pmgrid != 0;
+  // r_pot: the walk's column, behind it the mesh column; gt_nint: the counts in Peano order
+  if(c->r_pot.ensure(2 * (size_t)n) || c->gt_nint.ensure((size_t)n))
+    return NGRAVS_ERR_NOMEM;
+  PotWalk w;
+  int rc;
+  if((rc = potential_walk_setup(c, &w)))
+    return rc;
+  HIP_TRY(c, hipEventRecord(c->evk0, c->stream));
+  if((rc = dispatch(c, PotRows{}, w.key, [&](auto row) { return launch_potential(row, c, w, n, c->gt_nint.p); })))
+    return rc;
+  HIP_TRY(c, hipEventRecord(c->evk1, c->stream));
+  HIP_TRY(c, hipGetLastError());
+  double *mesh = nullptr;
+  if(pm)
+    {
+      // the mesh at the CURRENT positions: deposit, transforms and Green multiply of a PM step, without its force and without
+      // touching r_pm or have_pm; pm_phi is then no longer the last PM step's
+      if((rc = pm_deposit(c)) || (rc = pm_solve(c)))
+        return rc;
+      mesh = c->r_pot.p + n;
+      HIP_TRY(c, hipMemsetAsync(mesh, 0, sizeof(double) * n, c->stream));
+      if((rc = pm_potential_gather(c, nullptr, nullptr, n, mesh)))
+        return rc;
+      c->pot_mesh_valid = true;
+    }
+  PotTail pt;
+  memset(&pt, 0, sizeof(pt));
+  for(int t = 0; t < NGRAVS_NTYPES; t++)
+    {
+      pt.fsoft[t] = c->cfg.force_softening[t];
+      pt.t2g[t] = c->cfg.type_to_grav[t];
+    }
+  pt.G = c->cfg.G;
+  if(par && par->comoving)
+    {
+      if(c->cfg.periodic)
+        for(int g = 0; g < c->cfg.n_gravs; g++)
+          pt.lz[g] = law_sign(c->cfg.law_accel[g][g]) * LATTICE_ZERO *
+                     pow(par->omega0 * 3 * par->hubble * par->hubble / (8 * M_PI * c->cfg.G), 1.0 / 3);   // potential.c:256-257
+      else
+        pt.rfac = -0.5 * par->omega0 * par->hubble * par->hubble;                                         // potential.c:313
+    }
+  else if(par)
+    pt.rfac = -0.5 * par->omega_lambda * par->hubble * par->hubble;                                       // potential.c:326
+  hipLaunchKernelGGL(k_potential_finish, GRID1(n), 0, c->stream, c->s_pm.p, c->s_type.p, n, pt, mesh, c->r_pot.p);
+  hipLaunchKernelGGL(k_unpermute_f64, GRID1(n), 0, c->stream, c->s_idx.p, n, 1, c->r_pot.p, d_out);
+  if(d_nint)
+    hipLaunchKernelGGL(k_unpermute_i32, GRID1(n), 0, c->stream, c->s_idx.p, n, c->gt_nint.p, d_nint);
+  HIP_TRY(c, hipGetLastError());
+  if((rc = potential_walk_flag(c, w)))
+    return rc;
+  float ms = 0;
+  (void)hipEventElapsedTime(&ms, c->evk0, c->evk1);   // (complete: potential_walk_flag waited for the stream)
+  c->pot_walk_ms = ms;
+  return NGRAVS_OK;
+}
+
+int potential_targets_run(ngravs_ctx *c, long long nt)
+{
+  if(c->gt_acc.ensure(3 * (size_t)nt) || c->gt_nint.ensure((size_t)nt))
+    return NGRAVS_ERR_NOMEM;
+  PotWalk w;
+  int rc;
+  if((rc = potential_walk_setup(c, &w)))
+    return rc;
+  const unsigned int *ord;
+  if((rc = grav_targets_order(c, nt, &ord)))
+    return rc;
+  if((rc = dispatch(c, PotRows{}, w.key, [&](auto row) { return launch_potential_targets(row, c, w, nt, ord); })))
+    return rc;
+  HIP_TRY(c, hipGetLastError());
+  if(c->cfg.pmgrid && (rc = pm_potential_gather(c, c->gt_in.p, c->gt_type.p, nt, c->gt_acc.p)))
+    return rc;
+  return potential_walk_flag(c, w);
+}

@@ -127,8 +127,6 @@ struct LawIds
 //  periodic tree-only path: Ewald / lattice-sum correction (reference lattice_init forcetree.c:3611-3793,
 //  ewald_force ngravs.c:1170-1232, yukawa_lattice_force ngravs.c:1019-1090, lattice_corr forcetree.c:3803-3885)
 // =============================================================================================
-#define LAT_EN 64
-#define LAT_E1 (LAT_EN + 1)
 #define LAT_SZ ((size_t)3 * LAT_E1 * LAT_E1 * LAT_E1)
 
 #pragma clang fp contract(off)
@@ -2413,7 +2411,7 @@ static bool has_yukawa(const ngravs_ctx *c)
   return false;
 }
 
-static TreeView tree_view(ngravs_ctx *c)
+TreeView tree_view(ngravs_ctx *c)
 {
   TreeView tv;
   tv.first = c->n_first.p;
@@ -3310,6 +3308,28 @@ int walk_finish(ngravs_ctx *c)
   return NGRAVS_OK;
 }
 
+int grav_targets_order(ngravs_ctx *c, long long nt, const unsigned int **ord)
+{
+  *ord = c->gt_ord.p;   // 0 .. nt-1 (k_grav_tg_prep)
+  if(!c->tune.walk_tg_sort)
+    return NGRAVS_OK;
+  if(c->gt_key.ensure(2 * (size_t)nt))
+    return NGRAVS_ERR_NOMEM;
+  int rc;
+  const double fac21 = c->dom[7] * (double)(1 << (TREE_BITS - NGRAVS_BITS_PER_DIMENSION));
+  if((rc = dom_keys_only(c, c->gt_in.p + 5 * nt, nt, c->dom, fac21, TREE_BITS, reinterpret_cast<long long *>(c->gt_key.p))))
+    return rc;
+  size_t bytes = 0;
+  HIP_TRY(c, hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, c->gt_key.p, c->gt_key.p + nt, c->gt_ord.p, c->gt_ord.p + nt, (int)nt, 0,
+                                                3 * TREE_BITS, c->stream));
+  if(c->gt_tmp.ensure(bytes))
+    return NGRAVS_ERR_NOMEM;
+  HIP_TRY(c, hipcub::DeviceRadixSort::SortPairs(c->gt_tmp.p, bytes, c->gt_key.p, c->gt_key.p + nt, c->gt_ord.p, c->gt_ord.p + nt, (int)nt, 0,
+                                                3 * TREE_BITS, c->stream));
+  *ord = c->gt_ord.p + nt;
+  return NGRAVS_OK;
+}
+
 // ngravs_gravity_tree_targets: the targets that grav_targets_check passed, ordered along the Peano curve of the engine's domain
 // (the wave moves in lock-step: 64 targets far apart cost the union of their walks), walked by k_walk_targets
 int walk_targets_run(ngravs_ctx *c, long long nt, double far)
@@ -3327,21 +3347,9 @@ int walk_targets_run(ngravs_ctx *c, long long nt, double far)
   make_walk_params(c, &wp);
   LawIds li;
   make_law_ids(c, &li);
-  const unsigned int *ord = c->gt_ord.p;   // 0 .. nt-1 (k_grav_tg_prep)
-  if(c->tune.walk_tg_sort)
-    {
-      const double fac21 = c->dom[7] * (double)(1 << (TREE_BITS - NGRAVS_BITS_PER_DIMENSION));
-      if((rc = dom_keys_only(c, c->gt_in.p + 5 * nt, nt, c->dom, fac21, TREE_BITS, reinterpret_cast<long long *>(c->gt_key.p))))
-        return rc;
-      size_t bytes = 0;
-      HIP_TRY(c, hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, c->gt_key.p, c->gt_key.p + nt, c->gt_ord.p, c->gt_ord.p + nt, (int)nt, 0,
-                                                    3 * TREE_BITS, c->stream));
-      if(c->gt_tmp.ensure(bytes))
-        return NGRAVS_ERR_NOMEM;
-      HIP_TRY(c, hipcub::DeviceRadixSort::SortPairs(c->gt_tmp.p, bytes, c->gt_key.p, c->gt_key.p + nt, c->gt_ord.p, c->gt_ord.p + nt, (int)nt, 0,
-                                                    3 * TREE_BITS, c->stream));
-      ord = c->gt_ord.p + nt;
-    }
+  const unsigned int *ord;
+  if((rc = grav_targets_order(c, nt, &ord)))
+    return rc;
   const int key[] = {c->cfg.n_gravs, pm, latt, wp.user != 0, 0};
   if((rc = dispatch(c, StrictRows{}, key, [&](auto row) { return launch_strict_targets(row, c, wp, li, nt, ord); })))
     return rc;

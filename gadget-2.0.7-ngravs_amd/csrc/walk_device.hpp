@@ -6,6 +6,9 @@
 #ifndef WAVE
 #define WAVE 64
 #endif
+// the octant grid of the lattice tables, force (kernels_walk.hip) and potential (kernels_potential.hip): NGRAVS_EN + 1 points a side
+#define LAT_EN 64
+#define LAT_E1 (LAT_EN + 1)
 
 __device__ __forceinline__ double nearest(double x, double box, double boxhalf)
 {

@@ -42,8 +42,11 @@ class Timeline:
         time_bet_statistics: None (no energy statistics), or All.TimeBetStatistics: whenever All.Time has passed the last
         statistics by that much (run.c:52-59), on_station("statistics", timeline) is called in front of the "advance" station,
         sys_state becomes the abi.SysState of compute_global_quantities_of_system(), and the line of energy.txt is appended to
-        energy_lines and to energy_file (a path opened for append, or an object with write).  potential: None, or a function of
-        the timeline that returns the P[].Potential column (of the kind of the columns) or None; the loop computes no potentials.
+        energy_lines and to energy_file (a path opened for append, or an object with write).  potential: None (no potentials:
+        EnergyPot is 0 and no POT block), a function of the timeline that returns the P[].Potential column (of the kind of the
+        columns) or None, or "device": the statistics and the snapshot station call Engine.compute_potential on the columns as
+        drifted (compute_potential(), potential.c:22-345; the snapshot station hands the moved particles over and builds the tree
+        first, potential.c:50-61) and potential_column is that column afterwards.
         output: None (no snapshot files; the loop is then exactly the one without this argument), or a dict: dir (All.OutputDir,
         with its separator), base (All.SnapshotFileBase), snap_format (1 or 2), rule (abi.make_output_rule: the list of output
         times, or TimeOfFirstSnapshot / TimeBetSnapshot), blocks_mask (abi.snap_mask), mass_table (All.MassTable), ids (a function
@@ -74,7 +77,10 @@ class Timeline:
         self.time_bet_statistics = None if time_bet_statistics is None else float(time_bet_statistics)
         if self.time_bet_statistics is not None:
             self.time_last_statistics = par.time_begin - self.time_bet_statistics   # init.c:94
+        if isinstance(potential, str) and potential != "device":
+            raise ValueError('potential: None, a function of the timeline, or "device"')
         self.potential, self.sys_state, self.energy_lines = potential, None, []
+        self.potential_column = None
         self._energy_file = open(energy_file, "a") if isinstance(energy_file, (str, bytes)) or hasattr(energy_file, "__fspath__") else energy_file
         self.output = None if output is None else dict(output)
         if self.output is not None:
@@ -93,9 +99,11 @@ class Timeline:
     def _time_cols(self, names):
         return {k: self.cols[k] for k in names if k in self.cols}
 
-    def _hand_over(self, rebuild):
-        """P[] to the engine: a new particle set in front of a decomposition, else the drifted rows of the kept tree"""
+    def _hand_over(self, rebuild, pos=None):
+        """P[] to the engine: a new particle set in front of a decomposition, else the drifted rows of the kept tree.  pos: the
+        position column to hand over instead of the caller's"""
         c = self.cols
+        pos = c["pos"] if pos is None else pos
         if self.device:
             import torch
             act = (c["ti_endstep"] == self.ti_current).to(torch.uint8)
@@ -104,7 +112,7 @@ class Timeline:
             act = (c["ti_endstep"] == self.ti_current).astype(np.uint8)
         p = abi.Particles()
         p.n = self.n
-        p.pos, p.pos_stride = _addr(c["pos"]), 24
+        p.pos, p.pos_stride = _addr(pos), 24
         p.mass, p.mass_stride = _addr(c["mass"]), 8
         p.type, p.type_stride = _addr(c["type"]), 4
         p.old_acc, p.old_acc_stride = _addr(c["old_acc"]), 8
@@ -129,11 +137,37 @@ class Timeline:
         eng._check(self._lib.ngravs_get_accel(eng._h, _addr(c["grav_accel"]), 24, _addr(c["grav_pm"]) if self.mesh else None, 24,
                                               _addr(c["old_acc"]), 8, None, 0, int(self.device), 1), "ngravs_get_accel")
 
+    def _potential(self, moved):
+        """the P[].Potential column of a station, or None.  "device": compute_potential() of the engine; moved: the columns have
+        been drifted since the engine saw them, so they are handed over and the tree is built first (potential.c:50-61) -- a
+        periodic run hands over the positions mapped back onto the box, which the potential does not notice"""
+        if self.potential != "device":
+            return self.potential(self) if self.potential else None
+        eng, c = self.eng, self.cols
+        if moved:
+            pos = c["pos"]
+            if eng.cfg.periodic:
+                box = eng.cfg.box_size
+                pos = pos - box * (pos / box).floor() if self.device else pos - box * np.floor(pos / box)
+                pos[pos >= box] = 0.0   # (-1e-17 + box rounds to box)
+            self._hand_over(True, pos=pos)
+            eng.domain_Decomposition()
+            eng.force_treebuild()
+            self.have_tree = True
+        if self.potential_column is None:
+            if self.device:
+                import torch
+                self.potential_column = torch.zeros(self.n, dtype=torch.float64, device=c["pos"].device)
+            else:
+                self.potential_column = np.zeros(self.n)
+        eng.compute_potential(self.par, into=self.potential_column)
+        return self.potential_column
+
     def _statistics(self):
-        """energy_statistics() (run.c:413-433) on the columns as they are, without the potential computation"""
+        """energy_statistics() (run.c:413-433) on the columns as they are, with compute_potential() first when potential is "device" """
         from . import energy_line
         self._station("statistics")
-        pot = self.potential(self) if self.potential else None
+        pot = self._potential(moved=False)
         self.sys_state = self.eng.global_quantities(self._time_cols(TIME_COLS), self.par, self.ti_current, self.pm_ti, pot)
         line = energy_line(self.sys_state, self.time)
         self.energy_lines.append(line)
@@ -156,7 +190,7 @@ class Timeline:
         if o is None:
             raise ValueError("the timeline has no output=")
         self._station("snapshot")
-        pot = self.potential(self) if self.potential else None
+        pot = self._potential(moved=True)
         mask = int(o.get("blocks_mask", abi.SNAP_ALWAYS))
         mask = (mask | (1 << abi.SNAP_POT)) if pot is not None else (mask & ~(1 << abi.SNAP_POT))
         path = "%s%s_%03d" % (os.fspath(o.get("dir", "")), o.get("base", "snapshot"), self.snapshot_file_count)

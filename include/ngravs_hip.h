@@ -847,8 +847,8 @@ int ngravs_advance_and_find_timesteps(ngravs_ctx *ctx, const ngravs_time_cols_t 
  * (run.c:413-433), the station of the main loop between compute_accelerations() and advance_and_find_timesteps() (run.c:52-59).
  * Split like the displacement constraint: the local sums on the device, then a host rule on the (all-reduced) sums, so that a host
  * with several tasks adds the 78 numbers of its tasks in between (the reference's MPI_Reduce, global.c:118-127).
- * The potential is NOT computed: P[].Potential is a column the caller may hand in; without it EnergyPot is 0, as in the reference
- * built without COMPUTE_POTENTIAL_ENERGY. */
+ * P[].Potential is a column the caller hands in, ngravs_compute_potential's or its own; without it EnergyPot is 0, as in the
+ * reference built without COMPUTE_POTENTIAL_ENERGY. */
 #define NGRAVS_GLOBAL_NSUMS 78
 typedef struct {   /* struct state_of_system, allvars.h, field for field: 119 doubles, 952 bytes; [3] of a vector is its norm */
   double Mass, EnergyKin, EnergyPot, EnergyInt, EnergyTot, Momentum[4], AngMomentum[4], CenterOfMass[4];
@@ -890,7 +890,7 @@ int ngravs_energy_line(const ngravs_sysstate_t *s, double time, char *buf, int64
  *   MASS  Mass, only for the types whose mass_table entry is 0 (io.c:501-508)
  *   U     dmax(MinEgySpec, Entropy / (gamma - 1) * pow(Density a3inv, gamma - 1)); gamma == 1: Entropy (ISOTHERM_EQS)
  *   RHO HSML ENDT   Density, Hsml, DtEntropy of the type-0 rows
- *   POT   snap->potential (the library computes none); the block exists only with the column
+ *   POT   snap->potential (ngravs_compute_potential's column, or the caller's own); the block exists only with the column
  *   ACCE  fac1 GravAccel; with a mesh: += fac1 GravPM; type 0: += fac2 HydroAccel  (fac1 = 1 / a^2, fac2 = 1 / a^(3 gamma - 2))
  *   TSTP  (Ti_endstep - Ti_begstep) Timebase_interval
  * a = time_begin exp(ti_current timebase_interval) when comoving, else 1.  The context supplies PERIODIC, BoxSize and PMGRID.
@@ -899,7 +899,7 @@ int ngravs_energy_line(const ngravs_sysstate_t *s, double time, char *buf, int64
  * that is not finite or has |x| >= 1024 BoxSize (the reference's loops would run that many trips, and for ever from 2^24 box
  * lengths on), snap_format 3 (no HDF5).  NGRAVS_ERR_STATE: a block call before a plan or with an n that is not the plan's.
  * Not provided: HDF5, LONGIDS, LONG_X/Y/Z, several files per snapshot and the communicator driver for several tasks (the ranged
- * block call is the per-task half), restart files, the computation of potentials. */
+ * block call is the per-task half), restart files. */
 enum { NGRAVS_SNAP_POS, NGRAVS_SNAP_VEL, NGRAVS_SNAP_ID, NGRAVS_SNAP_MASS, NGRAVS_SNAP_U, NGRAVS_SNAP_RHO, NGRAVS_SNAP_HSML,
        NGRAVS_SNAP_POT, NGRAVS_SNAP_ACCE, NGRAVS_SNAP_ENDT, NGRAVS_SNAP_TSTP, NGRAVS_SNAP_NBLOCKS };   /* enum iofields, allvars.h */
 typedef struct {
@@ -940,6 +940,44 @@ int ngravs_snapshot_write(ngravs_ctx *ctx, const ngravs_time_cols_t *cols, const
  * time_begin, time_max and comoving of par.  NGRAVS_ERR_ARG with a message in ngravs_last_error(NULL) where the reference ends
  * with 13123 (TimeBetSnapshot <= 1 comoving, <= 0 otherwise), 110 or 111 (no time found in a million steps). */
 int ngravs_find_next_outputtime(const ngravs_time_params_t *par, const ngravs_output_rule_t *rule, int32_t ti_curr, int32_t *ti_next);
+
+/* ---- Gravitational potentials: compute_potential() (potential.c:22-345) for one task -- the column ngravs_global_sums and the POT
+ * block of a snapshot take.  What the reference's potential routines mean, not what they do (DESIGN.md §8 lists their defects).
+ * Built-in laws with a wired potential companion: NGRAVS_LAW_NEWTON / NGRAVS_LAW_NEG_NEWTON (newtonian_pot, neg_newtonian_pot) with
+ * NGRAVS_SPLINE_PLUMMER / NGRAVS_SPLINE_NEG_PLUMMER (plummer_pot, neg_plummer_pot; ngravs.c:368-489); a pair wired NONE gives 0.
+ * For ALL own rows, whatever their active flags, in the order of potential.c:244-337:
+ *   1. the potential walk of the built tree with the context's opening criterion (the strict walk's traversal): per source of mass
+ *      m at distance r, h = max(h_target, h_source):  r >= h: -= Pfn(m, r);  r < h: += Pspl(m, h, r);  periodic tree-only: += m x
+ *      the trilinear lookup of sign(law) ewald_psi / BoxSize in the same visit;  TreePM, for r < 6 Asmth: the long-range share
+ *      m erf(r / 2 Asmth) / r of the pair is removed from both branches, from the row's own visit too (the mesh holds it)
+ *   2. += m / SofteningTable[type] = 2.8 m / force_softening[type]
+ *   3. comoving and periodic: -= LatticeZero[g][g] m^(2/3) (Omega0 3 H^2 / (8 pi G))^(1/3), LatticeZero = sign(law) 2.8372975
+ *   4. *= G
+ *   5. TreePM: += G / (pi BoxSize) x the CIC read-back of the mesh potential (deposit, transforms and Green multiply at the CURRENT
+ *      positions; k = 0 is 0, as for the force)
+ *   6. comoving, not periodic: += -0.5 Omega0 H^2 |pos|^2;  not comoving: += -0.5 OmegaLambda H^2 |pos|^2
+ * par: the parameters of the time calls (comoving, omega0, omega_lambda, hubble are read), or NULL: neither comoving nor Lambda.
+ * potential: the caller's column, stride in bytes, caller's row order; nint (may be NULL): the interactions of every row's walk,
+ * int32, contiguous.  GravAccel, GravPM, OldAcc and the costs of the last force computation stay as they are; with a mesh the call
+ * rewrites the potential mesh: ngravs_pm_targets is refused until the next PM step, ngravs_potential_targets is served until the
+ * next PM step or hand-over of particles.
+ * NGRAVS_ERR_ARG for a NULL ctx.  Refused with a message and nothing written: NGRAVS_ERR_ARG for a NULL potential, world_size > 1 or
+ * a multi-task working set, adaptive gas softening, a Yukawa, coloyuk, BAM or user law in a wired pair, a mesh without periodic
+ * boundaries; NGRAVS_ERR_STATE without a built tree of the current particle set (after ngravs_update_particles it is refit first). */
+int ngravs_compute_potential(ngravs_ctx *ctx, const ngravs_time_params_t *par, double *potential, int64_t potential_stride,
+                             int32_t on_device, int32_t *nint);
+/* Step 1 x G, plus step 5 with a mesh, at nt target records (the records of ngravs_gravity_tree_targets, any order, any finite
+ * position when not periodic): no self term, no cosmological term -- the potential of this engine's particles at the targets, so
+ * that the potential of a set split over engines is the sum over the engines.  pot[nt] and nint[nt] (may be NULL), contiguous,
+ * of the kind of the records.  With a mesh the mesh of the last ngravs_compute_potential is read: NGRAVS_ERR_STATE without one.
+ * Other refusals as above and as for ngravs_gravity_tree_targets' records. */
+int ngravs_potential_targets(ngravs_ctx *ctx, const ngravs_grav_targets_t *targets, int64_t nt, double *pot, int32_t *nint);
+/* The lattice potential table of the pair (target, source) as the periodic tree-only walk reads it: out[65^3] (host),
+ * [i][j][k] = sign(law) ewald_psi(i / 128, j / 128, k / 128) / BoxSize, the origin sign(law) 2.8372975 / BoxSize.  Tabulated on the
+ * device at the first use.  NGRAVS_ERR_ARG unless the configuration is periodic without a mesh and the pair is wired. */
+int ngravs_lattice_potential_table(ngravs_ctx *ctx, int32_t target, int32_t source, double *out);
+/* device milliseconds of the walk kernel of the last ngravs_compute_potential (HIP events) */
+int ngravs_last_potential_ms(ngravs_ctx *ctx, double *walk_ms);
 
 #ifdef __cplusplus
 }
