@@ -32,7 +32,7 @@ EXPORTS = [
     "ngravs_set_particles",
     "ngravs_set_old_acc", "ngravs_set_gas_softening", "ngravs_update_particles", "ngravs_force_update_tree", "ngravs_domain_decomposition", "ngravs_discard_grav_pm",
     "ngravs_force_treebuild", "ngravs_gravity_tree",
-    "ngravs_pmforce_periodic", "ngravs_compute_accelerations", "ngravs_get_accel", "ngravs_get_stats", "ngravs_walk_unopened",
+    "ngravs_pmforce_periodic", "ngravs_compute_accelerations", "ngravs_get_accel", "ngravs_get_stats", "ngravs_walk_unopened", "ngravs_walk_moment_skips",
     "ngravs_get_domain", "ngravs_get_keys", "ngravs_get_order", "ngravs_get_shard", "ngravs_last_error",
     "ngravs_peano_hilbert_key", "ngravs_peano_keys", "ngravs_shortrange_table", "ngravs_direct_sum", "ngravs_direct_sum_targets",
     "ngravs_dd_num_local", "ngravs_dd_local_extent", "ngravs_dd_set_extent", "ngravs_get_domain_extent", "ngravs_dd_set_toptree",
@@ -581,6 +581,13 @@ class Engine:
         v = C.c_int64(0)
         self._check(lib().ngravs_walk_unopened(self._h, C.byref(v)), "ngravs_walk_unopened")
         return int(v.value)
+
+    def walk_moment_skips(self):
+        """(skips, within_reach) of the last group walk's traversal: nodes opened from the node head alone, their moments never
+        fetched, out of the nodes within reach of their group; (0, 0) when the walk ran without the head"""
+        s, w = C.c_int64(0), C.c_int64(0)
+        self._check(lib().ngravs_walk_moment_skips(self._h, C.byref(s), C.byref(w)), "ngravs_walk_moment_skips")
+        return int(s.value), int(w.value)
 
     def set_opening(self, theta, err_tol_force_acc):
         self._check(lib().ngravs_set_opening(self._h, theta, err_tol_force_acc), "ngravs_set_opening")

@@ -169,6 +169,11 @@ struct TreeView
   const int *first, *count, *child, *flags;
   const int *npart;        // particles per species below a node (NGRAVS_ACCUMULATOR, allvars.h:645-648); null unless a BAM law is wired
   const double4 *geo, *mom;
+  // node head of the group walk: {flags, first, count, float bits of mass_lo} per node, mass_lo = the sum of the node's species
+  // masses rounded toward zero to float.  Null unless the tree is a freshly built single-task tree (ngravs_ctx::head_valid) and
+  // the tuning walk_head is on: the walk then reads flags, first and count from their own arrays and always fetches the moments
+  const int4 *head;
+  double head_eps;         // slack of the head's distance bound: 2^-40 x the largest coordinate magnitude of the domain
   int nnodes;
   // start table of the group walk (TreePM only): node index of every cell of one complete tree level, [ix][iy][iz]
   const int *ltab;
@@ -190,6 +195,7 @@ struct Tuning
   int walk_ring = 1;        // TreePM evaluation through the ring-pool kernel (kernels_eval.hip); 0: k_walk_group2<...,2>
   int walk_ring_k = 0;      // ... with at most this many slots per wave (0: as many as fit, at most 8)
   int pm_cus = -1;          // PM beside the walk on this many reserved CUs (-1: chosen per step, 0: PM and walk one after another)
+  int walk_head = 1;        // group walk traversal reads the node head (TreeView::head); 0: the separate arrays, moments always fetched
   int walk_tg_sort = 1;     // ngravs_gravity_tree_targets walks its targets in Peano order (0: in the caller's order, for measurements)
   int sph_verbose = 0;      // ngravs_sph_density prints its iteration statistics (targets, rounds, candidates, neighbours) to stdout
 };
@@ -299,6 +305,8 @@ struct ngravs_ctx
   int64_t level_start[MAX_LEVELS + 2];
   DevBuf<int> n_first, n_count, n_child, n_flags, n_nchild;
   DevBuf<double4> n_geo, n_mom;
+  DevBuf<int4> n_head;        // see TreeView::head (written by k_moments of a build)
+  bool head_valid = false;    // n_head matches n_flags / n_first / n_count / n_mom: set by the build, cleared by whatever alters them afterwards
   DevBuf<int> tb_count;   // one-pass build: per-level node counts of every block of particles
   DevBuf<int> n_npart;        // [nodes][NG] particle counts per species (BAM wirings only)
   DevBuf<int> scan_out;
@@ -319,12 +327,13 @@ struct ngravs_ctx
   int walk_spread = 0;        // > 1: every group of 64 targets is walked as `spread` sub-groups by the fused kernel
   int walk_sg = 1;            // split walk: groups per traversal unit (shared item lists) of the last launch
   long long walk_unopened = 0;   // top leaves the last group walk wanted opened but had to use as monopoles (not imported)
+  long long walk_moment_skips = 0, walk_head_survivors = 0;   // last group walk: nodes opened without their moments / nodes within reach (0 without a head)
   int walk_unit_state = 4;    // groups per traversal unit the TreePM walk is in (4, 2 or 1): changed with hysteresis on walk_ia_ratio
   double walk_ia_ratio = 0;   // pairs per target of the last TreePM group walk / what a uniform box of the same mean density gives
                               // (0: no such walk yet): > 1 in clustered sets, where smaller traversal units accept more cells
   bool all_active = true;     // the caller passed no active flags
   DevBuf<int> walk_ovf;       // split walk: groups left to the fused kernel (lists or LIFO outgrew their region)
-  DevBuf<int> walk_counters;  // [1] overflow flag, [2] groups in walk_ovf, [3] of them by the LIFO, [8..15] per-XCD group counters, [16..23] 64-bit walk statistics
+  DevBuf<int> walk_counters;  // [1] overflow flag, [2] groups in walk_ovf, [3] of them by the LIFO, [8..15] per-XCD group counters, [16..23] 64-bit walk statistics, [26..29] 64-bit node-head statistics
   DevBuf<double> r_acc, r_pm, r_oldacc;
   DevBuf<int> r_nint;
   // pm

@@ -548,7 +548,7 @@ __global__ void k_moments(const double4 *__restrict__ s_pm, const unsigned char 
                           const int *__restrict__ n_child, const double4 *__restrict__ n_geo,
                           double4 *__restrict__ n_mom, int *__restrict__ n_flags, int node0, int nnodes_level,
                           WalkParams wp, double4 *__restrict__ geo_rw = nullptr, int *__restrict__ n_npart = nullptr,
-                          int *__restrict__ n_count_rw = nullptr)
+                          int *__restrict__ n_count_rw = nullptr, int4 *__restrict__ n_head = nullptr)
 {
   int t = blockIdx.x * blockDim.x + threadIdx.x;
   if(t >= nnodes_level)
@@ -731,9 +731,21 @@ __global__ void k_moments(const double4 *__restrict__ s_pm, const unsigned char 
   const int cnt_node = (n_count_rw && !(fl & FLAG_BUCKET)) ? cnt_acc : n_count[node];
   const bool range_coded = (fl & FLAG_BUCKET) || (cnt_node <= FLAG_SPECIES_SLOTS && !(fl & FLAG_PARTIAL));
   const unsigned sp = NG > 1 ? ((range_coded ? sp_range : sp_slot) & 0xffffu) : 0u;
-  n_flags[node] = (fl & (FLAG_BUCKET | FLAG_PSEUDO | FLAG_PARTIAL)) | (4 * sa.maxsofttype + 32 * sa.diff) | (int)(sp << FLAG_SPECIES_SHIFT);
+  const int fl_out = (fl & (FLAG_BUCKET | FLAG_PSEUDO | FLAG_PARTIAL)) | (4 * sa.maxsofttype + 32 * sa.diff) | (int)(sp << FLAG_SPECIES_SHIFT);
+  n_flags[node] = fl_out;
   if(n_count_rw && !(fl & FLAG_BUCKET))
     n_count_rw[node] = cnt_acc;
+  if(n_head)
+    {
+      // the group walk's node head (TreeView::head): mass_lo bounds the walk's own sum of the species masses (same terms, same
+      // order) from below, so it is rounded toward zero
+      double summass = 0;
+#pragma unroll
+      for(int g = 0; g < NG; g++)
+        summass += m[g];
+      const float mass_lo = summass > 0 ? __double2float_rz(summass) : 0.0f;
+      n_head[node] = make_int4(fl_out, n_first[node], cnt_node, __float_as_int(mass_lo));
+    }
 }
 
 // Global top of a multi-task tree: monopoles and softening flags of the tree nodes that are top-tree nodes, from the all-reduced
@@ -786,6 +798,7 @@ __global__ void k_top_moments(const int *__restrict__ n_top, const int *__restri
 static int tree_top_moments(ngravs_ctx *c)
 {
   const TopTree &t = c->top;
+  c->head_valid = false;   // moments and flags of the top nodes change
   WalkParams wp;
   make_walk_params(c, &wp);
   for(int l = (t.h.depth < c->nlevels - 1 ? t.h.depth : c->nlevels - 1); l >= 0; l--)
@@ -930,6 +943,16 @@ int tree_moments(ngravs_ctx *c, bool refit, bool counts)
   WalkParams wp;
   make_walk_params(c, &wp);
   int *cntp = counts ? c->n_count.p : nullptr;
+  // the node head is written by the build of a single-task tree only: a refit and the global top of a multi-task tree alter
+  // fields it holds, and the walks of such trees read the separate arrays
+  c->head_valid = false;
+  int4 *headp = nullptr;
+  if(!refit && !c->top.on)
+    {
+      if(c->n_head.ensure((size_t)c->max_nodes))
+        return NGRAVS_ERR_NOMEM;
+      headp = c->n_head.p;
+    }
   for(int l = c->nlevels - 1; l >= 0; l--)
     {
       long long l0 = c->level_start[l], lc = c->level_start[l + 1] - l0;
@@ -940,21 +963,22 @@ int tree_moments(ngravs_ctx *c, bool refit, bool counts)
         {
         case 1:
           hipLaunchKernelGGL(k_moments<1>, dim3(nb), dim3(bs), 0, c->stream, c->s_pm.p, c->s_type.p, c->n_first.p,
-                             c->n_count.p, c->n_child.p, c->n_geo.p, c->n_mom.p, c->n_flags.p, (int)l0, (int)lc, wp, grw, npp, cntp);
+                             c->n_count.p, c->n_child.p, c->n_geo.p, c->n_mom.p, c->n_flags.p, (int)l0, (int)lc, wp, grw, npp, cntp, headp);
           break;
         case 2:
           hipLaunchKernelGGL(k_moments<2>, dim3(nb), dim3(bs), 0, c->stream, c->s_pm.p, c->s_type.p, c->n_first.p,
-                             c->n_count.p, c->n_child.p, c->n_geo.p, c->n_mom.p, c->n_flags.p, (int)l0, (int)lc, wp, grw, npp, cntp);
+                             c->n_count.p, c->n_child.p, c->n_geo.p, c->n_mom.p, c->n_flags.p, (int)l0, (int)lc, wp, grw, npp, cntp, headp);
           break;
         default:
           hipLaunchKernelGGL(k_moments<3>, dim3(nb), dim3(bs), 0, c->stream, c->s_pm.p, c->s_type.p, c->n_first.p,
-                             c->n_count.p, c->n_child.p, c->n_geo.p, c->n_mom.p, c->n_flags.p, (int)l0, (int)lc, wp, grw, npp, cntp);
+                             c->n_count.p, c->n_child.p, c->n_geo.p, c->n_mom.p, c->n_flags.p, (int)l0, (int)lc, wp, grw, npp, cntp, headp);
           break;
         }
     }
   HIP_TRY(c, hipGetLastError());
   if(c->top.on)
     return tree_top_moments(c);
+  c->head_valid = headp != nullptr;
   return NGRAVS_OK;
 }
 

@@ -850,6 +850,10 @@ __global__ __launch_bounds__(MODE == 1 ? GW3_TBLOCK : (MODE == 2 ? GW2_MAXWAVES 
   // walk statistics: summed per wave over its groups and flushed ONCE (device-scope atomics on four shared addresses,
   // one set per group, serialise in the memory controller and cost more than the traversal itself)
   unsigned long long acc_st[4] = {0, 0, 0, 0};
+  // node head: nodes opened without their moments / nodes that passed (i).  Counted per lane in ONE packed register per group
+  // (hstat below) and summed over the wave after the traversal: the traversal kernel holds the group's box and the walk's
+  // constants in scalar registers and has none to spare for counters kept through the loop
+  unsigned long long acc_hd[2] = {0, 0};   // (the persistent kernels: flushed once per wave)
   for(;;)
     {
       long long grp = -1;
@@ -1043,6 +1047,7 @@ __global__ __launch_bounds__(MODE == 1 ? GW3_TBLOCK : (MODE == 2 ? GW2_MAXWAVES 
       double ax = 0, ay = 0, az = 0;
       int nint = 0;
       int st_entries = 0, st_nodes = 0, st_batches = 0;   // walk statistics (per group, wave-uniform)
+      unsigned hstat = 0;   // node head, this lane's nodes of this group (a lane tests a 64th of a unit's nodes: far below 2^16)
 
       // ES list entries against this lane's target as straight-line code (no branch on the common path).  Measured at C4
       // (round 2): with 4 waves per SIMD the latencies are hidden by the other waves, and one entry per trip beats two
@@ -1795,14 +1800,23 @@ __global__ __launch_bounds__(MODE == 1 ? GW3_TBLOCK : (MODE == 2 ? GW2_MAXWAVES 
           // opened (dec >= 2): bit 0 FLAG_PARTIAL, bits 1-16 the node's species field (FLAG_SPECIES_*)
           unsigned info = 0;
           bool pseudo_hit = false;
+          // (wave-uniform: a scalar branch.  TreePM walks only: the cut makes nearly every node within reach an opened one -- 95 % take
+          // the shortcut at C4 --, while a tree-only walk accepts most of what it tests -- 9 % in a Plummer sphere, where head
+          // and test cost the traversal a wave per SIMD and half its time again, 1.27 -> 1.90 ms at 2^22)
+          const bool hd = PM && tv.head != nullptr;
           int4 ch_lo = {-1, -1, -1, -1}, ch_hi = {-1, -1, -1, -1};
           if(my >= 0)
             {
               // The kernels are bound by the number of scattered lane-loads (the other waves hide the latency), so the
               // record is fetched in stages: geometry first, the multipole moments only if the cell is within reach, the child
               // links only if the node is opened.
+              // With a node head (tv.head: flags, first, count and a lower bound of the mass in ONE 16-byte record, valid for a
+              // freshly built single-task tree) the second stage is often not needed at all: see `sure` below.
               const double4 geo = tv.geo[my];
-              const int fl = tv.flags[my];
+              int4 head = {0, 0, 0, 0};
+              if(hd)
+                head = tv.head[my];
+              const int fl = hd ? head.x : tv.flags[my];
               const double len = geo.w, half = 0.5 * len;
               double cx = geo.x - bcx, cy = geo.y - bcy, cz = geo.z - bcz;   // plain (inside-cell test has no NEAREST)
               double wx = cx, wy = cy, wz = cz;
@@ -1814,19 +1828,68 @@ __global__ __launch_bounds__(MODE == 1 ? GW3_TBLOCK : (MODE == 2 ? GW2_MAXWAVES 
                 }
               const int mst = (fl >> 2) & 7;
               bool drop = (mst == 7);   // empty
+              // distance of the cell's CENTRE to the box, per axis (negative: inside)
+              const double tx = fabs(wx) - bhx, ty = fabs(wy) - bhy, tz = fabs(wz) - bhz;
               if(PM && !drop)
                 {
                   // (i) nothing inside the cell can be within the cut of any target
-                  double q0 = fmax(0.0, fabs(wx) - bhx - half), q1 = fmax(0.0, fabs(wy) - bhy - half),
-                         q2 = fmax(0.0, fabs(wz) - bhz - half);
+                  double q0 = fmax(0.0, tx - half), q1 = fmax(0.0, ty - half), q2 = fmax(0.0, tz - half);
                   if(q0 * q0 + q1 * q1 + q2 * q2 >= wp.reach2)
                     drop = true;
                 }
+              // `sure`: the node is opened whatever its moments say, so they are not fetched.
+              // Every species with mass has its centre of mass inside the cell, so along each axis its distance to the box is at
+              // most h = max(0, t + half) -- with nearest images too: |nearest(x)| <= |x + k L| for every k, so the image of
+              // (cell centre + offset) is no farther than the image of the centre plus the offset.  Hence r2g <= r2hi = sum h^2
+              // for every species with mass, and r2min, the smallest r2g over ALL species (the junk centre of a massless one can
+              // only lower it), is at most r2hi: an opening criterion that holds with r2hi in place of r2min holds below.
+              // Rounding: the STORED centre of mass is fl(sum m x / sum m) over at most 8 terms per tree level and may leave the
+              // cell by a few hundred ulp of the largest coordinate, and nearest_abs() rounds a few times more: head_eps
+              // (2^-40 x the largest coordinate magnitude of the domain, 2^13 ulp) is added to the half side and covers both,
+              // so that the computed r2min exceeds the computed r2hi by at most the ~8 roundings of the two sums of squares
+              // (2^-50 relative).  mass_lo is the fp64 sum of the species masses in the walk's own order, rounded TOWARD ZERO to
+              // float: mass_lo <= summass exactly.  What remains is the rounding of the three or four products on either side
+              // of the criterion (2^-51 relative): the factor 1 + 2^-20 covers all of it a billion times over and costs
+              // nothing measurable in how often the shortcut fires.
+              // Test (ii) needs t > rcut + half on some axis; such a lane is not `sure` and runs the code below as before.  (At
+              // the default reach, reach2 <= rcut2, (ii) can never fire for a node that passed (i): t - half > rcut on one axis
+              // alone gives q^2 > rcut^2 >= reach2.  It stays for walk_exact_reach and wider reaches.)
+              bool sure = false;
+              // the axis part of (ii), taken here so that the distances need not stay in registers across the moments
+              bool far = false;
+              if(PM && !drop)
+                {
+                  const double eff = wp.rcut + half;
+                  far = tx > eff || ty > eff || tz > eff;
+                }
               if(!drop)
                 {
-                  first = tv.first[my];
-                  count = tv.count[my];
-                  unsigned massmask = 0;
+                  if(hd)
+                    {
+                      first = head.y;
+                      count = head.z;
+                      const double mass_lo = (double)__int_as_float(head.w);
+                      const double he = half + tv.head_eps;
+                      const double h0 = fmax(0.0, tx + he), h1 = fmax(0.0, ty + he), h2 = fmax(0.0, tz + he);
+                      const double r2hi = (h0 * h0 + h1 * h1 + h2 * h2) * (1.0 + 9.5367431640625e-07);   // 1 + 2^-20
+                      if(wp.use_theta)
+                        sure = len * len > r2hi * wp.theta2;
+                      else
+                        sure = mass_lo * len * len > r2hi * r2hi * aold_min;
+                      sure = sure && mass_lo > 0.0 && !(fl & FLAG_PSEUDO);
+                      sure = sure && !far;
+                      hstat += sure ? 0x10001u : 1u;   // bits 0-15 nodes within reach, 16-31 of them without their moments
+                    }
+                  else
+                    {
+                      first = tv.first[my];
+                      count = tv.count[my];
+                    }
+                }
+              bool open = sure;
+              unsigned massmask = 0;
+              if(!drop && !sure)
+                {
                   double r2min = BIG, r2far = 0, summass = 0;   // r2far: the largest of the species' distances, each to the nearest point of the box
 #pragma unroll
                   for(int g = 0; g < NG; g++)
@@ -1847,15 +1910,10 @@ __global__ __launch_bounds__(MODE == 1 ? GW3_TBLOCK : (MODE == 2 ? GW2_MAXWAVES 
                       r2far = r2g > r2far ? r2g : r2far;
                     }
                   // (ii) the reference's own cut (forcetree.c:1828-1862) holds for every target
-                  if(PM && r2min > wp.rcut2)
-                    {
-                      double eff = wp.rcut + half;
-                      if(fabs(wx) - bhx > eff || fabs(wy) - bhy > eff || fabs(wz) - bhz > eff)
-                        drop = true;
-                    }
+                  if(PM && r2min > wp.rcut2 && far)
+                    drop = true;
                   if(!drop)
                     {
-                      bool open;
                       if(wp.use_theta)
                         open = len * len > r2min * wp.theta2;
                       else
@@ -1880,23 +1938,26 @@ __global__ __launch_bounds__(MODE == 1 ? GW3_TBLOCK : (MODE == 2 ? GW2_MAXWAVES 
                         }
                       else if(!open && hT_min < hs_node && r2far < hs_node * hs_node && ((fl >> 5) & 1))
                         open = true;
-                      // A top leaf whose particles were not imported (FLAG_PSEUDO: global monopoles, no children) cannot be opened.
-                      // The import decision covers every node a TARGET may open under the criterion in force at the decomposition; the
-                      // box of a group that spans several top leaves can come closer to a node than any of their boxes, and a host may
-                      // have changed the criterion since.  Such a node is used as a monopole (it used to drop out of the force) and
-                      // counted: ngravs_walk_unopened().
-                      if(open && (fl & FLAG_PSEUDO))
-                        {
-                          open = false;
-                          pseudo_hit = true;
-                        }
-                      if(open)
-                        dec = ((fl & FLAG_BUCKET) || (count <= wp.nleaf && !(fl & FLAG_PARTIAL))) ? 3 : 2;
-                      else
-                        dec = 1;
-                      static_assert(FLAG_PARTIAL << 1 == 1 << FLAG_SPECIES_SHIFT, "one shift takes both out of the flags word");
-                      info = open ? (NG > 1 ? ((unsigned)fl >> (FLAG_SPECIES_SHIFT - 1)) & 0x1ffffu : 0u) : massmask;
                     }
+                }
+              if(!drop)
+                {
+                  // A top leaf whose particles were not imported (FLAG_PSEUDO: global monopoles, no children) cannot be opened.
+                  // The import decision covers every node a TARGET may open under the criterion in force at the decomposition; the
+                  // box of a group that spans several top leaves can come closer to a node than any of their boxes, and a host may
+                  // have changed the criterion since.  Such a node is used as a monopole (it used to drop out of the force) and
+                  // counted: ngravs_walk_unopened().  (Never a `sure` lane: the monopoles need the node's mass mask.)
+                  if(open && (fl & FLAG_PSEUDO))
+                    {
+                      open = false;
+                      pseudo_hit = true;
+                    }
+                  if(open)
+                    dec = ((fl & FLAG_BUCKET) || (count <= wp.nleaf && !(fl & FLAG_PARTIAL))) ? 3 : 2;
+                  else
+                    dec = 1;
+                  static_assert(FLAG_PARTIAL << 1 == 1 << FLAG_SPECIES_SHIFT, "one shift takes both out of the flags word");
+                  info = open ? (NG > 1 ? ((unsigned)fl >> (FLAG_SPECIES_SHIFT - 1)) & 0x1ffffu : 0u) : massmask;
                 }
             }
           {
@@ -2062,6 +2123,27 @@ __global__ __launch_bounds__(MODE == 1 ? GW3_TBLOCK : (MODE == 2 ? GW2_MAXWAVES 
             break;
           wave_sync();
         }
+      if(PM && MODE != 2 && tv.head != nullptr)
+        {
+          unsigned long long hs = ((unsigned long long)(hstat >> 16) << 32) | (unsigned long long)(hstat & 0xffffu);
+          for(int off = 32; off > 0; off >>= 1)
+            hs += __shfl_xor(hs, off);
+          if constexpr(MODE == 1)
+            {
+              // one wave of the traversal kernel walks one unit: one pair of atomics per unit, and nothing waits for them
+              unsigned long long *hd64 = reinterpret_cast<unsigned long long *>(counter + 26);
+              if(lane == 0 && hs != 0ull)
+                {
+                  atomicAdd(&hd64[0], hs >> 32);
+                  atomicAdd(&hd64[1], hs & 0xffffffffull);
+                }
+            }
+          else
+            {
+              acc_hd[0] += hs >> 32;
+              acc_hd[1] += hs & 0xffffffffull;
+            }
+        }
       if constexpr(MODE == 1)
         {
 #pragma unroll
@@ -2132,6 +2214,12 @@ __global__ __launch_bounds__(MODE == 1 ? GW3_TBLOCK : (MODE == 2 ? GW2_MAXWAVES 
       for(int q = 0; q < 4; q++)
         if(acc_st[q])
           atomicAdd(&st64[q], acc_st[q]);
+    }
+  if(MODE == 0 && lane == 0 && acc_hd[1] != 0ull)
+    {
+      unsigned long long *hd64 = reinterpret_cast<unsigned long long *>(counter + 26);
+      atomicAdd(&hd64[0], acc_hd[0]);
+      atomicAdd(&hd64[1], acc_hd[1]);
     }
 }
 
@@ -2420,6 +2508,9 @@ TreeView tree_view(ngravs_ctx *c)
   tv.flags = c->n_flags.p;
   tv.geo = c->n_geo.p;
   tv.mom = c->n_mom.p;
+  tv.head = (c->head_valid && c->tune.walk_head) ? c->n_head.p : nullptr;
+  // (every particle lies in the root cell, dom[3..5] its centre and dom[6] its side)
+  tv.head_eps = 9.094947017729282e-13 * (fmax(fabs(c->dom[3]), fmax(fabs(c->dom[4]), fabs(c->dom[5]))) + c->dom[6]);   // 2^-40
   tv.npart = (cfg_has_bam(c->cfg) || cfg_has_user(c->cfg)) ? c->n_npart.p : nullptr;
   tv.nnodes = (int)c->nnodes;
   tv.ltab = c->lvl_table.p;
@@ -3207,6 +3298,7 @@ int walk_complete(ngravs_ctx *c)
   WalkParams wp;
   make_walk_params(c, &wp);   // (what walk_enqueue launched with: nothing it depends on has changed)
   c->walk_unopened = 0;
+  c->walk_moment_skips = c->walk_head_survivors = 0;
   if(strict && c->top.on)
     {
       int flag = 0;
@@ -3275,6 +3367,10 @@ int walk_complete(ngravs_ctx *c)
         int unop = 0;
         HIP_TRY(c, hipMemcpy(&unop, c->walk_counters.p + 4, sizeof(int), hipMemcpyDeviceToHost));
         c->walk_unopened = unop;
+        unsigned long long hd64[2] = {0, 0};
+        HIP_TRY(c, hipMemcpy(hd64, c->walk_counters.p + 26, sizeof(hd64), hipMemcpyDeviceToHost));
+        c->walk_moment_skips = (long long)hd64[0];
+        c->walk_head_survivors = (long long)hd64[1];
       }
       if(flag)
         {

@@ -345,6 +345,12 @@ int ngravs_get_stats(ngravs_ctx *ctx, ngravs_stats_t *out);
  * task).  The reference walk (NGRAVS_WALK_STRICT) does not substitute: ngravs_gravity_tree() returns NGRAVS_ERR_STATE instead.
  * Replaces nothing in the reference: its export / import loop (gravtree.c:112-285) follows the walk wherever it goes. */
 int ngravs_walk_unopened(ngravs_ctx *ctx, int64_t *count);
+/* Group walk (NGRAVS_WALK_GROUP), diagnostics of the last walk's traversal: how many tested nodes were opened from the node head
+ * alone, their multipole moments never fetched (*skips), out of how many nodes within reach of their group of targets
+ * (*within_reach, may be NULL).  Both 0 when the walk ran without the head: tuning "walk_head" 0, a refit tree, a multi-task tree,
+ * a tree-only walk.
+ * Replaces nothing in the reference. */
+int ngravs_walk_moment_skips(ngravs_ctx *ctx, int64_t *skips, int64_t *within_reach);
 /* DomainCorner[3], DomainCenter[3], DomainLen, DomainFac (domain.c:916-923) -> out[8] */
 int ngravs_get_domain(ngravs_ctx *ctx, double out[8]);
 /* 18-bit reference Peano-Hilbert keys in original particle order (domain.c:938-944). */
