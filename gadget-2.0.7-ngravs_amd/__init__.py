@@ -26,7 +26,7 @@ _LIB = None
 EXPORTS = [
     "ngravs_abi_version", "ngravs_build_info", "ngravs_config_default", "ngravs_create", "ngravs_create_with_laws", "ngravs_destroy",
     "ngravs_last_walk_kernel", "ngravs_last_pm_cus", "ngravs_cu_probe", "ngravs_shortrange_table_with_laws", "ngravs_user_table_eval",
-    "ngravs_create_with_lattice", "ngravs_user_lattice_table",
+    "ngravs_create_with_lattice", "ngravs_user_lattice_table", "ngravs_create_with_potentials",
     "ngravs_set_fatal_handler", "ngravs_set_opening", "ngravs_set_walk_mode", "ngravs_set_softening", "ngravs_dd_record_bytes", "ngravs_get_config", "ngravs_set_tuning",
     "ngravs_memcpy", "ngravs_device_alloc", "ngravs_device_free",
     "ngravs_set_particles",
@@ -137,6 +137,7 @@ def lib():
         L.ngravs_dd_get_ids.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.ngravs_create_with_lattice.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
         L.ngravs_user_lattice_table.argtypes = [abi.LATTICE_FN, C.c_double, C.c_void_p]
+        L.ngravs_create_with_potentials.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
         L.ngravs_sph_density.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ngravs_sph_kernel.argtypes = [C.c_double, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         L.ngravs_sph_hydro.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -214,8 +215,9 @@ def shortrange_table_with_laws(cfg, user_fns):
 
 def user_table_eval(kind, fn, r, r_lo=0.0, r_hi=0.0, h=0.0):
     """what the kernels evaluate for a user law, built and evaluated on the host (no GPU): kind USER_ACCEL -> accel(1,1,r^2,r,1)
-    from the table over [r_lo, r_hi]; USER_SPLINE -> spline(1,1,h,r,1) from the table of softening h.  Returns (values, the
-    largest relative deviation the fit saw at its check points)."""
+    from the table over [r_lo, r_hi]; USER_SPLINE -> spline(1,1,h,r,1) from the table of softening h; USER_POT -> pot(1,1,0,r,1)
+    and USER_POT_SPLINE -> pot_spline(1,1,h,r,1) of a user_potentials entry in the same way.  Returns (values, the largest
+    relative deviation the fit saw at its check points)."""
     arr, _, keep = abi.user_registry([(kind, fn)])
     r = np.ascontiguousarray(r, dtype=np.float64)
     out = np.zeros_like(r)
@@ -429,18 +431,23 @@ def sph_density_update(sums, hsml, left, right, rounds, des_num_ngb, max_num_ngb
 class Engine:
     """One task's gravity state: the replacement for the reference's globals on this path."""
 
-    def __init__(self, cfg, user_fns=None, user_lattice=None):
+    def __init__(self, cfg, user_fns=None, user_lattice=None, user_potentials=None):
         """user_fns: [(abi.USER_ACCEL | USER_SPLINE | USER_GREENS | USER_NORMED, f), ...], f(target, source, r2_or_h_or_k2,
         r_or_k, N) -> float; entry k is wired as abi.LAW_USER0 + k / abi.SPLINE_USER0 + k.  user_lattice: [(target, source,
         fn), ...], the lattice correction of a pair wired with a user accel id in a periodic run (the reference's
         LatticeForce[target][source]): fn is an abi.LATTICE_FN (e.g. from the model's shared library) or a Python callable
-        fn(i, j, k, x, force), which is slow here -- 65^3 = 274 625 calls, serialised by the GIL.  The callbacks are kept alive
-        with the engine (the library calls them when it (re)builds its tables)."""
+        fn(i, j, k, x, force), which is slow here -- 65^3 = 274 625 calls, serialised by the GIL.  user_potentials: [(target,
+        source, pot, pot_spline, lattice_pot or None, lattice_zero), ...], the potential companions of a pair (the reference's
+        PotentialFxns, PotentialSplines, LatticePotential, LatticeZero [target][source]) for compute_potential() and
+        potential_targets(): pot and pot_spline as the laws of user_fns, lattice_pot an abi.LATTICE_POT_FN or a Python callable
+        fn(x) -> float.  The callbacks are kept alive with the engine (the library calls them when it (re)builds its tables)."""
         self.cfg = cfg
         self._h = C.c_void_p()
         self._user_arr, nfns, self._user_keep = abi.user_registry(user_fns)
         self._lat_arr, nlat, self._lat_keep = abi.lattice_registry(user_lattice)
-        rc = lib().ngravs_create_with_lattice(C.byref(cfg), self._user_arr, nfns, self._lat_arr, nlat, C.byref(self._h))
+        self._pot_arr, npot, self._pot_keep = abi.potential_registry(user_potentials)
+        rc = lib().ngravs_create_with_potentials(C.byref(cfg), self._user_arr, nfns, self._lat_arr, nlat, self._pot_arr, npot,
+                                                 C.byref(self._h))
         if rc != 0:
             msg = lib().ngravs_last_error(None)
             self.status = rc

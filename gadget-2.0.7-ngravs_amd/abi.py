@@ -21,6 +21,7 @@ LAW_USER0 = 64
 SPLINE_USER0 = 64
 MAX_USER_FNS = 8
 USER_ACCEL, USER_SPLINE, USER_GREENS, USER_NORMED = range(4)
+USER_POT, USER_POT_SPLINE = 4, 5   # user_table_eval only: potentials travel in user_potentials (ngravs_create_with_potentials)
 KERNEL_NONE, KERNEL_STRICT, KERNEL_STRICT_USER, KERNEL_GROUP, KERNEL_GROUP_USER, KERNEL_STRICT_ADAPTIVE, KERNEL_GROUP_ADAPTIVE = range(7)
 # the reference's `gravity` type (allvars.h:134): double f(double target, double source, double r2_or_h_or_k2, double r_or_k, long N)
 GravityFn = C.CFUNCTYPE(C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_long)
@@ -91,6 +92,31 @@ def lattice_registry(user_lattice):
         keep.append(w)
         arr[k].target, arr[k].source, arr[k].fn = int(t), int(s), w
     return arr, len(user_lattice), keep
+
+
+# the model's potential companions (ngravs_create_with_potentials): the reference's latpot, double fn(double x[3])
+LATTICE_POT_FN = C.CFUNCTYPE(C.c_double, C.POINTER(C.c_double))
+
+
+class UserPotential(C.Structure):
+    _fields_ = [("target", C.c_int32), ("source", C.c_int32), ("pot", GravityFn), ("pot_spline", GravityFn),
+                ("lattice_pot", LATTICE_POT_FN), ("lattice_zero", C.c_double)]
+
+
+def potential_registry(user_potentials):
+    """[(target, source, pot, pot_spline, lattice_pot or None, lattice_zero), ...] -> (ctypes array of UserPotential, its length,
+    the callback wrappers, which must outlive every use of the array); None for pot or pot_spline is NULL, which the library refuses"""
+    user_potentials = list(user_potentials or [])
+    arr = (UserPotential * max(len(user_potentials), 1))()
+    keep = []
+    for k, (t, s, pot, spl, lat, zero) in enumerate(user_potentials):
+        wp = GravityFn() if pot is None else (pot if isinstance(pot, GravityFn) else GravityFn(pot))
+        ws = GravityFn() if spl is None else (spl if isinstance(spl, GravityFn) else GravityFn(spl))
+        wl = LATTICE_POT_FN() if lat is None else (lat if isinstance(lat, LATTICE_POT_FN) else LATTICE_POT_FN(lat))
+        keep += [wp, ws, wl]
+        arr[k].target, arr[k].source, arr[k].pot, arr[k].pot_spline, arr[k].lattice_pot = int(t), int(s), wp, ws, wl
+        arr[k].lattice_zero = float(zero)
+    return arr, len(user_potentials), keep
 
 
 def user_registry(user_fns):

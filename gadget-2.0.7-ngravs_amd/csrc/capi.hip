@@ -177,6 +177,13 @@ extern "C" int ngravs_create_with_laws(const ngravs_config_t *cfg, const ngravs_
 extern "C" int ngravs_create_with_lattice(const ngravs_config_t *cfg, const ngravs_user_fn_t *fns, int nfns,
                                           const ngravs_user_lattice_t *lat, int nlat, ngravs_ctx **out)
 {
+  return ngravs_create_with_potentials(cfg, fns, nfns, lat, nlat, nullptr, 0, out);
+}
+
+extern "C" int ngravs_create_with_potentials(const ngravs_config_t *cfg, const ngravs_user_fn_t *fns, int nfns,
+                                             const ngravs_user_lattice_t *lat, int nlat, const ngravs_user_potential_t *pots, int npot,
+                                             ngravs_ctx **out)
+{
   if(!cfg || !out)
     return NGRAVS_ERR_ARG;
   *out = nullptr;
@@ -184,6 +191,8 @@ extern "C" int ngravs_create_with_lattice(const ngravs_config_t *cfg, const ngra
   int rc = check_config(cfg, why);
   if(rc == NGRAVS_OK)
     rc = user_check_config(cfg, fns, nfns, lat, nlat, why);
+  if(rc == NGRAVS_OK)
+    rc = user_check_potentials(cfg, pots, npot, why);
   if(rc != NGRAVS_OK)
     {
       ngravs_report(nullptr, rc, why);
@@ -201,6 +210,8 @@ extern "C" int ngravs_create_with_lattice(const ngravs_config_t *cfg, const ngra
   c->cfg = *cfg;
   c->user_fns.assign(fns, fns + nfns);
   c->user_lat.assign(lat, lat + nlat);
+  c->user_pot.assign(pots, pots + npot);
+  user_pot_registry(c);
   memset(&c->stats, 0, sizeof(c->stats));
   if(hipSetDevice(cfg->device) != hipSuccess || hipStreamCreate(&c->stream) != hipSuccess ||
      hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess ||
@@ -273,6 +284,7 @@ extern "C" void ngravs_destroy(ngravs_ctx *c)
   c->n_mom.release();
   c->n_npart.release();
   c->user_tab.release();
+  c->upot_tab.release();
   c->user_green.release();
   c->scan_out.release();
   c->tb_count.release();
@@ -2519,6 +2531,14 @@ static int potential_refusals(ngravs_ctx *c, const Refuse &refuse)
       {
         const int law = c->cfg.law_accel[a][b], spl = c->cfg.law_spline[a][b];
         const std::string at = "[" + std::to_string(a) + "][" + std::to_string(b) + "]";
+        if(user_pot_entry(c, a, b))
+          {
+            // the model's own companions serve any law a table linear in the source mass can carry
+            if((law >= NGRAVS_LAW_BAMBAM && law < NGRAVS_LAW_USER0) || (spl >= NGRAVS_SPLINE_BAMBAM && spl < NGRAVS_SPLINE_USER0))
+              return refuse(NGRAVS_ERR_ARG, "law_accel / law_spline" + at + " is a BAM law: its potential depends on the target mass and on N, "
+                                            "which a node's monopole cannot carry; BAM potentials are not served");
+            continue;
+          }
         if(law != NGRAVS_LAW_NONE && law != NGRAVS_LAW_NEWTON && law != NGRAVS_LAW_NEG_NEWTON)
           return refuse(NGRAVS_ERR_ARG, "law_accel" + at + " has no wired potential companion (only newtonian and neg_newtonian have; Yukawa, "
                                         "coloyuk, BAM and user laws are not served)");
@@ -2587,7 +2607,7 @@ extern "C" int ngravs_potential_targets(ngravs_ctx *c, const ngravs_grav_targets
   if((rc = grav_targets_stage(c, refuse, t, nt, &far)))
     return rc;
   const bool empty = c->n_local == 0 || c->nnodes <= 0;   // nothing to walk
-  if(!empty && (rc = potential_targets_run(c, nt)))
+  if(!empty && (rc = potential_targets_run(c, nt, far)))
     return rc;
   if((rc = col_deliver_or_zeros(c, empty ? nullptr : c->gt_acc.p, sizeof(double) * (size_t)nt, pot, t->on_device)))
     return rc;

@@ -128,6 +128,15 @@ __host__ __device__ inline double ul_spline(const UserTabs &u, int k, double h, 
   return ul_poly(u.spl + ((size_t)(k * u.nh + i) * u.Ss + j) * UL_NC, 2 * (s - j) - 1);
 }
 
+// The model's potential companions (ngravs_create_with_potentials) as the potential walk reads them: the tables of UserTabs with
+// p(r) = r pot(1, 1, 0, r, 1) in the place of g(r) and pot_spline(1, 1, h, u h, 1) in the place of the force spline, one table per
+// distinct function; kp / ks [target][source]: the table of the pair's pot / pot_spline, -1 for a pair without an entry (cN / cS)
+struct PotUser
+{
+  UserTabs ut;
+  int kp[NG_MAX][NG_MAX], ks[NG_MAX][NG_MAX];
+};
+
 // constants every kernel needs, passed by value (fits kernarg / SGPRs)
 struct WalkParams
 {
@@ -432,7 +441,15 @@ struct ngravs_ctx
   bool pot_table_ready = false;
   DevBuf<double> pot_lat;     // [ng][ng][65^3]: sign(law) ewald_psi / BoxSize on the octant grid of `lat` (periodic tree-only)
   bool pot_lat_ready = false;
-  DevBuf<double> r_pot;       // [n], Peano order: the walk's sum, then the finished potential
+  // the model's potential companions (ngravs_create_with_potentials): the entries, their distinct pot / pot_spline functions as a
+  // registry of kinds NGRAVS_USER_POT / NGRAVS_USER_POT_SPLINE, and the tables of that registry (user_pot_tables_ensure)
+  std::vector<ngravs_user_potential_t> user_pot;
+  std::vector<ngravs_user_fn_t> upot_fns;
+  DevBuf<double> upot_tab;
+  UserTabs upot_ut = {};
+  bool upot_ready = false;
+  double upot_soft[NGRAVS_NTYPES] = {0, 0, 0, 0, 0, 0};
+  DevBuf<double> r_pot;      // [n], Peano order: the walk's sum, then the finished potential
   // pm_phi holds the potentials of the mesh of the last ngravs_compute_potential, at the positions of that call; cleared by the
   // next deposit and by every hand-over of particles
   bool pot_mesh_valid = false;
@@ -524,6 +541,15 @@ void ngravs_report(ngravs_ctx *ctx, int code, const std::string &msg);
 int user_tables_ensure(ngravs_ctx *c, double r_need);
 int user_green_ensure(ngravs_ctx *c);   // PM: the G(k2) tables of the user greens ids   // (re)build the tables if r_need or the softenings are not covered
 double user_normed(const ngravs_user_fn_t *fns, int nfns, int law, double k2);
+// the potential entries of ngravs_create_with_potentials: the creation checks; the entry of pair (a, b) (nullptr: none); the
+// registry of distinct functions and the pair -> table maps; the tables for walks that reach r_need; one lattice table
+// out[65^3] = fn / box, the origin zero / box, sampled on host threads
+int user_check_potentials(const ngravs_config_t *cfg, const ngravs_user_potential_t *pots, int npot, std::string &why);
+const ngravs_user_potential_t *user_pot_entry(const ngravs_ctx *c, int a, int b);
+void user_pot_registry(ngravs_ctx *c);
+void user_pot_maps(const ngravs_ctx *c, PotUser *pu);
+int user_pot_tables_ensure(ngravs_ctx *c, double r_need);
+int user_pot_lattice_tabulate(ngravs_lattice_pot_fn fn, double zero, double box, double *out, std::string &why);
 // ---- kernels_walk.hip
 void make_walk_params(const ngravs_ctx *c, WalkParams *wp);
 int walk_run(ngravs_ctx *c);        // walk_enqueue + walk_complete
@@ -554,7 +580,8 @@ int grav_targets_order(ngravs_ctx *c, long long nt, const unsigned int **ord);
 // (may be null) gets the interaction counts in caller order.
 int potential_run(ngravs_ctx *c, const ngravs_time_params_t *par, double *d_out, int *d_nint);
 // the walk x G (+ the mesh part with a mesh) at the targets of gt_in / gt_type -> gt_acc[nt], gt_nint[nt], caller order
-int potential_targets_run(ngravs_ctx *c, long long nt);
+// far: the largest distance of a target from the domain's centre (grav_targets_check), for the reach of the model's potential tables
+int potential_targets_run(ngravs_ctx *c, long long nt, double far);
 int potential_lattice_ensure(ngravs_ctx *c);
 // ---- kernels_eval.hip
 int eval_ring_slots(const WalkParams &wp, bool yuk, int waves);

@@ -11,6 +11,7 @@
 // the pseudo-node flag) with the potential walk's two differences: a periodic tree-only run adds the lattice term in the same
 // visit (no second walk), and the short-range walk prunes by the eff_dist box alone -- here with the table's reach.  Wired companions: newtonian_pot,
 // neg_newtonian_pot, plummer_pot, neg_plummer_pot (ngravs.c:368-489), as the coefficients cN / cS of WalkParams (+1, -1, 0).
+// The USR variants also read the model's own companions (ngravs_create_with_potentials) from the tables user_laws.cpp builds.
 #include "engine.hpp"
 #include "walk_device.hpp"
 #include "columns.hpp"
@@ -85,13 +86,22 @@ __device__ __forceinline__ double lat_pot_lookup(const double *__restrict__ a, d
          a[o + si + sj + 1] * f8;
 }
 
+// The last kernel argument: the model's potential tables (USR), or a word nobody reads -- the USR = false kernels are the code
+// they were before there were such tables
+struct NoPotUser
+{
+  int unused;
+};
+template <bool USR> using PotUserArg = std::conditional_t<USR, PotUser, NoPotUser>;
+
 // One lane's potential walk for a target given by value: the one body of k_potential_walk (own rows) and k_potential_targets
 // (records handed in).  table: PM the long-range potential E [tg][sg][NTAB], LATT the lattice potential [tg][sg][E1^3].
-template <int NG, bool PM, bool LATT>
+// USR: a pair with an entry of ngravs_create_with_potentials evaluates the entry's two tables (pu), every other pair cN / cS.
+template <int NG, bool PM, bool LATT, bool USR>
 __device__ __forceinline__ void potential_walk_lane(const TreeView &tv, const double4 *__restrict__ s_pm, const unsigned char *__restrict__ s_type,
                                                     const double *__restrict__ table, const WalkParams &wp, const double utorwpi,
                                                     const double reach, const bool valid, const StrictTarget &T, int *sn, int *ss, int *__restrict__ err_flag,
-                                                    double &pot_out, int &nint_out)
+                                                    const PotUserArg<USR> &pu, double &pot_out, int &nint_out)
 {
   const double px = T.x, py = T.y, pz = T.z, aold = T.aold, hT = T.h;
   const int tg = T.tg;
@@ -100,6 +110,39 @@ __device__ __forceinline__ void potential_walk_lane(const TreeView &tv, const do
   const int NO_SKIP = 0x7fffffff;
   int lane_skip = valid ? NO_SKIP : -1;   // (kernels_walk.hip, strict_walk_lane)
   int sp = -1;
+
+  // USR: the tables of this lane's target species against every source species, one byte each (table + 1; 0: no entry).  The
+  // source species of a visit is the same for the whole wave, the target's is the lane's: the piece of the table a lane reads
+  // depends on its r anyway, so the coefficients come through vector loads
+  unsigned kpk = 0, ksk = 0;
+  if constexpr(USR)
+    {
+#pragma unroll
+      for(int g = 0; g < NG; g++)
+        {
+          kpk |= (unsigned)(pu.kp[tg][g] + 1) << (8 * g);
+          ksk |= (unsigned)(pu.ks[tg][g] + 1) << (8 * g);
+        }
+    }
+  // PotentialFxns / PotentialSplines of the pair (tg, g) for a source of mass m
+  auto p_far = [&](int g, double m, double r) -> double {
+    if constexpr(USR)
+      {
+        const int k = (int)((kpk >> (8 * g)) & 0xff) - 1;
+        if(k >= 0)
+          return m * (ul_g(pu.ut, k, r) / r);
+      }
+    return wp.cN[tg][g] * (m / r);
+  };
+  auto p_near = [&](int g, double m, double h, double r) -> double {
+    if constexpr(USR)
+      {
+        const int k = (int)((ksk >> (8 * g)) & 0xff) - 1;
+        if(k >= 0)
+          return m * ul_spline(pu.ut, k, h, r);
+      }
+    return wp.cS[tg][g] * plummer_pot(m, h, r);
+  };
 
   // one source (particle or one species of a node): forcetree.c:2725-2768 / :3104ff
   auto interact = [&](int g, double dx, double dy, double dz, double r2, double m, double h) -> bool {
@@ -112,16 +155,16 @@ __device__ __forceinline__ void potential_walk_lane(const TreeView &tv, const do
         // the mesh's share of this pair, removed inside h too: the mesh holds it for close pairs and for the particle itself
         const double lr = m * utorwpi * table[((size_t)tg * NG + g) * NTAB + tab];
         if(r >= h)
-          pot -= wp.cN[tg][g] * (m / r) - lr;
+          pot -= p_far(g, m, r) - lr;
         else
-          pot += wp.cS[tg][g] * plummer_pot(m, h, r) + lr;
+          pot += p_near(g, m, h, r) + lr;
       }
     else
       {
         if(r >= h)
-          pot -= wp.cN[tg][g] * (m / r);
+          pot -= p_far(g, m, r);
         else
-          pot += wp.cS[tg][g] * plummer_pot(m, h, r);
+          pot += p_near(g, m, h, r);
         if(LATT)
           pot += m * lat_pot_lookup(table + ((size_t)tg * NG + g) * POT_LAT_SZ, wp.fac_intp, dx, dy, dz);   // forcetree.c:2737
       }
@@ -305,11 +348,11 @@ __device__ __forceinline__ void potential_walk_lane(const TreeView &tv, const do
 }
 
 // targets: ALL own rows [0, n) in Peano order, whatever their active flags, 64 consecutive rows per wave
-template <int NG, bool PM, bool LATT>
+template <int NG, bool PM, bool LATT, bool USR>
 __global__ __launch_bounds__(256) void k_potential_walk(TreeView tv, const double4 *__restrict__ s_pm, const unsigned char *__restrict__ s_type,
                                                         const double *__restrict__ s_oldacc, const double *__restrict__ table, WalkParams wp,
                                                         double utorwpi, double reach, long long n, double *__restrict__ r_pot, int *__restrict__ r_nint,
-                                                        int *__restrict__ err_flag)
+                                                        int *__restrict__ err_flag, PotUserArg<USR> pu)
 {
   __shared__ int st_node[4][MAX_LEVELS + 2], st_slot[4][MAX_LEVELS + 2];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -333,7 +376,7 @@ __global__ __launch_bounds__(256) void k_potential_walk(TreeView tv, const doubl
     }
   double pot;
   int nint;
-  potential_walk_lane<NG, PM, LATT>(tv, s_pm, s_type, table, wp, utorwpi, reach, valid, T, st_node[wave], st_slot[wave], err_flag, pot, nint);
+  potential_walk_lane<NG, PM, LATT, USR>(tv, s_pm, s_type, table, wp, utorwpi, reach, valid, T, st_node[wave], st_slot[wave], err_flag, pu, pot, nint);
   if(valid)
     {
       r_pot[ti] = pot;
@@ -342,13 +385,14 @@ __global__ __launch_bounds__(256) void k_potential_walk(TreeView tv, const doubl
 }
 
 // targets: records handed in (ngravs_potential_targets), the columns of k_walk_targets; the sum x G goes to the caller's index
-template <int NG, bool PM, bool LATT>
+template <int NG, bool PM, bool LATT, bool USR>
 __global__ __launch_bounds__(256) void k_potential_targets(TreeView tv, const double4 *__restrict__ s_pm, const unsigned char *__restrict__ s_type,
                                                            const double *__restrict__ table, WalkParams wp, double utorwpi, double reach,
                                                            const double *__restrict__ t_pos, const double *__restrict__ t_oldacc,
                                                            const double *__restrict__ t_mass, const int *__restrict__ t_type,
                                                            const unsigned int *__restrict__ ord, long long nt, double G,
-                                                           double *__restrict__ o_pot, int *__restrict__ o_nint, int *__restrict__ err_flag)
+                                                           double *__restrict__ o_pot, int *__restrict__ o_nint, int *__restrict__ err_flag,
+                                                           PotUserArg<USR> pu)
 {
   __shared__ int st_node[4][MAX_LEVELS + 2], st_slot[4][MAX_LEVELS + 2];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -373,7 +417,7 @@ __global__ __launch_bounds__(256) void k_potential_targets(TreeView tv, const do
     }
   double pot;
   int nint;
-  potential_walk_lane<NG, PM, LATT>(tv, s_pm, s_type, table, wp, utorwpi, reach, valid, T, st_node[wave], st_slot[wave], err_flag, pot, nint);
+  potential_walk_lane<NG, PM, LATT, USR>(tv, s_pm, s_type, table, wp, utorwpi, reach, valid, T, st_node[wave], st_slot[wave], err_flag, pu, pot, nint);
   if(valid)
     {
       o_pot[me] = pot * G;
@@ -391,8 +435,18 @@ struct PotTail
   double lz[NG_MAX];    // LatticeZero[g][g] (Omega0 3 H^2 / (8 pi G))^(1/3), 0 unless comoving and periodic
   double G, rfac;       // rfac: -0.5 Omega0 H^2 (comoving, not periodic) or -0.5 OmegaLambda H^2 (not comoving), else 0
 };
+// USR: the self term of a type whose species pair [g][g] has an entry is - m pot_spline(1, 1, h, 0, 1) read from the entry's
+// table with the walk's own operations (ks: the table per type, -1 without an entry), so that it takes out what the walk added
+// for the row itself to the last bit; lz then holds the entries' LatticeZero
+struct PotSelf
+{
+  UserTabs ut;
+  int ks[NGRAVS_NTYPES];
+};
+template <bool USR> using PotSelfArg = std::conditional_t<USR, PotSelf, NoPotUser>;
+template <bool USR>
 __global__ void k_potential_finish(const double4 *__restrict__ s_pm, const unsigned char *__restrict__ s_type, long long n, PotTail pt,
-                                   const double *__restrict__ mesh, double *__restrict__ r_pot)
+                                   const double *__restrict__ mesh, double *__restrict__ r_pot, PotSelfArg<USR> ps)
 {
   const long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
   if(i >= n)
@@ -401,7 +455,15 @@ __global__ void k_potential_finish(const double4 *__restrict__ s_pm, const unsig
   const int type = s_type[i];
   double pot = r_pot[i];
   const double h_inv = 1 / pt.fsoft[type];
-  pot += p.w * h_inv * 2.8;
+  bool own_table = false;
+  if constexpr(USR)
+    if(ps.ks[type] >= 0)
+      {
+        pot -= p.w * ul_spline(ps.ut, ps.ks[type], pt.fsoft[type], 0.0);
+        own_table = true;
+      }
+  if(!own_table)
+    pot += p.w * h_inv * 2.8;
   const double lz = pt.lz[pt.t2g[type]];
   if(lz != 0)
     pot -= lz * pow(p.w, 2.0 / 3);
@@ -433,14 +495,41 @@ int potential_lattice_ensure(ngravs_ctx *c)
   const int ng = c->cfg.n_gravs, npts = LAT_E1 * LAT_E1 * LAT_E1;
   if(c->pot_lat.ensure((size_t)ng * ng * POT_LAT_SZ))
     return NGRAVS_ERR_NOMEM;
+  std::vector<double> host;   // one table of the model's (ngravs_create_with_potentials), sampled on the host
   for(int k = 0; k < ng * ng; k++)
     {
+      double *dst = c->pot_lat.p + (size_t)k * POT_LAT_SZ;
+      if(const ngravs_user_potential_t *e = user_pot_entry(c, k / ng, k % ng))
+        {
+          // the pair's own LatticePotential and LatticeZero: 65^3 - 1 calls per distinct function and zero
+          int src = -1;
+          for(int q = 0; q < k && src < 0; q++)
+            if(const ngravs_user_potential_t *o = user_pot_entry(c, q / ng, q % ng))
+              if(o->lattice_pot == e->lattice_pot && o->lattice_zero == e->lattice_zero)
+                src = q;
+          if(src >= 0)
+            {
+              HIP_TRY(c, hipMemcpyAsync(dst, c->pot_lat.p + (size_t)src * POT_LAT_SZ, sizeof(double) * POT_LAT_SZ, hipMemcpyDeviceToDevice, c->stream));
+              continue;
+            }
+          std::string why;
+          host.resize(POT_LAT_SZ);
+          if(!e->lattice_pot)   // (refused at creation for a periodic tree-only configuration)
+            return NGRAVS_ERR_WIRING;
+          if(int rc = user_pot_lattice_tabulate(e->lattice_pot, e->lattice_zero, c->cfg.box_size, host.data(), why))
+            {
+              ngravs_report(c, rc, "potential entry [" + std::to_string(k / ng) + "][" + std::to_string(k % ng) + "]: " + why);
+              return rc;
+            }
+          HIP_TRY(c, hipMemcpyAsync(dst, host.data(), sizeof(double) * POT_LAT_SZ, hipMemcpyHostToDevice, c->stream));
+          HIP_TRY(c, hipStreamSynchronize(c->stream));   // (host is reused)
+          continue;
+        }
       const double sign = law_sign(c->cfg.law_accel[k / ng][k % ng]);
       int src = -1;
       for(int q = 0; q < k && src < 0; q++)
-        if(law_sign(c->cfg.law_accel[q / ng][q % ng]) == sign)
+        if(!user_pot_entry(c, q / ng, q % ng) && law_sign(c->cfg.law_accel[q / ng][q % ng]) == sign)
           src = q;
-      double *dst = c->pot_lat.p + (size_t)k * POT_LAT_SZ;
       if(src >= 0)
         HIP_TRY(c, hipMemcpyAsync(dst, c->pot_lat.p + (size_t)src * POT_LAT_SZ, sizeof(double) * POT_LAT_SZ, hipMemcpyDeviceToDevice, c->stream));
       else
@@ -471,8 +560,9 @@ static int potential_table_ensure(ngravs_ctx *c)
   return NGRAVS_OK;
 }
 
-// k_potential_walk / k_potential_targets<NG, PM, LATT>: TreePM, periodic tree-only, tree-only
-template <int NG> using PotRowsNG = Table<Row<NG, 1, 0>, Row<NG, 0, 1>, Row<NG, 0, 0>>;
+// k_potential_walk / k_potential_targets<NG, PM, LATT, USR>: TreePM, periodic tree-only, tree-only; each with the built-in
+// companions alone and with the model's tables
+template <int NG> using PotRowsNG = Table<Row<NG, 1, 0, 0>, Row<NG, 0, 1, 0>, Row<NG, 0, 0, 0>, Row<NG, 1, 0, 1>, Row<NG, 0, 1, 1>, Row<NG, 0, 0, 1>>;
 using PotRows = decltype(PotRowsNG<1>{} + PotRowsNG<2>{} + PotRowsNG<3>{});
 
 struct PotWalk
@@ -480,23 +570,40 @@ struct PotWalk
   WalkParams wp;
   double utorwpi, reach;   // 1 / (2 pi Asmth); NTAB / asmthfac = 6 Asmth: tab < NTAB inside it
   const double *table;
-  int key[3];
+  int key[4];
   int *flag;
+  PotUser pu;              // USR (key[3]): the model's tables
 };
-// tables, parameters and the zeroed flag word of one potential walk
-static int potential_walk_setup(ngravs_ctx *c, PotWalk *w)
+template <bool USR> static PotUserArg<USR> pot_user_arg(const PotWalk &w)
 {
-  const bool pm = c->cfg.pmgrid != 0, latt = c->cfg.periodic && !pm;
+  if constexpr(USR)
+    return w.pu;
+  else
+    return NoPotUser{0};
+}
+// tables, parameters and the zeroed flag word of one potential walk; far: the largest distance of a target from the domain's centre
+static int potential_walk_setup(ngravs_ctx *c, PotWalk *w, double far)
+{
+  const bool pm = c->cfg.pmgrid != 0, latt = c->cfg.periodic && !pm, usr = !c->user_pot.empty();
   int rc;
   if(pm && (rc = potential_table_ensure(c)))
     return rc;
   if(latt && (rc = potential_lattice_ensure(c)))
     return rc;
+  // the largest r a pair can have: 6 Asmth, half a box diagonal, or the farthest target against the far corner of the domain
+  // (user_reach / lattice_reach / walk_targets_run of kernels_walk.hip, with their margin)
+  const double diag = sqrt(3.0) * c->dom[6];
+  if(usr && (rc = user_pot_tables_ensure(c, pm ? 1.25 * 6.0 * c->asmth : (latt ? 1.25 * 0.5 * sqrt(3.0) * c->cfg.box_size
+                                                                              : 1.25 * fmax(diag, far + 0.5 * diag)))))
+    return rc;
+  memset(&w->pu, 0, sizeof(w->pu));
+  if(usr)
+    user_pot_maps(c, &w->pu);
   make_walk_params(c, &w->wp);
   w->utorwpi = pm ? 1.0 / (2 * M_PI * c->asmth) : 0.0;
   w->reach = pm ? NTAB / w->wp.asmthfac : 0.0;
   w->table = pm ? c->pot_table.p : (latt ? c->pot_lat.p : nullptr);
-  w->key[0] = c->cfg.n_gravs, w->key[1] = pm, w->key[2] = latt;
+  w->key[0] = c->cfg.n_gravs, w->key[1] = pm, w->key[2] = latt, w->key[3] = usr;
   if(c->gt_counters.ensure(GT_C_COUNT))
     return NGRAVS_ERR_NOMEM;
   HIP_TRY(c, hipMemsetAsync(c->gt_counters.p, 0, GT_C_COUNT * sizeof(unsigned long long), c->stream));
@@ -516,20 +623,21 @@ static int potential_walk_flag(ngravs_ctx *c, const PotWalk &w)
   return NGRAVS_OK;
 }
 
-template <int NG, int PM, int LATT> static int launch_potential(Row<NG, PM, LATT>, ngravs_ctx *c, const PotWalk &w, long long n, int *d_nint)
+template <int NG, int PM, int LATT, int USR>
+static int launch_potential(Row<NG, PM, LATT, USR>, ngravs_ctx *c, const PotWalk &w, long long n, int *d_nint)
 {
   const long long ngroups = (n + WAVE - 1) / WAVE;
-  hipLaunchKernelGGL((k_potential_walk<NG, PM, LATT>), dim3((unsigned)((ngroups + 3) / 4)), dim3(256), 0, c->stream, tree_view(c), c->s_pm.p,
-                     c->s_type.p, c->s_oldacc.p, w.table, w.wp, w.utorwpi, w.reach, n, c->r_pot.p, d_nint, w.flag);
+  hipLaunchKernelGGL((k_potential_walk<NG, PM, LATT, USR>), dim3((unsigned)((ngroups + 3) / 4)), dim3(256), 0, c->stream, tree_view(c), c->s_pm.p,
+                     c->s_type.p, c->s_oldacc.p, w.table, w.wp, w.utorwpi, w.reach, n, c->r_pot.p, d_nint, w.flag, pot_user_arg<USR>(w));
   return NGRAVS_OK;
 }
-template <int NG, int PM, int LATT>
-static int launch_potential_targets(Row<NG, PM, LATT>, ngravs_ctx *c, const PotWalk &w, long long nt, const unsigned int *ord)
+template <int NG, int PM, int LATT, int USR>
+static int launch_potential_targets(Row<NG, PM, LATT, USR>, ngravs_ctx *c, const PotWalk &w, long long nt, const unsigned int *ord)
 {
   const long long ngroups = (nt + WAVE - 1) / WAVE;
-  hipLaunchKernelGGL((k_potential_targets<NG, PM, LATT>), dim3((unsigned)((ngroups + 3) / 4)), dim3(256), 0, c->stream, tree_view(c), c->s_pm.p,
+  hipLaunchKernelGGL((k_potential_targets<NG, PM, LATT, USR>), dim3((unsigned)((ngroups + 3) / 4)), dim3(256), 0, c->stream, tree_view(c), c->s_pm.p,
                      c->s_type.p, w.table, w.wp, w.utorwpi, w.reach, c->gt_in.p, c->gt_in.p + 3 * nt, c->gt_in.p + 4 * nt, c->gt_type.p, ord, nt, c->cfg.G,
-                     c->gt_acc.p, c->gt_nint.p, w.flag);
+                     c->gt_acc.p, c->gt_nint.p, w.flag, pot_user_arg<USR>(w));
   return NGRAVS_OK;
 }
 
@@ -542,7 +650,7 @@ int potential_run(ngravs_ctx *c, const ngravs_time_params_t *par, double *d_out,
     return NGRAVS_ERR_NOMEM;
   PotWalk w;
   int rc;
-  if((rc = potential_walk_setup(c, &w)))
+  if((rc = potential_walk_setup(c, &w, 0.0)))   // (own rows: inside the domain)
     return rc;
   HIP_TRY(c, hipEventRecord(c->evk0, c->stream));
   if((rc = dispatch(c, PotRows{}, w.key, [&](auto row) { return launch_potential(row, c, w, n, c->gt_nint.p); })))
@@ -574,14 +682,26 @@ int potential_run(ngravs_ctx *c, const ngravs_time_params_t *par, double *d_out,
     {
       if(c->cfg.periodic)
         for(int g = 0; g < c->cfg.n_gravs; g++)
-          pt.lz[g] = law_sign(c->cfg.law_accel[g][g]) * LATTICE_ZERO *
-                     pow(par->omega0 * 3 * par->hubble * par->hubble / (8 * M_PI * c->cfg.G), 1.0 / 3);   // potential.c:256-257
+          {
+            const ngravs_user_potential_t *e = user_pot_entry(c, g, g);   // the model's LatticeZero[g][g]
+            pt.lz[g] = (e ? e->lattice_zero : law_sign(c->cfg.law_accel[g][g]) * LATTICE_ZERO) *
+                       pow(par->omega0 * 3 * par->hubble * par->hubble / (8 * M_PI * c->cfg.G), 1.0 / 3);   // potential.c:256-257
+          }
       else
         pt.rfac = -0.5 * par->omega0 * par->hubble * par->hubble;                                         // potential.c:313
     }
   else if(par)
     pt.rfac = -0.5 * par->omega_lambda * par->hubble * par->hubble;                                       // potential.c:326
-  hipLaunchKernelGGL(k_potential_finish, GRID1(n), 0, c->stream, c->s_pm.p, c->s_type.p, n, pt, mesh, c->r_pot.p);
+  if(w.key[3])
+    {
+      PotSelf ps;
+      ps.ut = w.pu.ut;
+      for(int t = 0; t < NGRAVS_NTYPES; t++)
+        ps.ks[t] = w.pu.ks[pt.t2g[t]][pt.t2g[t]];
+      hipLaunchKernelGGL(k_potential_finish<true>, GRID1(n), 0, c->stream, c->s_pm.p, c->s_type.p, n, pt, mesh, c->r_pot.p, ps);
+    }
+  else
+    hipLaunchKernelGGL(k_potential_finish<false>, GRID1(n), 0, c->stream, c->s_pm.p, c->s_type.p, n, pt, mesh, c->r_pot.p, NoPotUser{0});
   hipLaunchKernelGGL(k_unpermute_f64, GRID1(n), 0, c->stream, c->s_idx.p, n, 1, c->r_pot.p, d_out);
   if(d_nint)
     hipLaunchKernelGGL(k_unpermute_i32, GRID1(n), 0, c->stream, c->s_idx.p, n, c->gt_nint.p, d_nint);
@@ -594,13 +714,13 @@ int potential_run(ngravs_ctx *c, const ngravs_time_params_t *par, double *d_out,
   return NGRAVS_OK;
 }
 
-int potential_targets_run(ngravs_ctx *c, long long nt)
+int potential_targets_run(ngravs_ctx *c, long long nt, double far)
 {
   if(c->gt_acc.ensure(3 * (size_t)nt) || c->gt_nint.ensure((size_t)nt))
     return NGRAVS_ERR_NOMEM;
   PotWalk w;
   int rc;
-  if((rc = potential_walk_setup(c, &w)))
+  if((rc = potential_walk_setup(c, &w, far)))
     return rc;
   const unsigned int *ord;
   if((rc = grav_targets_order(c, nt, &ord)))

@@ -72,14 +72,15 @@ template <typename X, typename F> static double fit_run(int n, X &&x, F &&phi, d
 }
 
 // r-space table of one law over octaves e_lo .. e_lo + n_oct - 1 with S sub-intervals each
-static double fit_accel(ngravs_gravity_fn f, int e_lo, int n_oct, int S, double *out)
+// (pot: a PotentialFxns function instead, as p(r) = r pot(1, 1, 0, r, 1))
+static double fit_accel(ngravs_gravity_fn f, bool pot, int e_lo, int n_oct, int S, double *out)
 {
   double worst = 0;
   for(int o = 0; o < n_oct; o++)
     {
       const int e = e_lo + o;
       auto x = [&](int j, double t) { return ldexp(0.5 + (j + 0.5 * (t + 1)) / (2.0 * S), e); };
-      auto g = [&](double r) { return r * r * f(1.0, 1.0, r * r, r, 1); };
+      auto g = [&](double r) { return pot ? r * f(1.0, 1.0, 0.0, r, 1) : r * r * f(1.0, 1.0, r * r, r, 1); };
       worst = fmax(worst, fit_run(S, x, g, out + (size_t)o * S * UL_NC));
     }
   return worst;
@@ -116,7 +117,7 @@ static int distinct_soft(const double *fs, double *h)
   return nh;
 }
 
-// Build the accel tables of every ACCEL entry and the spline tables of every SPLINE entry of a registry into host memory.
+// Build the accel tables of every ACCEL (POT) entry and the spline tables of every SPLINE (POT_SPLINE) entry of a registry into host memory.
 // r_hi: largest r the walks can evaluate.  Returns the largest check-point deviation.
 static double build_tables(const ngravs_user_fn_t *fns, int nfns, const double *fsoft, double r_hi, UserTabs *ut, std::vector<double> &h)
 {
@@ -138,8 +139,8 @@ static double build_tables(const ngravs_user_fn_t *fns, int nfns, const double *
       acc.assign((size_t)nfns * n_oct * S * UL_NC, 0.0);
       double w = 0;
       for(int k = 0; k < nfns; k++)
-        if(fns[k].kind == NGRAVS_USER_ACCEL)
-          w = fmax(w, fit_accel(fns[k].fn, e_lo, n_oct, S, acc.data() + (size_t)k * n_oct * S * UL_NC));
+        if(fns[k].kind == NGRAVS_USER_ACCEL || fns[k].kind == NGRAVS_USER_POT)
+          w = fmax(w, fit_accel(fns[k].fn, fns[k].kind == NGRAVS_USER_POT, e_lo, n_oct, S, acc.data() + (size_t)k * n_oct * S * UL_NC));
       if(w <= UL_TOL || S >= UL_S_MAX)
         {
           worst = fmax(worst, w);
@@ -152,7 +153,7 @@ static double build_tables(const ngravs_user_fn_t *fns, int nfns, const double *
       spl.assign((size_t)nfns * nh * Ss * UL_NC, 0.0);
       double w = 0;
       for(int k = 0; k < nfns; k++)
-        if(fns[k].kind == NGRAVS_USER_SPLINE)
+        if(fns[k].kind == NGRAVS_USER_SPLINE || fns[k].kind == NGRAVS_USER_POT_SPLINE)
           for(int q = 0; q < nh; q++)
             w = fmax(w, fit_spline(fns[k].fn, hs[q], Ss, spl.data() + ((size_t)k * nh + q) * Ss * UL_NC));
       if(w <= UL_TOL || Ss >= UL_S_MAX)
@@ -203,49 +204,68 @@ int user_green_ensure(ngravs_ctx *c)
   return NGRAVS_OK;
 }
 
-int user_tables_ensure(ngravs_ctx *c, double r_need)
+// the device tables of one registry (the force laws', the potential companions'): (re)built when r_need or the softenings are
+// not covered by what is there
+static int registry_tables_ensure(ngravs_ctx *c, const std::vector<ngravs_user_fn_t> &fns, double r_need, const char *what,
+                                  DevBuf<double> &tab, UserTabs &cur, bool &ready, double *soft)
 {
-  if(c->user_fns.empty() || !cfg_has_user(c->cfg))
-    return NGRAVS_OK;
   bool same_soft = true;
   for(int t = 0; t < NGRAVS_NTYPES; t++)
-    same_soft = same_soft && c->user_soft[t] == c->cfg.force_softening[t];
-  const double top = c->user_ready ? ldexp(1.0, c->user_ut.e_lo + c->user_ut.n_oct - 1) : 0.0;
-  if(c->user_ready && same_soft && r_need < top)
+    same_soft = same_soft && soft[t] == c->cfg.force_softening[t];
+  const double top = ready ? ldexp(1.0, cur.e_lo + cur.n_oct - 1) : 0.0;
+  if(ready && same_soft && r_need < top)
     return NGRAVS_OK;
   // grow geometrically so that a slowly expanding domain re-tabulates rarely
   const double r_hi = fmax(r_need, 2.0 * top);
   std::vector<double> h;
   UserTabs ut;
-  const double worst = build_tables(c->user_fns.data(), (int)c->user_fns.size(), c->cfg.force_softening, r_hi > 0 ? r_hi : 1.0, &ut, h);
+  const double worst = build_tables(fns.data(), (int)fns.size(), c->cfg.force_softening, r_hi > 0 ? r_hi : 1.0, &ut, h);
   if(!(worst <= UL_FAIL))
     {
-      ngravs_report(c, NGRAVS_ERR_WIRING, "a user-defined law cannot be tabulated to 1e-9 with " + std::to_string(UL_S_MAX) +
+      ngravs_report(c, NGRAVS_ERR_WIRING, std::string(what) + " cannot be tabulated to 1e-9 with " + std::to_string(UL_S_MAX) +
                                                " sub-intervals per octave / softening (a kink or a steep feature?): deviation " +
                                                std::to_string(worst));
       return NGRAVS_ERR_WIRING;
     }
   const size_t spl_off = (size_t)(uintptr_t)ut.spl / sizeof(double);
-  if(c->user_tab.ensure(h.size() + 1))
+  if(tab.ensure(h.size() + 1))
     return NGRAVS_ERR_NOMEM;
-  HIP_TRY(c, hipMemcpyAsync(c->user_tab.p, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(tab.p, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  ut.coef = c->user_tab.p;
-  ut.spl = c->user_tab.p + spl_off;
-  c->user_ut = ut;
+  ut.coef = tab.p;
+  ut.spl = tab.p + spl_off;
+  cur = ut;
   for(int t = 0; t < NGRAVS_NTYPES; t++)
-    c->user_soft[t] = c->cfg.force_softening[t];
-  c->user_ready = true;
+    soft[t] = c->cfg.force_softening[t];
+  ready = true;
   return NGRAVS_OK;
+}
+
+int user_tables_ensure(ngravs_ctx *c, double r_need)
+{
+  if(c->user_fns.empty() || !cfg_has_user(c->cfg))
+    return NGRAVS_OK;
+  return registry_tables_ensure(c, c->user_fns, r_need, "a user-defined law", c->user_tab, c->user_ut, c->user_ready, c->user_soft);
+}
+
+int user_pot_tables_ensure(ngravs_ctx *c, double r_need)
+{
+  if(c->upot_fns.empty())
+    return NGRAVS_OK;
+  return registry_tables_ensure(c, c->upot_fns, r_need, "a potential function of the model (ngravs_create_with_potentials)", c->upot_tab,
+                                c->upot_ut, c->upot_ready, c->upot_soft);
 }
 
 extern "C" int ngravs_user_table_eval(const ngravs_user_fn_t *fn, double r_lo, double r_hi, double h, const double *r, int64_t n,
                                       double *out, double *max_err)
 {
-  if(!fn || !fn->fn || !r || !out || n < 0 || (fn->kind != NGRAVS_USER_ACCEL && fn->kind != NGRAVS_USER_SPLINE))
+  if(!fn || !fn->fn || !r || !out || n < 0)
+    return NGRAVS_ERR_ARG;
+  const bool over_r = fn->kind == NGRAVS_USER_ACCEL || fn->kind == NGRAVS_USER_POT;
+  if(!over_r && fn->kind != NGRAVS_USER_SPLINE && fn->kind != NGRAVS_USER_POT_SPLINE)
     return NGRAVS_ERR_ARG;
   double fs[NGRAVS_NTYPES] = {0, 0, 0, 0, 0, 0};
-  if(fn->kind == NGRAVS_USER_ACCEL)
+  if(over_r)
     {
       if(!(r_lo > 0) || !(r_hi > r_lo))
         return NGRAVS_ERR_ARG;
@@ -259,12 +279,13 @@ extern "C" int ngravs_user_table_eval(const ngravs_user_fn_t *fn, double r_lo, d
     }
   std::vector<double> tab;
   UserTabs ut;
-  const double w = build_tables(fn, 1, fs, fn->kind == NGRAVS_USER_ACCEL ? r_hi : 2 * h, &ut, tab);
+  const double w = build_tables(fn, 1, fs, over_r ? r_hi : 2 * h, &ut, tab);
   const size_t spl_off = (size_t)(uintptr_t)ut.spl / sizeof(double);
   ut.coef = tab.data();
   ut.spl = tab.data() + spl_off;
   for(int64_t i = 0; i < n; i++)
-    out[i] = fn->kind == NGRAVS_USER_ACCEL ? ul_g(ut, 0, r[i]) / (r[i] * r[i]) : ul_spline(ut, 0, h, r[i]);
+    out[i] = fn->kind == NGRAVS_USER_ACCEL ? ul_g(ut, 0, r[i]) / (r[i] * r[i])
+                                           : (fn->kind == NGRAVS_USER_POT ? ul_g(ut, 0, r[i]) / r[i] : ul_spline(ut, 0, h, r[i]));
   if(max_err)
     *max_err = w;
   return NGRAVS_OK;
@@ -353,6 +374,207 @@ bool user_lattice_complete(const ngravs_ctx *c)
       if(c->cfg.law_accel[a][b] >= NGRAVS_LAW_USER0 && !user_lattice_fn(c, a, b))
         return false;
   return true;
+}
+
+// ---- the model's potential companions (ngravs_create_with_potentials) -------------------------------------------------------
+// lattice_init's potcorr (forcetree.c:3699-3702): LatticePotential[l][m](x) at x = 0.5 (i, j, k) / NGRAVS_EN, the origin
+// LatticeZero[l][m], both divided by BoxSize; the layout of k_lattice_pot_table
+int user_pot_lattice_tabulate(ngravs_lattice_pot_fn fn, double zero, double box, double *out, std::string &why)
+{
+  const long long npts = (long long)ULAT_E1 * ULAT_E1 * ULAT_E1;
+  const unsigned hc = std::thread::hardware_concurrency();
+  const int nth = (int)std::max(1u, std::min((unsigned)ULAT_THREADS, hc));
+  std::vector<long long> bad(nth, -1);   // per thread: the first point whose sample is not finite
+  auto work = [&](int t) {
+    for(long long n = npts * t / nth; n < npts * (t + 1) / nth; n++)
+      {
+        const int i = (int)(n / (ULAT_E1 * ULAT_E1)), j = (int)((n / ULAT_E1) % ULAT_E1), k = (int)(n % ULAT_E1);
+        double x[3] = {0.5 * ((double)i) / ULAT_EN, 0.5 * ((double)j) / ULAT_EN, 0.5 * ((double)k) / ULAT_EN};
+        const double v = n == 0 ? zero : fn(x);   // the origin never calls the function
+        if(!std::isfinite(v))
+          {
+            bad[t] = n;
+            return;
+          }
+        out[n] = v / box;
+      }
+  };
+  std::vector<std::thread> th;
+  for(int t = 1; t < nth; t++)
+    {
+      try
+        {
+          th.emplace_back(work, t);
+        }
+      catch(...)
+        {
+          work(t);   // no thread to be had: this one does the share
+        }
+    }
+  work(0);
+  for(auto &x : th)
+    x.join();
+  for(int t = 0; t < nth; t++)
+    if(bad[t] >= 0)
+      {
+        const long long n = bad[t];
+        why = "lattice potential: non-finite value at point (" + std::to_string(n / (ULAT_E1 * ULAT_E1)) + ", " +
+              std::to_string((n / ULAT_E1) % ULAT_E1) + ", " + std::to_string(n % ULAT_E1) + ")";
+        return NGRAVS_ERR_WIRING;
+      }
+  return NGRAVS_OK;
+}
+
+const ngravs_user_potential_t *user_pot_entry(const ngravs_ctx *c, int a, int b)
+{
+  for(const ngravs_user_potential_t &e : c->user_pot)
+    if(e.target == a && e.source == b)
+      return &e;
+  return nullptr;
+}
+
+// the distinct pot and pot_spline functions of the entries, each tabulated once
+void user_pot_registry(ngravs_ctx *c)
+{
+  c->upot_fns.clear();
+  auto add = [&](int kind, ngravs_gravity_fn f) {
+    for(const ngravs_user_fn_t &u : c->upot_fns)
+      if(u.kind == kind && u.fn == f)
+        return;
+    c->upot_fns.push_back(ngravs_user_fn_t{kind, 0, f});
+  };
+  for(const ngravs_user_potential_t &e : c->user_pot)
+    {
+      add(NGRAVS_USER_POT, e.pot);
+      add(NGRAVS_USER_POT_SPLINE, e.pot_spline);
+    }
+}
+
+void user_pot_maps(const ngravs_ctx *c, PotUser *pu)
+{
+  auto find = [&](int kind, ngravs_gravity_fn f) {
+    for(size_t k = 0; k < c->upot_fns.size(); k++)
+      if(c->upot_fns[k].kind == kind && c->upot_fns[k].fn == f)
+        return (int)k;
+    return -1;
+  };
+  for(int a = 0; a < NG_MAX; a++)
+    for(int b = 0; b < NG_MAX; b++)
+      {
+        const ngravs_user_potential_t *e = a < c->cfg.n_gravs && b < c->cfg.n_gravs ? user_pot_entry(c, a, b) : nullptr;
+        pu->kp[a][b] = e ? find(NGRAVS_USER_POT, e->pot) : -1;
+        pu->ks[a][b] = e ? find(NGRAVS_USER_POT_SPLINE, e->pot_spline) : -1;
+      }
+  pu->ut = c->upot_ut;
+}
+
+static bool close_to(double a, double b);
+
+int user_check_potentials(const ngravs_config_t *cfg, const ngravs_user_potential_t *pots, int npot, std::string &why)
+{
+  if(npot < 0 || (npot > 0 && !pots))
+    {
+      why = "potential entries: a negative count or no array";
+      return NGRAVS_ERR_ARG;
+    }
+  const int ng = cfg->n_gravs;
+  auto name = [&](int e) {
+    return "potential entry " + std::to_string(e) + " [" + std::to_string(pots[e].target) + "][" + std::to_string(pots[e].source) + "]";
+  };
+  for(int e = 0; e < npot; e++)
+    {
+      const int a = pots[e].target, b = pots[e].source;
+      if(a < 0 || a >= ng || b < 0 || b >= ng)
+        {
+          why = name(e) + ": species pair out of range";
+          return NGRAVS_ERR_WIRING;
+        }
+      for(int q = 0; q < e; q++)
+        if(pots[q].target == a && pots[q].source == b)
+          {
+            why = name(e) + ": a second entry for this pair (entry " + std::to_string(q) + ")";
+            return NGRAVS_ERR_WIRING;
+          }
+      if(cfg->law_accel[a][b] == NGRAVS_LAW_NONE)
+        {
+          why = name(e) + ": law_accel of the pair is NONE (nothing is wired there)";
+          return NGRAVS_ERR_WIRING;
+        }
+      if(!pots[e].pot || !pots[e].pot_spline)
+        {
+          why = name(e) + ": no pot or no pot_spline function";
+          return NGRAVS_ERR_WIRING;
+        }
+      if(pots[e].lattice_pot && !cfg->periodic)
+        {
+          why = name(e) + ": a lattice potential in a non-periodic configuration";
+          return NGRAVS_ERR_WIRING;
+        }
+      if(!pots[e].lattice_pot && cfg->periodic && !cfg->pmgrid)
+        {
+          why = name(e) + ": a periodic tree-only run needs the pair's lattice_pot (the reference's LatticePotential)";
+          return NGRAVS_ERR_WIRING;
+        }
+      if(!std::isfinite(pots[e].lattice_zero))
+        {
+          why = name(e) + ": lattice_zero is not finite";
+          return NGRAVS_ERR_WIRING;
+        }
+      bool mirrored = a == b || cfg->law_accel[b][a] == NGRAVS_LAW_NONE;
+      for(int q = 0; q < npot && !mirrored; q++)
+        mirrored = pots[q].target == b && pots[q].source == a;
+      if(!mirrored)
+        {
+          why = name(e) + ": the mirrored pair has no entry (the two are probed against each other, ngravs_core.c:389-413)";
+          return NGRAVS_ERR_WIRING;
+        }
+    }
+  // ngravs_core.c:389, :408-413 for the pairs that have entries on both sides
+  for(int e = 0; e < npot; e++)
+    for(int q = 0; q < e; q++)
+      if(pots[q].target == pots[e].source && pots[q].source == pots[e].target)
+        {
+          if(!(pots[e].pot(1, 1, 0.5, 3, 1) == pots[q].pot(1, 1, 0.5, 3, 1)) ||
+             !(pots[e].pot_spline(1, 1, 0.5, 3, 1) == pots[q].pot_spline(1, 1, 0.5, 3, 1)))
+            {
+              why = name(e) + ": potential table violates Newton's third law against entry " + std::to_string(q) + " (ngravs_core.c:408-413)";
+              return NGRAVS_ERR_WIRING;
+            }
+          if(pots[e].lattice_pot != pots[q].lattice_pot || !(pots[e].lattice_zero == pots[q].lattice_zero))
+            {
+              why = name(e) + ": lattice_pot or lattice_zero differs from entry " + std::to_string(q) + " of the mirrored pair (ngravs_core.c:389)";
+              return NGRAVS_ERR_WIRING;
+            }
+        }
+  // what a tree can represent: linear in the source mass, independent of the target mass and of N (the probes of the force laws)
+  for(int e = 0; e < npot; e++)
+    {
+      auto probe = [&](ngravs_gravity_fn f, double x, double r) -> bool {
+        const double v = f(1, 1, x, r, 1);
+        return std::isfinite(v) && close_to(f(1, 2, x, r, 1), 2 * v) && close_to(f(1, 0.25, x, r, 1), 0.25 * v) &&
+               close_to(f(3, 1, x, r, 1), v) && close_to(f(1, 1, x, r, 7), v);
+      };
+      bool ok = true, no_h = true;
+      for(double r : {1e-3, 0.05, 0.7, 3.0, 40.0, 900.0})
+        {
+          ok = ok && probe(pots[e].pot, 0.5 * r, r);
+          no_h = no_h && close_to(pots[e].pot(1, 1, 0.5 * r, r, 1), pots[e].pot(1, 1, 0.0, r, 1));
+        }
+      for(double u : {0.0, 0.05, 0.3, 0.6, 0.95})
+        ok = ok && probe(pots[e].pot_spline, 1.0, u);
+      if(!ok)
+        {
+          why = name(e) + ": the tree needs a potential linear in the source mass and independent of the target mass and of N "
+                          "(a node's monopole is a mass sum)";
+          return NGRAVS_ERR_WIRING;
+        }
+      if(!no_h)
+        {
+          why = name(e) + ": pot depends on its softening argument h (it is tabulated over r alone, for r >= h)";
+          return NGRAVS_ERR_WIRING;
+        }
+    }
+  return NGRAVS_OK;
 }
 
 // ---- the checks of ngravs_create_with_laws ----------------------------------------------------------------------------------

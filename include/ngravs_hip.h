@@ -182,7 +182,11 @@ typedef enum {
   NGRAVS_USER_ACCEL = 0,    /* AccelFxns        */
   NGRAVS_USER_SPLINE = 1,   /* AccelSplines     */
   NGRAVS_USER_GREENS = 2,   /* GreensFxns       */
-  NGRAVS_USER_NORMED = 3    /* NormedGreensFxns */
+  NGRAVS_USER_NORMED = 3,   /* NormedGreensFxns */
+  /* the two potential tables: for ngravs_user_table_eval only -- a registry refuses them, potentials travel in the
+   * ngravs_user_potential_t entries of ngravs_create_with_potentials */
+  NGRAVS_USER_POT = 4,        /* PotentialFxns    */
+  NGRAVS_USER_POT_SPLINE = 5  /* PotentialSplines */
 } ngravs_user_kind;
 typedef struct {
   int32_t kind;             /* ngravs_user_kind */
@@ -201,6 +205,22 @@ typedef struct {
   int32_t target, source;   /* the species pair: law_accel[target][source] is a user id */
   ngravs_lattice_fn fn;     /* must stay valid as long as the context */
 } ngravs_user_lattice_t;
+/* The potential companions of one species pair, the reference's PotentialFxns, PotentialSplines, LatticePotential and LatticeZero
+ * [target][source] (allvars.h:134-149; ngravs.c:132-150 wires newtonian_pot, plummer_pot, ewald_psi and 2.8372975).  pot and
+ * pot_spline are evaluated at unit masses and N = 1 and scaled by the source mass; pot is tabulated over r alone, with 0 in the
+ * place of h (as pm_nonperiodic.c:564 calls it), and must not depend on it.  lattice_pot is the reference's `latpot`
+ * (allvars.h:139): called at x = 0.5 (i, j, k) / 64 in box units, every point of the octant grid but the origin, whose value is
+ * lattice_zero; the library divides both by BoxSize (forcetree.c:3699-3702).  It is called concurrently from at most 16 host
+ * threads, 65^3 - 1 calls per distinct function, at the first periodic tree-only potential call.  All functions must stay valid
+ * as long as the context. */
+typedef double (*ngravs_lattice_pot_fn)(double x[3]);
+typedef struct {
+  int32_t target, source;            /* the species pair [target][source]: law_accel of the pair is not NONE            */
+  ngravs_gravity_fn pot;             /* PotentialFxns:    f(target mass, source mass, h, r, N); newtonian_pot = +source / r */
+  ngravs_gravity_fn pot_spline;      /* PotentialSplines: f(target, source, h, r, N) for r < h; plummer_pot               */
+  ngravs_lattice_pot_fn lattice_pot; /* LatticePotential; NULL where not needed (not periodic, or with a mesh)            */
+  double lattice_zero;               /* LatticeZero                                                                      */
+} ngravs_user_potential_t;
 /* Which kernel the last ngravs_gravity_tree() walked with (ngravs_last_walk_kernel) */
 typedef enum {
   NGRAVS_KERNEL_NONE = 0,
@@ -235,6 +255,24 @@ int ngravs_create_with_laws(const ngravs_config_t *cfg, const ngravs_user_fn_t *
  * NGRAVS_ERR_WIRING and names the pair and the point. */
 int ngravs_create_with_lattice(const ngravs_config_t *cfg, const ngravs_user_fn_t *fns, int nfns, const ngravs_user_lattice_t *lat,
                                int nlat, ngravs_ctx **out);
+/* ngravs_create_with_lattice with the model's own potential companions, at most one entry per species pair;
+ * ngravs_create_with_lattice is this with npot = 0.  A pair without an entry behaves as before: Newton / neg-Newton with the
+ * Plummer splines have the built-in companions, every other law has none.  An entry may sit on any pair whose law_accel is not
+ * NONE, built in (Yukawa, coloyuk; Newton too, whose built-in companion it then replaces) or a user id; the BAM laws stay
+ * refused by the potential calls (their potentials depend on the target mass and on N, which a node's monopole cannot carry
+ * through a table that is linear in the source mass).  ngravs_compute_potential and ngravs_potential_targets serve a context in
+ * which every wired pair has a built-in companion or an entry.  The functions are sampled lazily into tables like the force
+ * laws (degree-7 pieces; p(r) = r pot(1, 1, 0, r, 1) over the octaves of r, pot_spline(1, 1, h, u h, 1) over u in [0, 1) for
+ * every distinct softening length; distinct function pointers once); they are rebuilt when ngravs_set_softening changes a length
+ * or the walk's largest r outgrows them, and a law whose fit is not within 1e-9 fails that call with NGRAVS_ERR_WIRING.
+ * Refused at creation with NGRAVS_ERR_WIRING, without GPU work and with nothing created: an entry out of range; two entries for
+ * one pair; an entry on a pair wired NONE; an entry without pot or pot_spline; pot[i][j](1,1,0.5,3,1) != pot[j][i](...) and the
+ * same for the splines (ngravs_core.c:408-413); lattice_pot pointers or lattice_zero that differ between [i][j] and [j][i]
+ * (ngravs_core.c:389); a pot or pot_spline that is not linear in the source mass or depends on the target mass or on N, or a pot
+ * that depends on h; a periodic tree-only configuration with an entry that has no lattice_pot; a lattice_pot in a configuration
+ * that is not periodic.  With a mesh lattice_pot is optional and unused; lattice_zero is read by the tail in every periodic run. */
+int ngravs_create_with_potentials(const ngravs_config_t *cfg, const ngravs_user_fn_t *fns, int nfns, const ngravs_user_lattice_t *lat,
+                                  int nlat, const ngravs_user_potential_t *pots, int npot, ngravs_ctx **out);
 /* NGRAVS_KERNEL_* of the last walk of the context (0 before the first) */
 int ngravs_last_walk_kernel(ngravs_ctx *ctx);
 /* CUs reserved for PM beside the walk in the last ngravs_compute_accelerations (0: PM and walk ran one after another) */
@@ -377,8 +415,10 @@ int ngravs_shortrange_table_with_laws(const ngravs_config_t *cfg, const ngravs_u
                                       double *pot_out);
 /* The tables the kernels evaluate for one user law, built and evaluated on the host (no GPU): kind NGRAVS_USER_ACCEL tabulates
  * fn over r in [r_lo, r_hi] and returns accel(1, 1, r^2, r, 1) from the table at the n radii r[]; NGRAVS_USER_SPLINE tabulates
- * fn for softening h and returns spline(1, 1, h, r, 1) from the table (0 <= r < h).  *max_err (may be NULL): the largest
- * relative deviation from the callback the fit saw at its check points. */
+ * fn for softening h and returns spline(1, 1, h, r, 1) from the table (0 <= r < h).  NGRAVS_USER_POT and
+ * NGRAVS_USER_POT_SPLINE do the same for the two potential functions of an ngravs_user_potential_t: pot(1, 1, 0, r, 1) over
+ * [r_lo, r_hi] and pot_spline(1, 1, h, r, 1).  *max_err (may be NULL): the largest relative deviation from the callback the
+ * fit saw at its check points. */
 int ngravs_user_table_eval(const ngravs_user_fn_t *fn, double r_lo, double r_hi, double h, const double *r, int64_t n, double *out,
                            double *max_err);
 /* One lattice-correction table as the kernels read it, built on the host (no GPU): out[3][65^3] (x, y, z; point (i, j, k) at
@@ -951,6 +991,14 @@ int ngravs_find_next_outputtime(const ngravs_time_params_t *par, const ngravs_ou
  * block of a snapshot take.  What the reference's potential routines mean, not what they do (DESIGN.md §8 lists their defects).
  * Built-in laws with a wired potential companion: NGRAVS_LAW_NEWTON / NGRAVS_LAW_NEG_NEWTON (newtonian_pot, neg_newtonian_pot) with
  * NGRAVS_SPLINE_PLUMMER / NGRAVS_SPLINE_NEG_PLUMMER (plummer_pot, neg_plummer_pot; ngravs.c:368-489); a pair wired NONE gives 0.
+ * Every other law, and a Newton pair whose companion is to be replaced, takes the model's own functions from an entry of
+ * ngravs_create_with_potentials: Pfn(m, r) = m pot(1, 1, 0, r, 1) and Pspl(m, h, r) = m pot_spline(1, 1, h, r, 1) from their
+ * tables, its lattice_pot(x) / BoxSize in the place of sign(law) ewald_psi / BoxSize in step 1 (the origin of the table
+ * lattice_zero / BoxSize), - m pot_spline[g][g](1, 1, h, 0, 1) in the place of step 2 for a row of species g (plummer_pot gives
+ * the reference's m / SofteningTable; a lone particle's potential is 0 under every law), and its lattice_zero[g][g] in step 3.  The
+ * long-range share removed in a TreePM run is that of the pair's law_normed, the mesh part that of its law_greens, built in or
+ * user, as for the force.  The mesh's k = 0 is 0: for a screened law, whose Green's function is finite there, this leaves a
+ * constant per target species (G sum of the source masses x greens(0) / volume) out of the column.
  * For ALL own rows, whatever their active flags, in the order of potential.c:244-337:
  *   1. the potential walk of the built tree with the context's opening criterion (the strict walk's traversal): per source of mass
  *      m at distance r, h = max(h_target, h_source):  r >= h: -= Pfn(m, r);  r < h: += Pspl(m, h, r);  periodic tree-only: += m x
@@ -968,8 +1016,8 @@ int ngravs_find_next_outputtime(const ngravs_time_params_t *par, const ngravs_ou
  * rewrites the potential mesh: ngravs_pm_targets is refused until the next PM step, ngravs_potential_targets is served until the
  * next PM step or hand-over of particles.
  * NGRAVS_ERR_ARG for a NULL ctx.  Refused with a message and nothing written: NGRAVS_ERR_ARG for a NULL potential, world_size > 1 or
- * a multi-task working set, adaptive gas softening, a Yukawa, coloyuk, BAM or user law in a wired pair, a mesh without periodic
- * boundaries; NGRAVS_ERR_STATE without a built tree of the current particle set (after ngravs_update_particles it is refit first). */
+ * a multi-task working set, adaptive gas softening, a BAM law in a wired pair, a wired pair that has neither a built-in companion
+ * nor an entry of ngravs_create_with_potentials (the first such pair is named), a mesh without periodic boundaries; NGRAVS_ERR_STATE without a built tree of the current particle set (after ngravs_update_particles it is refit first). */
 int ngravs_compute_potential(ngravs_ctx *ctx, const ngravs_time_params_t *par, double *potential, int64_t potential_stride,
                              int32_t on_device, int32_t *nint);
 /* Step 1 x G, plus step 5 with a mesh, at nt target records (the records of ngravs_gravity_tree_targets, any order, any finite
@@ -980,7 +1028,8 @@ int ngravs_compute_potential(ngravs_ctx *ctx, const ngravs_time_params_t *par, d
 int ngravs_potential_targets(ngravs_ctx *ctx, const ngravs_grav_targets_t *targets, int64_t nt, double *pot, int32_t *nint);
 /* The lattice potential table of the pair (target, source) as the periodic tree-only walk reads it: out[65^3] (host),
  * [i][j][k] = sign(law) ewald_psi(i / 128, j / 128, k / 128) / BoxSize, the origin sign(law) 2.8372975 / BoxSize.  Tabulated on the
- * device at the first use.  NGRAVS_ERR_ARG unless the configuration is periodic without a mesh and the pair is wired. */
+ * device at the first use.  A pair with an entry of ngravs_create_with_potentials: its lattice_pot / BoxSize, the origin its
+ * lattice_zero / BoxSize, sampled on the host. NGRAVS_ERR_ARG unless the configuration is periodic without a mesh and the pair is wired. */
 int ngravs_lattice_potential_table(ngravs_ctx *ctx, int32_t target, int32_t source, double *out);
 /* device milliseconds of the walk kernel of the last ngravs_compute_potential (HIP events) */
 int ngravs_last_potential_ms(ngravs_ctx *ctx, double *walk_ms);
