@@ -1597,7 +1597,7 @@ extern "C" int ngravs_direct_sum_targets(ngravs_ctx *c, const double *pos, const
   if(dt.ensure(nt) || dty.ensure(nt) || dacc.ensure(3 * nt))
     return NGRAVS_ERR_NOMEM;
   std::vector<double4> h((size_t)nt);
-  double r_need = 0;   // user-defined laws: farthest a target can be from a source (target to domain centre + half diagonal)
+  double far = 0;   // user-defined laws: the farthest target from the domain's centre (table_reach)
   for(int64_t k = 0; k < nt; k++)
     {
       h[k].x = pos[3 * k];
@@ -1605,14 +1605,14 @@ extern "C" int ngravs_direct_sum_targets(ngravs_ctx *c, const double *pos, const
       h[k].z = pos[3 * k + 2];
       h[k].w = mass ? mass[k] : 1.0;
       const double dx = h[k].x - c->dom[3], dy = h[k].y - c->dom[4], dz = h[k].z - c->dom[5];
-      r_need = fmax(r_need, 1.25 * (sqrt(dx * dx + dy * dy + dz * dz) + 0.5 * sqrt(3.0) * c->dom[6]));
+      far = fmax(far, sqrt(dx * dx + dy * dy + dz * dz));
     }
   int rc = NGRAVS_OK;
   if(hipMemcpyAsync(dt.p, h.data(), sizeof(double4) * nt, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
      hipMemcpyAsync(dty.p, type, sizeof(int) * nt, hipMemcpyHostToDevice, c->stream) != hipSuccess)
     rc = NGRAVS_ERR_NO_DEVICE;
   if(!rc)
-    rc = direct_run_targets(c, dt.p, dty.p, nt, dacc.p, r_need);
+    rc = direct_run_targets(c, dt.p, dty.p, nt, dacc.p, far);
   if(!rc && hipMemcpyAsync(acc, dacc.p, sizeof(double) * 3 * nt, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
     rc = NGRAVS_ERR_NO_DEVICE;
   (void)hipStreamSynchronize(c->stream);

@@ -539,6 +539,10 @@ bool user_lattice_complete(const ngravs_ctx *c);
 int user_lattice_tabulate(ngravs_lattice_fn fn, double box, double *out, std::string &why);
 void ngravs_report(ngravs_ctx *ctx, int code, const std::string &msg);
 int user_tables_ensure(ngravs_ctx *c, double r_need);
+// The r_need of a law's or a potential's tables, a quarter to spare: the largest distance a pair is evaluated at.  shortrange: a
+// walk, which a mesh cuts at the end of the short-range table; not the direct sum.  far: the largest distance of a target from
+// the domain's centre (0: own rows)
+double table_reach(const ngravs_ctx *c, bool shortrange, double far);
 int user_green_ensure(ngravs_ctx *c);   // PM: the G(k2) tables of the user greens ids   // (re)build the tables if r_need or the softenings are not covered
 double user_normed(const ngravs_user_fn_t *fns, int nfns, int law, double k2);
 // the potential entries of ngravs_create_with_potentials: the creation checks; the entry of pair (a, b) (nullptr: none); the
@@ -557,7 +561,7 @@ int walk_enqueue(ngravs_ctx *c);
 int walk_complete(ngravs_ctx *c);
 int walk_finish(ngravs_ctx *c);
 int direct_run(ngravs_ctx *c, const int *d_idx, int64_t nt, double *d_acc);
-int direct_run_targets(ngravs_ctx *c, const double4 *d_tpm, const int *d_ttype, int64_t nt, double *d_acc, double r_need = 0);
+int direct_run_targets(ngravs_ctx *c, const double4 *d_tpm, const int *d_ttype, int64_t nt, double *d_acc, double far = 0);   // far: as table_reach
 // adaptive softening: s_soft from in_gsoft and the order, n_maxsoft bottom-up from the tree (nodes: also the node column), each
 // only when stale
 int adaptive_refresh(ngravs_ctx *c, bool nodes);

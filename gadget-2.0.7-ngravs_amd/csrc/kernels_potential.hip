@@ -7,13 +7,15 @@
 //   the tail of compute_potential           potential.c:244-337     k_potential_finish
 // The mesh part (pmpotential_periodic) is kernels_pm.hip's pm_solve + k_potential_gather.
 //
-// The walk is the strict walk's traversal (kernels_walk.hip: wave-lock-step depth-first, every lane its own decision, lane_skip,
-// the pseudo-node flag) with the potential walk's two differences: a periodic tree-only run adds the lattice term in the same
-// visit (no second walk), and the short-range walk prunes by the eff_dist box alone -- here with the table's reach.  Wired companions: newtonian_pot,
+// The walk is the strict walk's traversal (strict_walk.hpp: the driver, the species offsets, the opening criterion, the reach box,
+// the pseudo-node flag -- the code the force walk runs) with the potential walk's own interaction and softening rule and its two
+// differences: a periodic tree-only run adds the lattice term in the same visit (no second walk), and the short-range walk
+// prunes by the eff_dist box alone -- here with the table's reach.  Wired companions: newtonian_pot,
 // neg_newtonian_pot, plummer_pot, neg_plummer_pot (ngravs.c:368-489), as the coefficients cN / cS of WalkParams (+1, -1, 0).
 // The USR variants also read the model's own companions (ngravs_create_with_potentials) from the tables user_laws.cpp builds.
 #include "engine.hpp"
 #include "walk_device.hpp"
+#include "strict_walk.hpp"
 #include "columns.hpp"
 
 #pragma clang fp contract(off)
@@ -103,13 +105,13 @@ __device__ __forceinline__ void potential_walk_lane(const TreeView &tv, const do
                                                     const double reach, const bool valid, const StrictTarget &T, int *sn, int *ss, int *__restrict__ err_flag,
                                                     const PotUserArg<USR> &pu, double &pot_out, int &nint_out)
 {
-  const double px = T.x, py = T.y, pz = T.z, aold = T.aold, hT = T.h;
+  const double hT = T.h;
   const int tg = T.tg;
   double pot = 0;
   int nint = 0;
-  const int NO_SKIP = 0x7fffffff;
-  int lane_skip = valid ? NO_SKIP : -1;   // (kernels_walk.hip, strict_walk_lane)
-  int sp = -1;
+  StrictDfs w;
+  w.sn = sn;
+  w.ss = ss;
 
   // USR: the tables of this lane's target species against every source species, one byte each (table + 1; 0: no entry).  The
   // source species of a visit is the same for the whole wave, the target's is the lane's: the piece of the table a lane reads
@@ -174,91 +176,41 @@ __device__ __forceinline__ void potential_walk_lane(const TreeView &tv, const do
   auto do_particle = [&](int p) {
     const double4 q = s_pm[p];   // uniform address -> scalar load
     const int qt = s_type[p];
-    if(lane_skip > sp)
+    if(w.takes_part())
       {
-        double dx = q.x - px, dy = q.y - py, dz = q.z - pz;
-        if(wp.periodic)
-          {
-            dx = nearest(dx, wp.box, wp.boxhalf);
-            dy = nearest(dy, wp.box, wp.boxhalf);
-            dz = nearest(dz, wp.box, wp.boxhalf);
-          }
+        double dx, dy, dz;
+        const double r2 = offset_from(q, T, wp, wp.periodic, dx, dy, dz);
         double h = hT;
         if(h < wp.fsoft[qt])
           h = wp.fsoft[qt];
-        const bool added = interact(wp.t2g[qt], dx, dy, dz, dx * dx + dy * dy + dz * dz, q.w, h);
+        const bool added = interact(wp.t2g[qt], dx, dy, dz, r2, q.w, h);
         if(added || !PM)
           nint++;
       }
   };
 
-  // returns true if some lane wants the node opened
   auto visit = [&](int c) -> bool {
     const int fl = tv.flags[c];
     const double4 geo = tv.geo[c];
     double4 mom[NG];
-#pragma unroll
-    for(int g = 0; g < NG; g++)
-      mom[g] = tv.mom[(long long)c * NG + g];
+    node_moments<NG>(tv, c, mom);
     bool open = false;
-    const bool takes_part = lane_skip > sp;
+    const bool takes_part = w.takes_part();
     if(takes_part)
       {
-        double dx[NG], dy[NG], dz[NG], r2[NG];
-        double r2min = INFINITY, r2max = -INFINITY, summass = 0;
-#pragma unroll
-        for(int g = 0; g < NG; g++)
-          {
-            summass += mom[g].w;
-            dx[g] = mom[g].x - px;
-            dy[g] = mom[g].y - py;
-            dz[g] = mom[g].z - pz;
-            if(wp.periodic)
-              {
-                dx[g] = nearest(dx[g], wp.box, wp.boxhalf);
-                dy[g] = nearest(dy[g], wp.box, wp.boxhalf);
-                dz[g] = nearest(dz[g], wp.box, wp.boxhalf);
-              }
-            r2[g] = dx[g] * dx[g] + dy[g] * dy[g] + dz[g] * dz[g];
-            if(r2[g] < r2min)
-              r2min = r2[g];
-            if(r2[g] > r2max)
-              r2max = r2[g];
-          }
-        const double len = geo.w;
-        bool done = false;   // pruned
+        double dx[NG], dy[NG], dz[NG], r2[NG], r2min, r2max, summass;
+        species_offsets<NG>(mom, T, wp, wp.periodic, dx, dy, dz, r2, r2min, r2max, summass);
+        // pruned: the eff_dist box of forcetree.c:2990-3021 (no test on r2min in front of it), with the reach of the table, 6 Asmth,
+        // in the place of rcut = 4.5 Asmth: a cell outside it holds no pair with tab < NTAB, so nothing is lost.  The
+        // reference's box drops pairs between the two, each worth erfc(2.25) = 1.5e-3 of its m / r
+        bool done = false;
         if(PM)
           {
-            // the eff_dist box of forcetree.c:2990-3021 (no test on r2min in front of it), with the reach of the table, 6 Asmth,
-            // in the place of rcut = 4.5 Asmth: a cell outside it holds no pair with tab < NTAB, so nothing is lost.  The
-            // reference's box drops pairs between the two, each worth erfc(2.25) = 1.5e-3 of its m / r
-            const double eff = reach + 0.5 * len;
-            double d0 = geo.x - px, d1 = geo.y - py, d2 = geo.z - pz;
-            if(wp.periodic)
-              {
-                d0 = nearest(d0, wp.box, wp.boxhalf);
-                d1 = nearest(d1, wp.box, wp.boxhalf);
-                d2 = nearest(d2, wp.box, wp.boxhalf);
-              }
-            if(d0 < -eff || d0 > eff || d1 < -eff || d1 > eff || d2 < -eff || d2 > eff)
+            if(outside_reach_box(geo, T, wp, reach + 0.5 * geo.w))
               done = true;
           }
         if(!done)
-          {
-            if(wp.use_theta)
-              {
-                if(len * len > r2min * wp.theta2)                      // forcetree.c:2642-2650
-                  open = true;
-              }
-            else
-              {
-                if(summass * len * len > r2min * r2min * aold)         // forcetree.c:2653
-                  open = true;
-                else if(fabs(geo.x - px) < 0.60 * len && fabs(geo.y - py) < 0.60 * len &&
-                        fabs(geo.z - pz) < 0.60 * len)                 // forcetree.c:2660-2670 (no NEAREST)
-                  open = true;
-              }
-          }
+          open = node_opens(geo, T, wp, r2min, summass);
         if(!done && !open)
           {
             double h = hT;
@@ -286,63 +238,12 @@ __device__ __forceinline__ void potential_walk_lane(const TreeView &tv, const do
               }
           }
       }
-    const bool wave_open = __any(open ? 1 : 0) != 0;
-    if(wave_open && takes_part && !open)
-      lane_skip = sp + 1;   // the node goes onto the stack at depth sp + 1: this lane is done with everything below it
-    if(wave_open && (fl & FLAG_PSEUDO) && threadIdx.x % WAVE == 0)
-      atomicOr(err_flag, 4);   // a top leaf that was not imported (k_walk_strict reports the same)
+    const bool wave_open = w.settle(takes_part, open);
+    report_pseudo(wave_open, fl, err_flag);   // a top leaf that was not imported (k_walk_strict reports the same)
     return wave_open;
   };
-
-  // lock-step depth-first driver (kernels_walk.hip, strict_walk_lane)
-  if(visit(0))
-    {
-      sp = 0;
-      sn[0] = 0;
-      ss[0] = 0;
-    }
-  while(sp >= 0)
-    {
-      const int node = __builtin_amdgcn_readfirstlane(sn[sp]);
-      const int slot = __builtin_amdgcn_readfirstlane(ss[sp]);
-      const int fl = tv.flags[node];
-      if(fl & FLAG_BUCKET)
-        {
-          const int f = tv.first[node], cnt = tv.count[node];
-          if(slot >= cnt)
-            {
-              sp--;
-              if(lane_skip > sp && lane_skip >= 0)
-                lane_skip = NO_SKIP;
-              continue;
-            }
-          ss[sp] = slot + 1;
-          do_particle(f + slot);
-          continue;
-        }
-      if(slot >= 8)
-        {
-          sp--;
-          if(lane_skip > sp && lane_skip >= 0)
-            lane_skip = NO_SKIP;   // the walk has left the subtree this lane sat out
-          continue;
-        }
-      ss[sp] = slot + 1;
-      const int c = __builtin_amdgcn_readfirstlane(tv.child[8 * (long long)node + slot]);
-      if(c == -1)
-        continue;
-      if(c <= -2)
-        {
-          do_particle(-2 - c);
-          continue;
-        }
-      if(visit(c))
-        {
-          sp++;
-          sn[sp] = c;
-          ss[sp] = 0;
-        }
-    }
+  w.reset(valid);
+  w.run(tv, visit, do_particle);
   pot_out = pot;
   nint_out = nint;
 }
@@ -354,29 +255,15 @@ __global__ __launch_bounds__(256) void k_potential_walk(TreeView tv, const doubl
                                                         double utorwpi, double reach, long long n, double *__restrict__ r_pot, int *__restrict__ r_nint,
                                                         int *__restrict__ err_flag, PotUserArg<USR> pu)
 {
-  __shared__ int st_node[4][MAX_LEVELS + 2], st_slot[4][MAX_LEVELS + 2];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const long long grp = (long long)blockIdx.x * 4 + wave;
-  const long long ti = grp * WAVE + lane;
-  if(grp * WAVE >= n)
+  int *sn, *ss;
+  long long ti;
+  bool valid;
+  if(!strict_wave(n, sn, ss, ti, valid))
     return;
-  const bool valid = ti < n;
-  StrictTarget T = {0, 0, 0, 0, 0, 1.0, 0};
-  if(valid)
-    {
-      const double4 p = s_pm[ti];
-      T.x = p.x;
-      T.y = p.y;
-      T.z = p.z;
-      T.mass = p.w;
-      const int ptype = s_type[ti];
-      T.tg = wp.t2g[ptype];
-      T.h = wp.fsoft[ptype];
-      T.aold = wp.errtol_acc * s_oldacc[ti];
-    }
+  const StrictTarget T = own_target(s_pm, s_type, s_oldacc, wp, ti, valid);
   double pot;
   int nint;
-  potential_walk_lane<NG, PM, LATT, USR>(tv, s_pm, s_type, table, wp, utorwpi, reach, valid, T, st_node[wave], st_slot[wave], err_flag, pu, pot, nint);
+  potential_walk_lane<NG, PM, LATT, USR>(tv, s_pm, s_type, table, wp, utorwpi, reach, valid, T, sn, ss, err_flag, pu, pot, nint);
   if(valid)
     {
       r_pot[ti] = pot;
@@ -394,30 +281,15 @@ __global__ __launch_bounds__(256) void k_potential_targets(TreeView tv, const do
                                                            double *__restrict__ o_pot, int *__restrict__ o_nint, int *__restrict__ err_flag,
                                                            PotUserArg<USR> pu)
 {
-  __shared__ int st_node[4][MAX_LEVELS + 2], st_slot[4][MAX_LEVELS + 2];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const long long grp = (long long)blockIdx.x * 4 + wave;
-  const long long t = grp * WAVE + lane;
-  if(grp * WAVE >= nt)
+  int *sn, *ss;
+  long long t, me;
+  bool valid;
+  if(!strict_wave(nt, sn, ss, t, valid))
     return;
-  const bool valid = t < nt;
-  StrictTarget T = {0, 0, 0, 0, 0, 1.0, 0};
-  long long me = 0;
-  if(valid)
-    {
-      me = ord[t];
-      T.x = t_pos[3 * me];
-      T.y = t_pos[3 * me + 1];
-      T.z = t_pos[3 * me + 2];
-      T.mass = t_mass[me];
-      const int ptype = t_type[me];
-      T.tg = wp.t2g[ptype];
-      T.h = wp.fsoft[ptype];
-      T.aold = wp.errtol_acc * t_oldacc[me];
-    }
+  const StrictTarget T = record_target(t_pos, t_oldacc, t_mass, t_type, ord, wp, t, valid, me);
   double pot;
   int nint;
-  potential_walk_lane<NG, PM, LATT, USR>(tv, s_pm, s_type, table, wp, utorwpi, reach, valid, T, st_node[wave], st_slot[wave], err_flag, pu, pot, nint);
+  potential_walk_lane<NG, PM, LATT, USR>(tv, s_pm, s_type, table, wp, utorwpi, reach, valid, T, sn, ss, err_flag, pu, pot, nint);
   if(valid)
     {
       o_pot[me] = pot * G;
@@ -590,11 +462,7 @@ static int potential_walk_setup(ngravs_ctx *c, PotWalk *w, double far)
     return rc;
   if(latt && (rc = potential_lattice_ensure(c)))
     return rc;
-  // the largest r a pair can have: 6 Asmth, half a box diagonal, or the farthest target against the far corner of the domain
-  // (user_reach / lattice_reach / walk_targets_run of kernels_walk.hip, with their margin)
-  const double diag = sqrt(3.0) * c->dom[6];
-  if(usr && (rc = user_pot_tables_ensure(c, pm ? 1.25 * 6.0 * c->asmth : (latt ? 1.25 * 0.5 * sqrt(3.0) * c->cfg.box_size
-                                                                              : 1.25 * fmax(diag, far + 0.5 * diag)))))
+  if(usr && (rc = user_pot_tables_ensure(c, table_reach(c, true, far))))
     return rc;
   memset(&w->pu, 0, sizeof(w->pu));
   if(usr)
@@ -626,16 +494,14 @@ static int potential_walk_flag(ngravs_ctx *c, const PotWalk &w)
 template <int NG, int PM, int LATT, int USR>
 static int launch_potential(Row<NG, PM, LATT, USR>, ngravs_ctx *c, const PotWalk &w, long long n, int *d_nint)
 {
-  const long long ngroups = (n + WAVE - 1) / WAVE;
-  hipLaunchKernelGGL((k_potential_walk<NG, PM, LATT, USR>), dim3((unsigned)((ngroups + 3) / 4)), dim3(256), 0, c->stream, tree_view(c), c->s_pm.p,
+  hipLaunchKernelGGL((k_potential_walk<NG, PM, LATT, USR>), strict_grid(n), dim3(256), 0, c->stream, tree_view(c), c->s_pm.p,
                      c->s_type.p, c->s_oldacc.p, w.table, w.wp, w.utorwpi, w.reach, n, c->r_pot.p, d_nint, w.flag, pot_user_arg<USR>(w));
   return NGRAVS_OK;
 }
 template <int NG, int PM, int LATT, int USR>
 static int launch_potential_targets(Row<NG, PM, LATT, USR>, ngravs_ctx *c, const PotWalk &w, long long nt, const unsigned int *ord)
 {
-  const long long ngroups = (nt + WAVE - 1) / WAVE;
-  hipLaunchKernelGGL((k_potential_targets<NG, PM, LATT, USR>), dim3((unsigned)((ngroups + 3) / 4)), dim3(256), 0, c->stream, tree_view(c), c->s_pm.p,
+  hipLaunchKernelGGL((k_potential_targets<NG, PM, LATT, USR>), strict_grid(nt), dim3(256), 0, c->stream, tree_view(c), c->s_pm.p,
                      c->s_type.p, w.table, w.wp, w.utorwpi, w.reach, c->gt_in.p, c->gt_in.p + 3 * nt, c->gt_in.p + 4 * nt, c->gt_type.p, ord, nt, c->cfg.G,
                      c->gt_acc.p, c->gt_nint.p, w.flag, pot_user_arg<USR>(w));
   return NGRAVS_OK;

@@ -241,6 +241,19 @@ static int registry_tables_ensure(ngravs_ctx *c, const std::vector<ngravs_user_f
   return NGRAVS_OK;
 }
 
+double table_reach(const ngravs_ctx *c, bool shortrange, double far)
+{
+  if(shortrange && c->cfg.pmgrid)
+    return 1.25 * 6.0 * c->asmth;   // TreePM: r < NTAB / asmthfac = 6 Asmth (forcetree.c:1962-1967)
+  if(c->cfg.periodic)
+    return 1.25 * 0.5 * sqrt(3.0) * c->cfg.box_size;   // the nearest image is at most half a box diagonal away
+  // the diagonal of the domain cube (drifted particles of a refit tree may leave it a little; beyond the table's end the last
+  // octave's polynomial is used), or the farthest target, which may lie outside the cube, against the cube's far corner.
+  // (A mesh implies periodic boundaries, capi.hip refuses anything else: a direct sum never comes here with a mesh.  The
+  // association is the force walks'; the potential walk used to write 1.25 * (sqrt(3.0) * dom[6]), at most an ulp away.)
+  return fmax(1.25 * sqrt(3.0) * c->dom[6], 1.25 * (far + 0.5 * sqrt(3.0) * c->dom[6]));
+}
+
 int user_tables_ensure(ngravs_ctx *c, double r_need)
 {
   if(c->user_fns.empty() || !cfg_has_user(c->cfg))

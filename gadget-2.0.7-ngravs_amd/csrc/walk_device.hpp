@@ -1,5 +1,6 @@
-// walk_device.hpp -- device helpers shared by the walk kernels (kernels_walk.hip, kernels_eval.hip) and the one way their
-// launchers choose an instantiation (Row / Table / dispatch, at the end)
+// walk_device.hpp -- device helpers shared by the walk kernels (kernels_walk.hip, kernels_eval.hip, kernels_potential.hip): the
+// minimum-image wraps, exp(-x), wave-level votes and reductions; and the one way their launchers choose an instantiation (Row /
+// Table / dispatch, at the end).  The traversal of the strict-walk family is strict_walk.hpp
 #pragma once
 #include "engine.hpp"
 
@@ -42,15 +43,6 @@ __device__ __forceinline__ double exp_neg_fast(double x, const double *__restric
   pz = __builtin_fma(pz, y, 1.0);
   return ldexp(t * pz, -(mi >> 5));
 }
-
-// What the strict walk knows of its target (the reference's walk reads the same of P[target] or of GravDataGet[target],
-// forcetree.c:1284-1313 / :1668-1695): position, ErrTolForceAcc * OldAcc, the softening length of its type (ADA: its own), its mass
-// (read by the BAM laws alone) and its species
-struct StrictTarget
-{
-  double x, y, z, aold, h, mass;
-  int tg;
-};
 
 // wave-level "any lane": the condition's lane mask is compared on the scalar unit (no vector select / compare round trip)
 __device__ __forceinline__ bool wave_any(bool p) { return __builtin_amdgcn_ballot_w64(p) != 0ull; }
