@@ -213,14 +213,15 @@ extern "C" int ngravs_create_with_potentials(const ngravs_config_t *cfg, const n
   c->user_pot.assign(pots, pots + npot);
   user_pot_registry(c);
   memset(&c->stats, 0, sizeof(c->stats));
-  if(hipSetDevice(cfg->device) != hipSuccess || hipStreamCreate(&c->stream) != hipSuccess ||
-     hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess ||
-     hipEventCreate(&c->evk0) != hipSuccess || hipEventCreate(&c->evk1) != hipSuccess || hipEventCreate(&c->ev_fork) != hipSuccess ||
-     hipEventCreate(&c->ev_pm0) != hipSuccess || hipEventCreate(&c->ev_pm1) != hipSuccess || hipEventCreate(&c->ev_walk) != hipSuccess)
+  if(hipSetDevice(cfg->device) != hipSuccess || c->own_stream.create() != hipSuccess ||
+     c->ev0.create() != hipSuccess || c->ev1.create() != hipSuccess ||
+     c->evk0.create() != hipSuccess || c->evk1.create() != hipSuccess || c->ev_fork.create() != hipSuccess ||
+     c->ev_pm0.create() != hipSuccess || c->ev_pm1.create() != hipSuccess || c->ev_walk.create() != hipSuccess)
     {
       delete c;
       return NGRAVS_ERR_NO_DEVICE;
     }
+  c->stream = c->own_stream;
   if(cfg->pmgrid)
     {
       c->asmth = cfg_asmth(cfg);
@@ -236,137 +237,14 @@ extern "C" void ngravs_destroy(ngravs_ctx *c)
     return;
   (void)hipSetDevice(c->cfg.device);
   (void)hipStreamSynchronize(c->stream);
-  pm_release(c);
-  pmslab_release(c);
-  c->in_cost.release();
-  c->in_pos.release();
-  c->in_mass.release();
-  c->in_oldacc.release();
-  c->in_gsoft.release();
-  c->gsoft_stage.release();
-  c->s_soft.release();
-  c->n_maxsoft.release();
-  c->in_type.release();
-  c->in_active.release();
-  c->in_key.release();
-  c->in_rec.release();
-  c->in_id.release();
-  c->dd_mask.release();
-  c->dd_counts.release();
-  c->dd_send.release();
-  c->dd_recv.release();
-  c->top.child.release();
-  c->top.leaf.release();
-  c->top.gcnt.release();
-  c->top.info.release();
-  c->top.gsum.release();
-  c->top.leaf_owner.release();
-  c->top.reqmask.release();
-  c->top.leaf_sums.release();
-  ngravs_host_toptree_free(&c->top.h);
-  c->n_top.release();
-  c->s_pm.release();
-  c->s_type.release();
-  c->s_active.release();
-  c->s_oldacc.release();
-  c->s_key.release();
-  c->s_idx.release();
-  c->idx_iota.release();
-  c->sort_tmp.release();
-  c->red_tmp.release();
-  c->n_first.release();
-  c->n_count.release();
-  c->n_child.release();
-  c->n_flags.release();
-  c->n_head.release();
-  c->n_nchild.release();
-  c->n_geo.release();
-  c->n_mom.release();
-  c->n_npart.release();
-  c->user_tab.release();
-  c->upot_tab.release();
-  c->user_green.release();
-  c->scan_out.release();
-  c->tb_count.release();
-  c->scan_tmp.release();
-  c->d_counters.release();
-  c->d_levels.release();
-  c->table.release();
-  c->lat.release();
-  c->walk_stack.release();
-  c->walk_counters.release();
-  c->walk_ovf.release();
-  c->walk_tlist.release();
-  c->walk_tmp.release();
-  c->lvl_table.release();
-  c->r_acc.release();
-  c->r_pm.release();
-  c->r_oldacc.release();
-  c->r_nint.release();
-  c->pm_rho.release();
-  c->pm_phi.release();
-  c->pm_mesh_valid = false;
-  c->pm_force.release();
-  c->pm_orig.release();
-  c->out_tmp.release();
-  c->out_tmpf.release();
-  c->sph_vel_in.release();
-  c->sph_h_in.release();
-  c->sph_vel.release();
-  c->sph_tlist.release();
-  c->sph_tmp.release();
-  c->sph_res.release();
-  c->sph_row.release();
-  c->sph_rounds.release();
-  c->sph_counters.release();
-  c->sph_col_in.release();
-  c->sph_ts_in.release();
-  c->sph_hsrc.release();
-  c->sph_hmax.release();
-  c->sph_gas_in.release();
-  c->sph_ti_in.release();
-  c->sph_tpos.release();
-  c->sph_gmass.release();
-  c->sph_gcount.release();
-  c->sph_tg_in.release();
-  c->sph_tg_ts.release();
-  c->sph_tg_key.release();
-  c->sph_tg_ord.release();
-  c->sph_tg_res.release();
-  c->gt_in.release();
-  c->gt_type.release();
-  c->gt_key.release();
-  c->gt_ord.release();
-  c->gt_tmp.release();
-  c->gt_acc.release();
-  c->gt_nint.release();
-  c->gt_counters.release();
-  c->pot_table.release();
-  c->pot_lat.release();
-  c->r_pot.release();
-  (void)hipEventDestroy(c->ev0);
-  (void)hipEventDestroy(c->ev1);
-  (void)hipEventDestroy(c->evk0);
-  (void)hipEventDestroy(c->evk1);
-  for(hipEvent_t e : c->ev_batch)
-    (void)hipEventDestroy(e);
-  (void)hipEventDestroy(c->ev_fork);
-  (void)hipEventDestroy(c->ev_pm0);
-  (void)hipEventDestroy(c->ev_pm1);
-  (void)hipEventDestroy(c->ev_walk);
   if(c->pm_stream)
     {
       (void)hipStreamSynchronize(c->pm_stream);
       (void)hipStreamSynchronize(c->walk_stream);
-      (void)hipStreamDestroy(c->pm_stream);
-      (void)hipStreamDestroy(c->walk_stream);
     }
-  c->probe_out.release();
-  c->time_buf.release();
-  c->snap_order.release();
-  c->snap_tmp.release();
-  (void)hipStreamDestroy(c->stream);
-  delete c;
+  pm_release(c);       // the FFT plans: boxed handles, not owners
+  pmslab_release(c);
+  delete c;            // buffers and events, then the streams (declaration order in ngravs_ctx)
 }
 
 extern "C" void ngravs_set_fatal_handler(ngravs_ctx *ctx, ngravs_fatal_fn fn)
@@ -987,33 +865,29 @@ static int masked_streams(ngravs_ctx *c, int R)
     {
       HIP_TRY(c, hipStreamSynchronize(c->pm_stream));
       HIP_TRY(c, hipStreamSynchronize(c->walk_stream));
-      (void)hipStreamDestroy(c->pm_stream);
-      (void)hipStreamDestroy(c->walk_stream);
-      c->pm_stream = c->walk_stream = nullptr;
+      c->pm_stream.adopt(nullptr);
+      c->walk_stream.adopt(nullptr);
       c->pm_stream_cus = 0;
     }
   uint32_t mp[8] = {0}, mw[8] = {0};
   for(int b = 0; b < 256; b++)
     (pm_cu_bit(R, b) ? mp : mw)[b / 32] |= 1u << (b % 32);
-  hipStream_t sp = nullptr, sw = nullptr;
-  if(hipExtStreamCreateWithCUMask(&sp, 8, mp) != hipSuccess || hipExtStreamCreateWithCUMask(&sw, 8, mw) != hipSuccess)
-    {
-      if(sp)
-        (void)hipStreamDestroy(sp);
-      (void)hipGetLastError();
-      return NGRAVS_ERR_NO_DEVICE;
-    }
+  // local owners: the context gets the pair only when both exist and carry the masks asked for
+  DevStream sp, sw;
+  hipStream_t h = nullptr;
+  if(hipExtStreamCreateWithCUMask(&h, 8, mp) == hipSuccess)
+    sp.adopt(h);
+  if(sp && hipExtStreamCreateWithCUMask(&h, 8, mw) == hipSuccess)
+    sw.adopt(h);
   uint32_t gp[8] = {0}, gw[8] = {0};
-  if(hipExtStreamGetCUMask(sp, 8, gp) != hipSuccess || hipExtStreamGetCUMask(sw, 8, gw) != hipSuccess || memcmp(gp, mp, sizeof mp) ||
-     memcmp(gw, mw, sizeof mw))
+  if(!sp || !sw || hipExtStreamGetCUMask(sp, 8, gp) != hipSuccess || hipExtStreamGetCUMask(sw, 8, gw) != hipSuccess ||
+     memcmp(gp, mp, sizeof mp) || memcmp(gw, mw, sizeof mw))
     {
-      (void)hipStreamDestroy(sp);
-      (void)hipStreamDestroy(sw);
       (void)hipGetLastError();
       return NGRAVS_ERR_NO_DEVICE;
     }
-  c->pm_stream = sp;
-  c->walk_stream = sw;
+  c->pm_stream = std::move(sp);
+  c->walk_stream = std::move(sw);
   c->pm_stream_cus = R;
   return NGRAVS_OK;
 }
@@ -1521,8 +1395,6 @@ extern "C" int ngravs_peano_keys(ngravs_ctx *c, const double *pos, int64_t n, co
   if(!rc && hipMemcpyAsync(keys, dkeys.p, sizeof(long long) * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
     rc = NGRAVS_ERR_NO_DEVICE;
   (void)hipStreamSynchronize(c->stream);
-  dpos.release();
-  dkeys.release();
   return rc;
 }
 
@@ -1570,10 +1442,6 @@ extern "C" int ngravs_direct_sum(ngravs_ctx *c, const int32_t *idx, int64_t nt, 
   if(!rc && hipMemcpyAsync(acc, dacc.p, sizeof(double) * 3 * nt, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
     rc = NGRAVS_ERR_NO_DEVICE;
   (void)hipStreamSynchronize(c->stream);
-  inv.release();
-  din.release();
-  dout.release();
-  dacc.release();
   return rc;
 }
 
@@ -1616,9 +1484,6 @@ extern "C" int ngravs_direct_sum_targets(ngravs_ctx *c, const double *pos, const
   if(!rc && hipMemcpyAsync(acc, dacc.p, sizeof(double) * 3 * nt, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
     rc = NGRAVS_ERR_NO_DEVICE;
   (void)hipStreamSynchronize(c->stream);
-  dt.release();
-  dty.release();
-  dacc.release();
   return rc;
 }
 

@@ -18,6 +18,7 @@
 #include <utility>
 #include <vector>
 #include "../../include/ngravs_host.h"
+#include "devbuf.hpp"
 
 #define NG_MAX NGRAVS_MAX_GRAVS
 #define NTAB NGRAVS_NTAB
@@ -49,33 +50,6 @@ struct ngravs_ctx;
   while(0)
 
 void ngravs_report(ngravs_ctx *ctx, int code, const std::string &msg);
-
-template <typename T> struct DevBuf
-{
-  T *p = nullptr;
-  size_t cap = 0;
-  int ensure(size_t n)
-  {
-    if(n <= cap)
-      return 0;
-    if(p)
-      (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    size_t want = n + n / 16 + 64;
-    if(hipMalloc((void **)&p, want * sizeof(T)) != hipSuccess)
-      return -1;
-    cap = want;
-    return 0;
-  }
-  void release()
-  {
-    if(p)
-      (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-};
 
 // User-defined laws (ngravs_create_with_laws; user_laws.cpp builds the tables, DESIGN.md "User-defined force laws").
 // Every table is a run of sub-intervals with a degree-7 polynomial in t in [-1, 1] each (UL_NC coefficients, Horner order
@@ -240,6 +214,7 @@ struct TopTree
   long long kept_total = -1;
   DevBuf<double> kept_sums;            // per leaf: TOP_CW + 1 doubles (the last one: the grown side of the leaf's cell, from its owner) + 1 status word
   DevBuf<double> leaf_len;             // per leaf: grown side of its cell (all tasks' maximum), for the pseudo nodes of a refit
+  ~TopTree() { ngravs_host_toptree_free(&h); }
 };
 
 // slab-decomposed particle mesh of the multi-task path (kernels_pmslab.hip)
@@ -265,6 +240,10 @@ struct ngravs_ctx
 {
   ngravs_config_t cfg;
   Tuning tune;
+  // Members are destroyed in reverse order of declaration: the streams stand before every buffer and event, so that these go
+  // first and the streams last.  own_stream: the stream ngravs_create* made (`stream` is a plain handle, OnStream reassigns it);
+  // pm_stream / walk_stream: PM beside the walk (ngravs_compute_accelerations), masked to disjoint sets of CUs
+  DevStream own_stream, pm_stream, walk_stream;
   PmSlab pms;
   TopTree top;
   DevBuf<int> n_top;          // top-tree node a tree node is (multi-task trees; -1: none)
@@ -357,8 +336,8 @@ struct ngravs_ctx
   DevBuf<float> out_tmpf;
   std::vector<unsigned char> host_stage;
   ngravs_stats_t stats;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr, evk0 = nullptr, evk1 = nullptr;
-  std::vector<hipEvent_t> ev_batch;   // split walk: 3 events per batch (before traversal, between, after evaluation)
+  DevEvent ev0, ev1, evk0, evk1;
+  std::vector<DevEvent> ev_batch;   // split walk: 3 events per batch (before traversal, between, after evaluation)
   int walk_batches = 0;               // batches of the last split walk (0: fused kernel)
   int walk_lcap = 0;                  // split walk: item-list capacity per group and species (grown on overflow)
   int walk_scap = 0;                  // split walk: LIFO capacity per group (grown on overflow)
@@ -384,8 +363,7 @@ struct ngravs_ctx
   DevBuf<double> gsoft_stage; // the next column while ngravs_set_gas_softening checks it
   DevBuf<double> s_soft;      // TreeView::soft
   DevBuf<double> n_maxsoft;   // TreeView::maxsoft
-  // PM beside the walk (ngravs_compute_accelerations): two streams masked to disjoint sets of CUs
-  hipStream_t pm_stream = nullptr, walk_stream = nullptr;
+  // PM beside the walk: pm_stream and walk_stream (above)
   int pm_stream_cus = 0;      // CUs of pm_stream's mask (0: no masked streams); walk_stream has the device's other CUs
   int device_cus = 0;         // CUs of the device
   int stream_cus = 0;         // CUs the launches on c->stream may use (0: the whole device); set by OnStream
@@ -393,7 +371,7 @@ struct ngravs_ctx
   double pm_solo_ms = 0, walk_solo_ms = 0;   // PM and walk spans of the last serial PM step of the particle set ...
   int pm_solo_steps = 0;      // ... of this many
   int pm_auto_cus = -1;       // the CUs chosen from them (-1: not yet)
-  hipEvent_t ev_fork = nullptr, ev_pm0 = nullptr, ev_pm1 = nullptr, ev_walk = nullptr;
+  DevEvent ev_fork, ev_pm0, ev_pm1, ev_walk;
   DevBuf<int> probe_out;      // ngravs_cu_probe
   DevBuf<double> user_green;  // PM: user Green's functions G(k2) at the integer k2 (GreenParams::ug); empty without a user greens id
   long long user_green_nk2 = 0;

@@ -693,8 +693,7 @@ template <typename T> static int grow_keep(ngravs_ctx *c, DevBuf<T> &b, size_t k
     if(hipMemcpyAsync(nb.p, b.p, keep * sizeof(T), hipMemcpyDeviceToDevice, c->stream) != hipSuccess)
       return -1;
   (void)hipStreamSynchronize(c->stream);
-  b.release();
-  b = nb;
+  b = std::move(nb);
   return 0;
 }
 
@@ -933,7 +932,6 @@ int dd_get_dest(ngravs_ctx *c, const int *leaf_owner, int *dest)
                      fac21, t.child.p, t.leaf.p, t.leaf_owner.p, (const unsigned long long *)nullptr, 0, (unsigned long long *)nullptr, d.p);
   HIP_TRY(c, hipMemcpyAsync(dest, d.p, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  d.release();
   return NGRAVS_OK;
 }
 
@@ -1154,25 +1152,15 @@ int dd_apply_migration(ngravs_ctx *c, const void *dev_records, int64_t nrec)
                        with_pm ? pm2.p : (double *)nullptr);
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   HIP_TRY(c, hipGetLastError());
-  c->in_pos.release();
-  c->in_mass.release();
-  c->in_oldacc.release();
-  c->in_type.release();
-  c->in_active.release();
-  c->in_id.release();
-  c->in_cost.release();
-  c->in_cost = cost2;
+  c->in_cost = std::move(cost2);
   if(with_pm)
-    {
-      c->pm_orig.release();
-      c->pm_orig = pm2;   // pm_parked stays as it was: zeros are not a PM force
-    }
-  c->in_pos = pos2;
-  c->in_mass = mass2;
-  c->in_oldacc = old2;
-  c->in_type = type2;
-  c->in_active = act2;
-  c->in_id = id2;
+    c->pm_orig = std::move(pm2);   // pm_parked stays as it was: zeros are not a PM force
+  c->in_pos = std::move(pos2);
+  c->in_mass = std::move(mass2);
+  c->in_oldacc = std::move(old2);
+  c->in_type = std::move(type2);
+  c->in_active = std::move(act2);
+  c->in_id = std::move(id2);
   c->n_local = (int64_t)kept + nrec;
   c->n = c->n_local;
   c->own_order_nlocal = -1;   // rows moved: the old order no longer names them
@@ -1254,23 +1242,21 @@ int dd_peano_order_own(ngravs_ctx *c, int force)
   const bool with_pm = c->pm_parked && c->pm_orig.p;
   if(pos2.ensure(3 * cap) || mass2.ensure(cap) || old2.ensure(cap) || type2.ensure(cap) || act2.ensure(cap) || id2.ensure(cap) ||
      cost2.ensure(cap) || (with_pm && pm2.ensure(3 * cap)))
-    {
-      pos2.release(), mass2.release(), old2.release(), type2.release(), act2.release(), id2.release(), cost2.release(), pm2.release();
-      return NGRAVS_ERR_NOMEM;
-    }
+    return NGRAVS_ERR_NOMEM;
   hipLaunchKernelGGL(k_dd_reorder, dim3((unsigned)((nl + 255) / 256)), dim3(256), 0, c->stream, c->idx_iota.p, nl, c->in_pos.p, c->in_mass.p,
                      c->in_type.p, c->in_oldacc.p, c->in_active.p, c->in_id.p, c->in_cost.p, with_pm ? c->pm_orig.p : (const double *)nullptr,
                      pos2.p, mass2.p, type2.p, old2.p, act2.p, id2.p, cost2.p, with_pm ? pm2.p : (double *)nullptr);
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   HIP_TRY(c, hipGetLastError());
-  c->in_pos.release(), c->in_mass.release(), c->in_oldacc.release(), c->in_type.release(), c->in_active.release(), c->in_id.release(),
-      c->in_cost.release();
-  c->in_pos = pos2, c->in_mass = mass2, c->in_oldacc = old2, c->in_type = type2, c->in_active = act2, c->in_id = id2, c->in_cost = cost2;
+  c->in_pos = std::move(pos2);
+  c->in_mass = std::move(mass2);
+  c->in_oldacc = std::move(old2);
+  c->in_type = std::move(type2);
+  c->in_active = std::move(act2);
+  c->in_id = std::move(id2);
+  c->in_cost = std::move(cost2);
   if(with_pm)
-    {
-      c->pm_orig.release();
-      c->pm_orig = pm2;
-    }
+    c->pm_orig = std::move(pm2);
   c->n = nl;                  // the imported copies of the last step are gone with the order that named them
   c->own_order_nlocal = -1;   // the rows ARE in that order now
   c->have_order = c->have_tree = c->have_acc = false;

@@ -408,14 +408,6 @@ void pmslab_release(ngravs_ctx *c)
   destroy_plan(s.plan2i);
   destroy_plan(s.plan1);
   s.plan_N = s.plan_nx = s.plan_ny = 0;
-  s.brick.release();
-  s.slab.release();
-  s.tbuf.release();
-  s.ebrick.release();
-  s.fmesh.release();
-  s.send.release();
-  s.recv.release();
-  s.desc.release();
 }
 
 static int ensure_plans(ngravs_ctx *c)

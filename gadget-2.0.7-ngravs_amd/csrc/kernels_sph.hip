@@ -1452,9 +1452,10 @@ int sph_density_update_device(long long n, const double *sums, double *h, double
                               double minh, int *accepted, double *const out[SPH_NRES], long long *failed)
 {
   *failed = 0;
-  unsigned long long *d_failed = nullptr;
-  if(hipMalloc(&d_failed, sizeof(unsigned long long)) != hipSuccess)
+  DevBuf<unsigned long long> failed_buf;
+  if(failed_buf.ensure(1))
     return NGRAVS_ERR_NOMEM;
+  unsigned long long *d_failed = failed_buf.p;
   SphScatterCols cols = {};
   for(int k = 0; k < SPH_NRES; k++)
     cols.dst[k] = reinterpret_cast<unsigned char *>(out[k]);
@@ -1468,7 +1469,6 @@ int sph_density_update_device(long long n, const double *sums, double *h, double
     }
   if(e == hipSuccess)
     e = hipMemcpy(&f, d_failed, sizeof(f), hipMemcpyDeviceToHost);   // (waits for the kernel)
-  (void)hipFree(d_failed);
   if(e != hipSuccess)
     return NGRAVS_ERR_NO_DEVICE;
   *failed = (long long)f;

@@ -2801,9 +2801,9 @@ static int launch_group3_t(Row<NG, PM, YUK, TAB_LDS, LATT, USR, ADA>, ngravs_ctx
   const size_t nbatches = (size_t)((nunits + batch - 1) / batch);
   while(c->ev_batch.size() < 3 * nbatches)
     {
-      hipEvent_t e;
-      HIP_TRY(c, hipEventCreate(&e));
-      c->ev_batch.push_back(e);
+      DevEvent e;
+      HIP_TRY(c, e.create());
+      c->ev_batch.push_back(std::move(e));
     }
   c->walk_batches = (int)nbatches;
   size_t ib = 0;
