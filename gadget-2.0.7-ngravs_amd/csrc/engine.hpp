@@ -10,6 +10,7 @@
 //   results, Peano order          : r_acc[3n] r_nint[n] r_pm[3n] r_oldacc[n]
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cstddef>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -167,6 +168,32 @@ struct TreeView
   const double *maxsoft;   // per node: the largest of them below it (0: empty node)
 };
 
+// The counters of a walk (ngravs_ctx::walk_counters): cleared in front of a walk, bumped by its kernels, read by the host after it
+struct WalkCounters
+{
+  int reserved0;
+  int err;               // error flag of the walk kernels: 1 a list overflowed, 2 the LIFO, 4 a top leaf that was not imported
+  int overflowed;        // split walk: groups in walk_ovf (their lists or LIFO outgrew their region) ...
+  int overflowed_lifo;   // ... of them by the LIFO
+  int unopened;          // top leaves the walk wanted opened but had to use as monopoles
+  int reserved1[3];
+  int xcd_next[8];       // the next group of each XCD's segment (the persistent kernels' group assignment; cleared between batches)
+  unsigned long long stats[4];   // pool entries, nodes tested, traversal batches, force-loop slots per lane: sums over the groups
+  int ntargets;          // length of the compacted target list (walk_tlist)
+  int reserved2;
+  unsigned long long head[2];    // node head: nodes opened without their moments, nodes that passed its test
+  int reserved3[2];
+};
+static_assert(sizeof(WalkCounters) == 32 * sizeof(int), "WalkCounters: 32 ints");
+static_assert(offsetof(WalkCounters, err) == 4 && offsetof(WalkCounters, overflowed) == 8 && offsetof(WalkCounters, overflowed_lifo) == 12 &&
+                  offsetof(WalkCounters, unopened) == 16 && offsetof(WalkCounters, xcd_next) == 32 && offsetof(WalkCounters, stats) == 64 &&
+                  offsetof(WalkCounters, ntargets) == 96 && offsetof(WalkCounters, head) == 104,
+              "WalkCounters: the layout the kernels and the host agree on");
+
+// LDS of the group walk's evaluating kernels: what a workgroup may use, and the block every one of them keeps behind its tables
+#define WALK_LDS_BUDGET ((size_t)160 * 1024)
+#define WALK_LDS_CONST (40 * sizeof(double))   // exp table (32 entries) + softening length per particle type (8)
+
 // ngravs_set_tuning(): performance / test parameters, set explicitly by the host (no environment variables)
 struct Tuning
 {
@@ -321,7 +348,7 @@ struct ngravs_ctx
                               // (0: no such walk yet): > 1 in clustered sets, where smaller traversal units accept more cells
   bool all_active = true;     // the caller passed no active flags
   DevBuf<int> walk_ovf;       // split walk: groups left to the fused kernel (lists or LIFO outgrew their region)
-  DevBuf<int> walk_counters;  // [1] overflow flag, [2] groups in walk_ovf, [3] of them by the LIFO, [8..15] per-XCD group counters, [16..23] 64-bit walk statistics, [26..29] 64-bit node-head statistics
+  DevBuf<WalkCounters> walk_counters;   // one: what each field is stands with the struct
   DevBuf<double> r_acc, r_pm, r_oldacc;
   DevBuf<int> r_nint;
   // pm
@@ -538,6 +565,10 @@ int walk_run(ngravs_ctx *c);        // walk_enqueue + walk_complete
 int walk_enqueue(ngravs_ctx *c);
 int walk_complete(ngravs_ctx *c);
 int walk_finish(ngravs_ctx *c);
+// hipFuncAttributeMaxDynamicSharedMemorySize of a walk kernel: set when the kernel is first launched with this size, not on every
+// step (the call takes the runtime's locks in front of the step's first walk launch).  The record is this engine's, the attribute the
+// process's: two live engines that launch one kernel with different sizes (walk_ring_k 4 and the default, say) must not share a process
+int walk_dyn_lds(ngravs_ctx *c, const void *kern, size_t lds);
 int direct_run(ngravs_ctx *c, const int *d_idx, int64_t nt, double *d_acc);
 int direct_run_targets(ngravs_ctx *c, const double4 *d_tpm, const int *d_ttype, int64_t nt, double *d_acc, double far = 0);   // far: as table_reach
 // adaptive softening: s_soft from in_gsoft and the order, n_maxsoft bottom-up from the tree (nodes: also the node column), each

@@ -31,7 +31,7 @@
 // lowered to coefficients  a(r) = m [ cN/r^2 + cY exp(-r ym)(ym/r + 1/r^2) ]  (none, newtonian,
 // neg_newtonian, yukawa, coloyuk) and kernels are compiled per N_GRAVS and per "has Yukawa".
 #include "engine.hpp"
-#include "walk_device.hpp"
+#include "group_frame.hpp"
 #include "strict_walk.hpp"
 #include "eval_asm.inc"   // ER_DIRECT_ASM: the tree-only force loop (the other blocks belong to kernels_eval.hip)
 #include <hipcub/hipcub.hpp>
@@ -580,8 +580,8 @@ template <int NG, bool PM, bool YUK, bool TAB_LDS, bool LATT, int MODE, bool USR
 __global__ __launch_bounds__(MODE == 1 ? GW3_TBLOCK : (MODE == 2 ? GW2_MAXWAVES : GW_MAXWAVES) * 64) void k_walk_group2(
     TreeView tv, const double4 *__restrict__ s_pm, const unsigned char *__restrict__ s_type,
     const double *__restrict__ s_oldacc, const unsigned char *__restrict__ s_active,
-    const double *__restrict__ table, WalkParams wp, long long t_first, long long t_count, int *__restrict__ counter,
-    int *__restrict__ stack_base, int *__restrict__ err_flag, double *__restrict__ r_acc, int *__restrict__ r_nint,
+    const double *__restrict__ table, WalkParams wp, long long t_first, long long t_count,
+    WalkCounters *__restrict__ counter, int *__restrict__ stack_base, int *__restrict__ err_flag, double *__restrict__ r_acc, int *__restrict__ r_nint,
     int *__restrict__ region_base, int *__restrict__ gcount, long long g_first, long long g_cnt, int lcap, int scap,
     int *__restrict__ glist, int S, int G0, const int *__restrict__ tlist, int SG)
 {
@@ -599,7 +599,7 @@ __global__ __launch_bounds__(MODE == 1 ? GW3_TBLOCK : (MODE == 2 ? GW2_MAXWAVES 
   const size_t tab_bytes = (PM && TAB_LDS) ? sizeof(double) * ntabs * NTAB : 0;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   double *expT = reinterpret_cast<double *>(smem + tab_bytes);
-  unsigned char *wbase = smem + tab_bytes + 40 * sizeof(double) + (size_t)wave * (ADA ? GW2_WAVE_LDS_ADA : GW2_WAVE_LDS);
+  unsigned char *wbase = smem + tab_bytes + WALK_LDS_CONST + (size_t)wave * (ADA ? GW2_WAVE_LDS_ADA : GW2_WAVE_LDS);
   double *fsT = expT + 32;   // softening length per particle type (8 entries; index 7 = empty node)
   double4 *lpos = reinterpret_cast<double4 *>(wbase) + 1;   // lpos[-1]: the NULL entry
   float *lfx = reinterpret_cast<float *>(wbase + sizeof(double4) * (2 * WAVE + 1));
@@ -655,8 +655,8 @@ __global__ __launch_bounds__(MODE == 1 ? GW3_TBLOCK : (MODE == 2 ? GW2_MAXWAVES 
   // of a target split the pool entries among them (entry j goes to lane j mod S), so all 64 lanes keep evaluating; their
   // partial sums are added at the end.  S = 64 is one target per wave: the box is the target itself and every group test
   // the reference's own per-target test.
-  // glist: MODE 1 appends the groups whose lists or LIFO outgrew their region (counter[2] = how many, counter[3] = how many
-  // of them by the LIFO); MODE 0 with a glist walks exactly those groups (of G0 targets each) again in sub-groups of G.
+  // glist: MODE 1 appends the groups whose lists or LIFO outgrew their region (counter->overflowed, ->overflowed_lifo);
+  // MODE 0 with a glist walks exactly those groups (of G0 targets each) again in sub-groups of G.
   const int G = WAVE / S;
   const long long ngroups = (MODE == 0 && !glist) ? (t_count + G - 1) / G : (MODE == 0 ? g_cnt * (G0 / G) : g_cnt);
   unsigned long long lane_pat = ~0ull;   // the pool entries this lane evaluates
@@ -685,12 +685,7 @@ __global__ __launch_bounds__(MODE == 1 ? GW3_TBLOCK : (MODE == 2 ? GW2_MAXWAVES 
       usoft = false;
     }
 
-  // XCD-aware group assignment: the Peano order is cut into 8 contiguous segments, one per XCD (own L2), and a
-  // workgroup pulls groups from the segment of the XCD it runs on (neighbouring groups share most of their
-  // tree nodes and sources); an exhausted segment steals from the others.  Placement only affects speed.
-  unsigned xcc = 0;
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-  xcc &= 7u;
+  const unsigned xcc = group_xcc();   // the persistent kernels' group assignment
   const long long seg = (ngroups + 7) / 8;
   int steal = 0;
   bool t_done = false;
@@ -721,7 +716,7 @@ __global__ __launch_bounds__(MODE == 1 ? GW3_TBLOCK : (MODE == 2 ? GW2_MAXWAVES 
           const int sx = (int)((xcc + steal) & 7u);
           int k = 0;
           if(lane == 0)
-            k = atomicAdd(&counter[8 + sx], 1);
+            k = atomicAdd(&counter->xcd_next[sx], 1);
           k = __builtin_amdgcn_readfirstlane(k);
           const long long g0 = seg * sx + k;
           if(k < seg && g0 < ngroups)
@@ -751,10 +746,10 @@ __global__ __launch_bounds__(MODE == 1 ? GW3_TBLOCK : (MODE == 2 ? GW2_MAXWAVES 
           stack = base + (size_t)NG * lcap;
         }
       grp += gbase;
-      // targets: the shard's Peano-ordered particles, or (individual timesteps: few active particles) the compacted list of
-      // its active ones, so that a wave works for 64 active targets instead of the few a 64-particle stretch contains
       const int nsub = MODE == 1 ? SG : 1;
       const long long tk = (tk_base >= 0 ? tk_base : grp * G * nsub) + lane / S;
+      // targets: the shard's Peano-ordered particles, or (individual timesteps: few active particles) the compacted list of
+      // its active ones, so that a wave works for 64 active targets instead of the few a 64-particle stretch contains
       const bool in_range = tk < t_count;
       const long long ti = tlist ? (in_range ? (long long)tlist[tk] : 0ll) : t_first + tk;
       const bool valid = in_range && (tlist != nullptr || (s_active[ti] & 1) != 0);
@@ -822,52 +817,22 @@ __global__ __launch_bounds__(MODE == 1 ? GW3_TBLOCK : (MODE == 2 ? GW2_MAXWAVES 
       const double *trow = tabp;
       const double *const etab = (PM && TAB_LDS) ? tab_s + (size_t)wp.ntab_lds * NTAB : table + (size_t)NG * NG * NTAB;
       // group bounding box and the conservative scalars
-      double lox = wave_min(mnx), hix = wave_max(mxx);
-      double loy = wave_min(mny), hiy = wave_max(mxy);
-      double loz = wave_min(mnz), hiz = wave_max(mxz);
-      const double bcx = wave_uniform(0.5 * (lox + hix)), bcy = wave_uniform(0.5 * (loy + hiy)), bcz = wave_uniform(0.5 * (loz + hiz));
-      const double bhx = wave_uniform(0.5 * (hix - lox)), bhy = wave_uniform(0.5 * (hiy - loy)), bhz = wave_uniform(0.5 * (hiz - loz));
+      const GroupBox box = group_box(mnx, mxx, mny, mxy, mnz, mxz);
+      const double bcx = box.cx, bcy = box.cy, bcz = box.cz, bhx = box.hx, bhy = box.hy, bhz = box.hz;
       const double aold_min = wave_min(mna);
       const double hT_min = wave_min(mnh);
       // may sources be wrapped once per group (relative to the box centre) instead of per pair?
-      const double bhmax = fmax(bhx, fmax(bhy, bhz));
-      // (wave-uniform by construction; read through an SGPR so that the branches on them are scalar branches)
-      const bool prewrap = __builtin_amdgcn_readfirstlane(
-                               (int)(wp.periodic && PM && (wp.boxhalf - bhmax) * (wp.boxhalf - bhmax) > wp.reach2 &&
-                                     (wp.boxhalf - bhmax) > 0)) != 0;
+      const bool prewrap = group_prewrap<PM>(wp.periodic, wp.boxhalf, wp.reach2, box.hmax());
       const bool lanewrap = wp.periodic && !prewrap;
       // A pre-wrapped pool holds positions RELATIVE to the box centre (what the cull computes anyway; adding the centre back
       // would cost 9 VALU per item and round once more), so the force loop subtracts the target's relative position.
       const double tpx = prewrap ? px - bcx : px, tpy = prewrap ? py - bcy : py, tpz = prewrap ? pz - bcz : pz;
-      // (1) A group whose whole region [box - reach, box + reach] lies inside the periodic box needs no image arithmetic
-      // at all: with every source inside [0, L] (wp.src_in_box) a plain difference IS the nearest-image difference for
-      // everything within reach, and everything else fails the cull either way.
-      bool nowrap = !wp.periodic;
-      if(PM && wp.periodic && wp.src_in_box)
-        {
-          const double rl_ = __builtin_sqrt(wp.reach2);
-          nowrap = __builtin_amdgcn_readfirstlane((int)(bcx - bhx - rl_ >= 0.0 && bcx + bhx + rl_ <= wp.box && bcy - bhy - rl_ >= 0.0 &&
-                                                        bcy + bhy + rl_ <= wp.box && bcz - bhz - rl_ >= 0.0 &&
-                                                        bcz + bhz + rl_ <= wp.box)) != 0;
-        }
-      // packed-fp32 reach pre-test (PM, no per-pair wrapping): positions relative to the box centre in fp32, threshold
-      // widened by the worst-case rounding so that no true hit is lost; the force loop re-tests in fp64 (in[k])
+      const bool nowrap = group_nowrap<PM>(wp.periodic, wp.src_in_box, wp.box, wp.reach2, box);   // or not at all?
+      // packed-fp32 reach pre-test (PM, no per-pair wrapping; constants and rounding bound: reach_pretest), |e|^2 stored per
+      // pool entry; the force loop re-tests in fp64 (in[k])
       typedef float f16v __attribute__((ext_vector_type(16)));
       const bool fastmask = PM && !lanewrap;
-      // r2 - thr = |e|^2 - 2 e.p + |p|^2 - thr with |e|^2 stored per pool entry: three packed FMAs per two entries.
-      // Rounding: e and p are fp32 roundings of coordinates relative to the box centre (each component <= bhmax + reach), so
-      // the true r2 moves by <= 4 rl dl; the evaluation itself makes <= 8 roundings of magnitudes <= M = 3 (2 bhmax + rl)^2.
-      const float tfx = (float)(px - bcx), tfy = (float)(py - bcy), tfz = (float)(pz - bcz);
-      const float m2x = -2.0f * tfx, m2y = -2.0f * tfy, m2z = -2.0f * tfz;
-      float cth;
-      {
-        const double rl = __builtin_sqrt(wp.reach2);
-        const double dl = 4.76837158203125e-07 * (bhmax + rl);   // 2^-21 x the largest relative coordinate
-        const double M = 3.0 * (2.0 * bhmax + rl) * (2.0 * bhmax + rl);
-        const double thr = (wp.reach2 + 4.0 * rl * dl + 1.0e-6 * M) * (1.0 + 2e-6);
-        cth = (float)((double)tfx * tfx + (double)tfy * tfy + (double)tfz * tfz - thr);
-        cth = cth - 1.2e-7f * __builtin_fabsf(cth);   // the cast may have rounded up: one ulp down
-      }
+      const float4 rp = reach_pretest(px - bcx, py - bcy, pz - bcz, box.hmax(), wp.reach2);
       // The masks are a 64 x 64 x 4 matrix product on the matrix cores (v_mfma_f32_32x32x2_f32, exact f32):
       //   D[entry][target] = |e|^2  +  (ex, ey, ez, 1) . (-2 tx, -2 ty, -2 tz, |t|^2 - thr),   hit <=> D < 0.
       // Rows are pool entries, columns targets, one 32 x 32 tile per (entry block, target block), K = 4 as two instructions.
@@ -879,7 +844,7 @@ __global__ __launch_bounds__(MODE == 1 ? GW3_TBLOCK : (MODE == 2 ? GW2_MAXWAVES 
       for(int tb = 0; tb < 2; tb++)
         {
           const int src = 32 * tb + (lane & 31);
-          const float x_ = __shfl(m2x, src), y_ = __shfl(m2y, src), z_ = __shfl(m2z, src), c_ = __shfl(cth, src);
+          const float x_ = __shfl(rp.x, src), y_ = __shfl(rp.y, src), z_ = __shfl(rp.z, src), c_ = __shfl(rp.w, src);
           mB[tb][0] = mh ? y_ : x_;
           mB[tb][1] = mh ? c_ : z_;
         }
@@ -1810,7 +1775,7 @@ __global__ __launch_bounds__(MODE == 1 ? GW3_TBLOCK : (MODE == 2 ? GW2_MAXWAVES 
           {
             const unsigned long long ph_ = __ballot(pseudo_hit ? 1 : 0);
             if(ph_ != 0ull && lane == 0)
-              atomicAdd(&counter[4], __popcll(ph_));
+              atomicAdd(&counter->unopened, __popcll(ph_));
           }
           if(dec == 2)
             {
@@ -1978,11 +1943,10 @@ __global__ __launch_bounds__(MODE == 1 ? GW3_TBLOCK : (MODE == 2 ? GW2_MAXWAVES 
           if constexpr(MODE == 1)
             {
               // one wave of the traversal kernel walks one unit: one pair of atomics per unit, and nothing waits for them
-              unsigned long long *hd64 = reinterpret_cast<unsigned long long *>(counter + 26);
               if(lane == 0 && hs != 0ull)
                 {
-                  atomicAdd(&hd64[0], hs >> 32);
-                  atomicAdd(&hd64[1], hs & 0xffffffffull);
+                  atomicAdd(&counter->head[0], hs >> 32);
+                  atomicAdd(&counter->head[1], hs & 0xffffffffull);
                 }
             }
           else
@@ -2010,16 +1974,9 @@ __global__ __launch_bounds__(MODE == 1 ? GW3_TBLOCK : (MODE == 2 ? GW2_MAXWAVES 
         }
       else
         {
-          if(MODE == 2 && (grp - gbase) % SG == 0)   // the unit's traversal statistics, once
-            {
-              const long long u_cnt = (g_cnt + SG - 1) / SG;
-              st_nodes = __builtin_amdgcn_readfirstlane(gcount[NG * u_cnt + ru]);          // wave-uniform: keep the statistics in SGPRs
-              st_batches = __builtin_amdgcn_readfirstlane(gcount[(NG + 1) * u_cnt + ru]);
-            }
-          acc_st[0] += (unsigned long long)st_entries;
-          acc_st[1] += (unsigned long long)st_nodes;
-          acc_st[2] += (unsigned long long)st_batches;
-          acc_st[3] += (unsigned long long)st_iters;
+          if(MODE == 2)
+            unit_stats<NG>(gcount, grp - gbase, g_cnt, SG, ru, st_nodes, st_batches);
+          walk_stats_add(acc_st, st_entries, st_nodes, st_batches, st_iters);
         }
       if(overflow)
         {
@@ -2027,46 +1984,29 @@ __global__ __launch_bounds__(MODE == 1 ? GW3_TBLOCK : (MODE == 2 ? GW2_MAXWAVES 
             {
               if(MODE == 1)
                 {
-                  glist[atomicAdd(&counter[2], 1)] = (int)grp;   // finished by the fused kernel in the same step
+                  glist[atomicAdd(&counter->overflowed, 1)] = (int)grp;   // finished by the fused kernel in the same step
                   if(stk_overflow)
-                    atomicAdd(&counter[3], 1);
+                    atomicAdd(&counter->overflowed_lifo, 1);
                 }
               else
                 atomicOr(err_flag, stk_overflow ? 2 : 1);
             }
           continue;
         }
-      if(MODE != 1 && S > 1)
-        {
-          for(int off = 1; off < S; off <<= 1)   // the S lanes of a target hold partial sums
-            {
-              ax += __shfl_xor(ax, off);
-              ay += __shfl_xor(ay, off);
-              az += __shfl_xor(az, off);
-              nint += __shfl_xor(nint, off);
-            }
-        }
-      if(MODE != 1 && valid && (lane & (S - 1)) == 0)
-        {
-          r_acc[3 * ti + 0] = ax;
-          r_acc[3 * ti + 1] = ay;
-          r_acc[3 * ti + 2] = az;
-          r_nint[ti] = nint;
-        }
+      if(MODE != 1)
+        group_store(S, lane, valid, ti, ax, ay, az, nint, r_acc, r_nint);
     }
   if(MODE != 1 && lane == 0)
     {
-      unsigned long long *st64 = reinterpret_cast<unsigned long long *>(counter + 16);
 #pragma unroll
       for(int q = 0; q < 4; q++)
         if(acc_st[q])
-          atomicAdd(&st64[q], acc_st[q]);
+          atomicAdd(&counter->stats[q], acc_st[q]);
     }
   if(MODE == 0 && lane == 0 && acc_hd[1] != 0ull)
     {
-      unsigned long long *hd64 = reinterpret_cast<unsigned long long *>(counter + 26);
-      atomicAdd(&hd64[0], acc_hd[0]);
-      atomicAdd(&hd64[1], acc_hd[1]);
+      atomicAdd(&counter->head[0], acc_hd[0]);
+      atomicAdd(&counter->head[1], acc_hd[1]);
     }
 }
 
@@ -2488,7 +2428,7 @@ static int launch_strict(Row<NG, PM, LATT, USER, ADA>, ngravs_ctx *c, const Walk
 {
   hipLaunchKernelGGL((k_walk_strict<NG, PM, LATT, USER, ADA>), strict_grid(c->shard_count), dim3(256), 0, c->stream, tree_view(c), c->s_pm.p, c->s_type.p,
                      c->s_oldacc.p, c->s_active.p, LATT ? c->lat.p : c->table.p, wp, li, (long long)c->shard_first,
-                     (long long)c->shard_count, c->r_acc.p, c->r_nint.p, c->walk_counters.p + 1);
+                     (long long)c->shard_count, c->r_acc.p, c->r_nint.p, &c->walk_counters.p->err);
   return NGRAVS_OK;
 }
 
@@ -2580,17 +2520,17 @@ static int walk_select_targets(ngravs_ctx *c)
   if((c->all_active && !imports) || c->shard_count <= 0 || !c->tune.walk_compact)
     return NGRAVS_OK;
   const int n = (int)c->shard_count;
-  if(c->walk_tlist.ensure((size_t)n) || c->walk_counters.ensure(32))
+  if(c->walk_tlist.ensure((size_t)n) || c->walk_counters.ensure(1))
     return NGRAVS_ERR_NOMEM;
   hipcub::CountingInputIterator<int> idx((int)c->shard_first);
   hipcub::TransformInputIterator<bool, ActiveFlag, const unsigned char *> flags(c->s_active.p + c->shard_first, ActiveFlag());
   size_t bytes = 0;
-  HIP_TRY(c, hipcub::DeviceSelect::Flagged(nullptr, bytes, idx, flags, c->walk_tlist.p, c->walk_counters.p + 24, n, c->stream));
+  HIP_TRY(c, hipcub::DeviceSelect::Flagged(nullptr, bytes, idx, flags, c->walk_tlist.p, &c->walk_counters.p->ntargets, n, c->stream));
   if(c->walk_tmp.ensure(bytes))
     return NGRAVS_ERR_NOMEM;
-  HIP_TRY(c, hipcub::DeviceSelect::Flagged(c->walk_tmp.p, bytes, idx, flags, c->walk_tlist.p, c->walk_counters.p + 24, n, c->stream));
+  HIP_TRY(c, hipcub::DeviceSelect::Flagged(c->walk_tmp.p, bytes, idx, flags, c->walk_tlist.p, &c->walk_counters.p->ntargets, n, c->stream));
   int cnt = 0;
-  HIP_TRY(c, hipMemcpyAsync(&cnt, c->walk_counters.p + 24, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(&cnt, &c->walk_counters.p->ntargets, sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   if(4ll * cnt < 3ll * n || imports)
     c->walk_ntargets = cnt;
@@ -2620,9 +2560,9 @@ struct EvalLds
 };
 static EvalLds eval_lds(const WalkParams &wp, bool tables, int max_waves, bool ada = false)
 {
-  const size_t fixed = (tables ? sizeof(double) * (wp.ntab_lds + wp.exp_tab) * NTAB : 0) + 40 * sizeof(double);
+  const size_t fixed = (tables ? sizeof(double) * (wp.ntab_lds + wp.exp_tab) * NTAB : 0) + WALK_LDS_CONST;
   const size_t per_wave = ada ? GW2_WAVE_LDS_ADA : GW2_WAVE_LDS;
-  int waves = (int)((160 * 1024 - fixed) / per_wave);
+  int waves = (int)((WALK_LDS_BUDGET - fixed) / per_wave);
   if(waves > max_waves)
     waves = max_waves;
   if(waves < 1)
@@ -2630,9 +2570,7 @@ static EvalLds eval_lds(const WalkParams &wp, bool tables, int max_waves, bool a
   return {waves, fixed + (size_t)waves * per_wave};
 }
 
-// hipFuncAttributeMaxDynamicSharedMemorySize of a walk kernel: set when the kernel is first launched with this size, not on every
-// step (the call takes the runtime's locks in front of the step's first walk launch)
-static int walk_dyn_lds(ngravs_ctx *c, const void *kern, size_t lds)
+int walk_dyn_lds(ngravs_ctx *c, const void *kern, size_t lds)
 {
   for(auto &e : c->walk_lds_set)
     if(e.first == kern)
@@ -2671,18 +2609,18 @@ static int launch_group2_t(Row<NG, PM, YUK, TAB_LDS, LATT, USR, ADA>, ngravs_ctx
     nblk = (ngroups + waves - 1) / waves;
   if(nblk < 1)
     nblk = 1;
-  if(c->walk_stack.ensure((size_t)nblk * waves * (GW_STACK + (size_t)NG * GW2_ITEMS)) || c->walk_counters.ensure(32))
+  if(c->walk_stack.ensure((size_t)nblk * waves * (GW_STACK + (size_t)NG * GW2_ITEMS)) || c->walk_counters.ensure(1))
     return NGRAVS_ERR_NOMEM;
   if(glist)   // second pass of a split walk: keep its statistics, restart the per-XCD group counters
-    HIP_TRY(c, hipMemsetAsync(c->walk_counters.p + 8, 0, sizeof(int) * 8, c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->walk_counters.p->xcd_next, 0, sizeof(WalkCounters::xcd_next), c->stream));
   else
-    HIP_TRY(c, hipMemsetAsync(c->walk_counters.p, 0, sizeof(int) * 32, c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->walk_counters.p, 0, sizeof(WalkCounters), c->stream));
   auto kern = k_walk_group2<NG, PM, YUK, TAB_LDS, LATT, 0, USR, ADA>;
   if(int rl = walk_dyn_lds(c, reinterpret_cast<const void *>(kern), lds))
     return rl;
   hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(waves * 64), lds, c->stream, tree_view(c), c->s_pm.p,
                      c->s_type.p, c->s_oldacc.p, c->s_active.p, LATT ? c->lat.p : c->table.p, wp, (long long)c->shard_first,
-                     walk_tcount(c), c->walk_counters.p, c->walk_stack.p, c->walk_counters.p + 1, c->r_acc.p,
+                     walk_tcount(c), c->walk_counters.p, c->walk_stack.p, &c->walk_counters.p->err, c->r_acc.p,
                      c->r_nint.p, (int *)nullptr, (int *)nullptr, 0ll, glist ? (long long)nlist : 0ll, 0, 0, glist, S, G0, walk_tlist(c), 1);
   return NGRAVS_OK;
 }
@@ -2777,11 +2715,11 @@ static int launch_group3_t(Row<NG, PM, YUK, TAB_LDS, LATT, USR, ADA>, ngravs_ctx
     batch = nunits;
   if(batch < 1)
     batch = 1;
-  if(c->walk_stack.ensure((size_t)batch * (region_ints + NG + 2)) || c->walk_counters.ensure(32) ||
+  if(c->walk_stack.ensure((size_t)batch * (region_ints + NG + 2)) || c->walk_counters.ensure(1) ||
      c->walk_ovf.ensure((size_t)nunits))
     return NGRAVS_ERR_NOMEM;
   int *region = c->walk_stack.p, *gcount = c->walk_stack.p + (size_t)batch * region_ints;
-  HIP_TRY(c, hipMemsetAsync(c->walk_counters.p, 0, sizeof(int) * 32, c->stream));
+  HIP_TRY(c, hipMemsetAsync(c->walk_counters.p, 0, sizeof(WalkCounters), c->stream));
   auto kt = k_walk_group2<NG, PM, YUK, TAB_LDS, LATT, 1, USR, ADA>;
   auto ke = k_walk_group2<NG, PM, YUK, TAB_LDS, LATT, 2, USR, ADA>;
   if(int rl = walk_dyn_lds(c, reinterpret_cast<const void *>(ke), lds))
@@ -2815,11 +2753,11 @@ static int launch_group3_t(Row<NG, PM, YUK, TAB_LDS, LATT, USR, ADA>, ngravs_ctx
       const long long tblk = 8 * (((nbu + GW3_TBLOCK / 64 - 1) / (GW3_TBLOCK / 64) + 7) / 8);
       hipLaunchKernelGGL(kt, dim3((unsigned)tblk), dim3(GW3_TBLOCK), 0, c->stream, tree_view(c), c->s_pm.p, c->s_type.p,
                          c->s_oldacc.p, c->s_active.p, LATT ? c->lat.p : c->table.p, wp, (long long)c->shard_first,
-                         walk_tcount(c), c->walk_counters.p, (int *)nullptr, c->walk_counters.p + 1, c->r_acc.p,
+                         walk_tcount(c), c->walk_counters.p, (int *)nullptr, &c->walk_counters.p->err, c->r_acc.p,
                          c->r_nint.p, region, gcount, u0, nbu, lcap, scap, c->walk_ovf.p, S, G, walk_tlist(c), SG);
       HIP_TRY(c, hipEventRecord(c->ev_batch[3 * ib + 1], c->stream));
       if(g0 > 0)
-        HIP_TRY(c, hipMemsetAsync(c->walk_counters.p + 8, 0, sizeof(int) * 8, c->stream));
+        HIP_TRY(c, hipMemsetAsync(c->walk_counters.p->xcd_next, 0, sizeof(WalkCounters::xcd_next), c->stream));
       long long nblk = ncu;
       if(nblk > (nb + waves - 1) / waves)
         nblk = (nb + waves - 1) / waves;
@@ -2834,7 +2772,7 @@ static int launch_group3_t(Row<NG, PM, YUK, TAB_LDS, LATT, USR, ADA>, ngravs_ctx
       else
       hipLaunchKernelGGL(ke, dim3((unsigned)nblk), dim3(waves * 64), lds, c->stream, tree_view(c), c->s_pm.p, c->s_type.p,
                          c->s_oldacc.p, c->s_active.p, LATT ? c->lat.p : c->table.p, wp, (long long)c->shard_first,
-                         walk_tcount(c), c->walk_counters.p, (int *)nullptr, c->walk_counters.p + 1, c->r_acc.p,
+                         walk_tcount(c), c->walk_counters.p, (int *)nullptr, &c->walk_counters.p->err, c->r_acc.p,
                          c->r_nint.p, region, gcount, g0, nb, lcap, scap, c->walk_ovf.p, S, G, walk_tlist(c), SG);
       HIP_TRY(c, hipEventRecord(c->ev_batch[3 * ib + 2], c->stream));
     }
@@ -2954,8 +2892,8 @@ static int walk_spread_choice(const ngravs_ctx *c, const WalkParams &wp, bool la
 // flag word and the four statistics sums of the walk kernels, after they have finished
 static int walk_read_back(ngravs_ctx *c, int *flag, unsigned long long (&st64)[4])
 {
-  HIP_TRY(c, hipMemcpyAsync(flag, c->walk_counters.p + 1, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(st64, c->walk_counters.p + 16, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(flag, &c->walk_counters.p->err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(st64, c->walk_counters.p->stats, sizeof(WalkCounters::stats), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return NGRAVS_OK;
 }
@@ -3106,9 +3044,9 @@ int walk_enqueue(ngravs_ctx *c)
   bool used_split = false;
   if(strict)
     {
-      if(c->walk_counters.ensure(32))
+      if(c->walk_counters.ensure(1))
         return NGRAVS_ERR_NOMEM;
-      HIP_TRY(c, hipMemsetAsync(c->walk_counters.p, 0, sizeof(int) * 32, c->stream));
+      HIP_TRY(c, hipMemsetAsync(c->walk_counters.p, 0, sizeof(WalkCounters), c->stream));
       c->last_walk_kernel = c->gsoft_on ? NGRAVS_KERNEL_STRICT_ADAPTIVE : (wp.user ? NGRAVS_KERNEL_STRICT_USER : NGRAVS_KERNEL_STRICT);
       const int key[] = {c->cfg.n_gravs, pm, latt, wp.user != 0, c->gsoft_on ? 1 : 0};
       rc = dispatch(c, StrictRows{}, key, [&](auto row) { return launch_strict(row, c, wp, li); });
@@ -3138,7 +3076,7 @@ int walk_complete(ngravs_ctx *c)
   if(strict && c->top.on)
     {
       int flag = 0;
-      HIP_TRY(c, hipMemcpyAsync(&flag, c->walk_counters.p + 1, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipMemcpyAsync(&flag, &c->walk_counters.p->err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
       HIP_TRY(c, hipStreamSynchronize(c->stream));
       if(flag & 4)
         {
@@ -3160,8 +3098,8 @@ int walk_complete(ngravs_ctx *c)
           // group tests open most of the tree: exactly those groups are redone by the fused kernel in sub-groups (one
           // target per wave if they are few: the box is then the target itself and every test the reference's own).
           // If they are many the regions grow for the following steps.
-          int ovf[2] = {0, 0};
-          HIP_TRY(c, hipMemcpy(ovf, c->walk_counters.p + 2, 2 * sizeof(int), hipMemcpyDeviceToHost));
+          int ovf[2] = {0, 0};   // overflowed, overflowed_lifo: neighbours, one copy
+          HIP_TRY(c, hipMemcpy(ovf, &c->walk_counters.p->overflowed, 2 * sizeof(int), hipMemcpyDeviceToHost));
           if(ovf[0] > 0)
             {
               rc = launch_group(c, wp, nullptr, c->walk_ovf.p, ovf[0]);
@@ -3201,10 +3139,10 @@ int walk_complete(ngravs_ctx *c)
       c->stats.reserved[5] = c->walk_batches;
       {
         int unop = 0;
-        HIP_TRY(c, hipMemcpy(&unop, c->walk_counters.p + 4, sizeof(int), hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(&unop, &c->walk_counters.p->unopened, sizeof(int), hipMemcpyDeviceToHost));
         c->walk_unopened = unop;
         unsigned long long hd64[2] = {0, 0};
-        HIP_TRY(c, hipMemcpy(hd64, c->walk_counters.p + 26, sizeof(hd64), hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(hd64, c->walk_counters.p->head, sizeof(hd64), hipMemcpyDeviceToHost));
         c->walk_moment_skips = (long long)hd64[0];
         c->walk_head_survivors = (long long)hd64[1];
       }

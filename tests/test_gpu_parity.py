@@ -1142,15 +1142,20 @@ def test_group_walk_unequal_softenings(pkg, O):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("wiring,ng,pmgrid,soft", [("newton", 1, 32, "one"), ("newton", 1, 256, "one"), ("c4", 2, 64, "one"), ("c4", 2, 256, "one"),
-                                                   ("c4", 3, 256, "one"), ("c4", 2, 256, "two"), ("newton", 1, 256, "two")])
-def test_ring_pool_kernel_is_the_synchronous_kernel(pkg, wiring, ng, pmgrid, soft):
+@pytest.mark.parametrize("wiring,ng,pmgrid,soft,every", [
+    pytest.param(*c, id="%s-%d-%d-%s" % c[:4] + ("-every%d" % c[4] if c[4] else "")) for c in
+    [("newton", 1, 32, "one", 0), ("newton", 1, 256, "one", 0), ("c4", 2, 64, "one", 0), ("c4", 2, 256, "one", 0), ("c4", 3, 256, "one", 0),
+     ("c4", 2, 256, "two", 0), ("newton", 1, 256, "two", 0), ("c4", 2, 16, "one", 33)]])
+def test_ring_pool_kernel_is_the_synchronous_kernel(pkg, wiring, ng, pmgrid, soft, every):
     """The ring-pool evaluation kernel (kernels_eval.hip: per-lane cursors, trip loop / cull in assembly) against the synchronous one
     (k_walk_group2<..., 2>, tuning walk_ring = 0) on the same item lists: identical interaction counts for every particle, forces to
     rounding (the two sum a target's pairs in different orders).  The cases walk through the kernel's variants: with / without a
     Yukawa law, the Yukawa factor through the table bins (PMGRID 256: ym * bin width < 1e-3) or through exp(), one softening length
     (assembly cull) or two (type bytes), both opening criteria, 5 / 6 / 4 ring slots.  (PMGRID 256 without a Yukawa law is the C3
-    bench's case: its exp table is not staged, the softening lengths sit right behind the tables.)"""
+    bench's case: its exp table is not staged, the softening lengths sit right behind the tables.)
+    every 33: every 33rd particle is active and PMGRID is 16, so that the walk compacts the targets and most groups of 64 of them
+    span a box too wide to wrap the sources once per group (bhmax >= boxhalf - reach): the per-pair image branch of the wrap
+    decision the kernels share, in the ring kernel, the synchronous one and the fused one (walk_fused 1), one lane per target."""
     n, L = 60000, 1.0
     pos, mass, typ = pkg.ic.uniform_box(n, box=L, n_gravs=ng, seed=91)
     pos[: n // 3] = np.mod(0.4 + 0.04 * np.random.default_rng(5).standard_normal((n // 3, 3)), 1.0)   # a clump: softened pairs
@@ -1158,6 +1163,13 @@ def test_ring_pool_kernel_is_the_synchronous_kernel(pkg, wiring, ng, pmgrid, sof
     softening = [eps] * 6 if soft == "one" else [eps, eps, 2.5 * eps, eps, 1.7 * eps, eps]
     out = {}
     variants = [("sync", {"walk_ring": 0}), ("ring", {}), ("ring4", {"walk_ring_k": 4})]
+    active = None
+    if every:
+        active = np.zeros(n, dtype=np.uint8)
+        active[::every] = 1
+        # (lists as long as a unit's can get: no group is left to the leftover pass, which is the fused kernel's)
+        base = {"walk_spread": 1, "walk_lcap": 65536}
+        variants = [("sync", dict(base, walk_ring=0)), ("ring", base), ("fused", dict(base, walk_fused=1))]
     if (wiring, ng, pmgrid, soft) == ("c4", 2, 256, "two"):
         # two / four lanes per target (walk_spread: what the library chooses for strongly clustered sets): the S lanes of a target share the
         # entries of every block, each against the synchronous kernel with the same spread
@@ -1166,22 +1178,38 @@ def test_ring_pool_kernel_is_the_synchronous_kernel(pkg, wiring, ng, pmgrid, sof
     for name, tune in variants:
         cfg = pkg.make_config(n_gravs=ng, periodic=1, pmgrid=pmgrid, box_size=L, G=1.0, theta=0.5, softening=softening,
                               type_to_grav=pkg.ic.default_type_to_grav(ng), wiring=wiring, walk_mode=pkg.WALK_GROUP)
-        eng = _engine(pkg, cfg, pos, mass, typ, tuning=tune)
+        eng = _engine(pkg, cfg, pos, mass, typ, tuning=tune, active=active)
         eng.compute_accelerations(pm_step=True)
         a1, o1, c1 = eng.get_accel()
+        if every and name == "sync":
+            # the case is about groups with a wide box: the share of them among the groups of 64 compacted targets
+            t = eng.order()
+            t = t[active[t] != 0]
+            reach = 4.5 * pkg.abi.ASMTH * L / pmgrid   # (4.5: NGRAVS_GROUP_REACH of ngravs_hip.h, the default group_reach)
+            wide = [0.5 * np.ptp(pos[t[k:k + 64]], axis=0).max() >= 0.5 * L - reach for k in range(0, len(t), 64)]
+            print("sparse: %d active targets, %d groups, %.2f of them with bhmax >= boxhalf - reach" % (len(t), len(wide), np.mean(wide)))
+            assert np.mean(wide) >= 0.5
         eng.set_old_acc(o1)
         eng.set_opening(0.0, 0.005)
         eng.gravity_tree()
         a2, _, c2 = eng.get_accel()
         out[name] = (a1, c1, a2, c2, eng.stats().reserved[3])
         eng.close()
-    for name, ref in [("ring", "sync"), ("ring4", "sync")] + [(v[0], "sync" + v[0][4:]) for v in variants if v[0].startswith("ring_s")]:
+    pairs = [("ring", "sync"), ("ring4", "sync")] + [(v[0], "sync" + v[0][4:]) for v in variants if v[0].startswith("ring_s")]
+    if every:
+        pairs = [("ring", "sync"), ("fused", "sync")]
+    for name, ref in pairs:
         r, s = out[name], out[ref]
+        rows = slice(None) if active is None else active != 0     # (inactive rows: all zero, asserted below)
         for k in (0, 2):
-            na = np.linalg.norm(s[k], axis=1)       # (a particle with nothing inside the cut has no short-range force at all)
-            e = np.linalg.norm(r[k] - s[k], axis=1) / np.maximum(na, 1e-6 * np.median(na))
+            na = np.linalg.norm(s[k][rows], axis=1)       # (a particle with nothing inside the cut has no short-range force at all)
+            e = np.linalg.norm((r[k] - s[k])[rows], axis=1) / np.maximum(na, 1e-6 * np.median(na))
             print("%s %s ng %d pmgrid %d %s: pass %d max |da|/|a| %.1e, trips per group %.1f (synchronous %.1f)" %
                   (name, wiring, ng, pmgrid, soft, k // 2 + 1, e.max(), r[4], s[4]))
             assert np.array_equal(r[k + 1], s[k + 1])
             assert e.max() < 1e-11
-        assert r[4] < s[4]
+            if active is not None:
+                assert np.all(r[k][active == 0] == 0) and np.all(s[k][active == 0] == 0) and np.all(s[k + 1][active == 0] == 0)
+                assert np.all(s[k + 1][active != 0] > 0)
+        if name != "fused":   # (the fused kernel evaluates in synchronous blocks too)
+            assert r[4] < s[4]
